@@ -2,7 +2,12 @@
 """bench.py — CTR examples/sec of one training step (forward + backward + TF1-Adam) of the hot
 path on synthetic WeChat-shaped data: 26 sparse fields x emb 16, batch 4096 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--model dcn|deepfm|xdeepfm|din]
+    python bench.py --gpus N --steps K --warmup W [--model dcn|deepfm|xdeepfm|din] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the
+benchmark measures: the per-kernel roofline table, the 400-step percentile run, the optimizer-state sweep, the box
+check, the DeepFM / xDeepFM / DIN lines of the default command, the host-fed leg and the CPU baseline.
+`--dump-outputs DIR` writes what the timed step computed in its last step (loss and variables) as .npy files.
 
 N > 1 is launched by the driver as
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
@@ -78,7 +83,14 @@ def parse_args(argv=None):
                          "reference scripts default to 0.1, deepfm.py:39).  Default 0 = BASELINE.json's parity configuration; a run "
                          "with a rate > 0 says so in config.workload")
     ap.add_argument("--no-extra-models", action="store_true",
-                    help="default run (--model dcn, N = 1): skip the DeepFM / xDeepFM / DIN lines appended under `models`")
+                    help="--full run (--model dcn, N = 1): skip the DeepFM / xDeepFM / DIN lines appended under `models`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (per-kernel rooflines, percentile run, optimizer-"
+                         "state sweep, box check, extra models, host-fed leg, CPU baseline); the --no-* flags and "
+                         "--sweep-batches select among these.  Default: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its loss, the dense variables, a "
+                         "fixed seeded sample of every embedding table's rows) as DIR/<name>.npy, float32 / float64, < 64 MB")
     args = ap.parse_args(argv)
     if args.config5:
         args.model = "deepfm"
@@ -86,12 +98,14 @@ def parse_args(argv=None):
     return args
 
 
-def self_launch(args) -> None:
-    """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): re-exec under
-    torch.distributed.run, one rank per GPU of this node, rendezvous on 127.0.0.1 — so the command is self-contained and
-    the line it prints says "n_gpus": N because N ranks really ran.  Fails loudly when the node has fewer than N GPUs
-    (RECALGO_DIST_BACKEND=gloo_staged, the bring-up mode in which ranks share devices, is exempt)."""
+def self_launch(args) -> int:
+    """`python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): run this command again under
+    torch.distributed.run in a child process, one rank per GPU of this node, rendezvous on 127.0.0.1 — so the command is
+    self-contained and the line it prints says "n_gpus": N because N ranks really ran.  Returns the launcher's exit status.
+    Fails loudly when the node has fewer than N GPUs (RECALGO_DIST_BACKEND=gloo_staged, the bring-up mode in which ranks
+    share devices, is exempt)."""
     import socket
+    import subprocess
     staged = os.environ.get("RECALGO_DIST_BACKEND", "nccl") == "gloo_staged"
     have = torch.cuda.device_count()
     if have < args.gpus and not staged:
@@ -107,7 +121,7 @@ def self_launch(args) -> None:
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")        # dmabuf IPC: what RCCL needs between processes on this stack
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execvpe(sys.executable, cmd, env)
+    return subprocess.run(cmd, env=env).returncode
 
 
 def build_estimator(args, device, rank=0, world=1, before_build=None):
@@ -992,6 +1006,40 @@ def cpu_baseline(args, seconds):
     return a
 
 
+DUMP_LIMIT_BYTES = 48 << 20         # what --dump-outputs writes in all
+
+
+def dump_outputs(out_dir, est, loss, world, rank):
+    """--dump-outputs DIR: what a caller of the timed step holds after its last step — the loss it returned and every
+    variable it updated — as DIR/<name>.npy (the variable's name with '/' -> '.'; float32, the loss float64), so that two
+    builds can be compared output for output on the same inputs.  An array larger than its share of DUMP_LIMIT_BYTES is
+    written as a fixed sample of its rows: the first half of the share from its first rows (for an embedding table the
+    Zipf head, the rows the batches touch most), the rest a uniform sample of the other rows, seeded by the array's name.
+    N > 1: the sharded tables are gathered (every rank takes part), rank 0 writes."""
+    import re
+    import zlib
+    import numpy as np
+    arrays = est.store.named_arrays(gather=world > 1)         # (brings every row's deferred Adam updates up to date)
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name in sorted(arrays):
+        t = arrays[name].detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.double()
+        if t.numel() * t.element_size() > share:
+            rows = t.reshape(t.shape[0], -1) if t.dim() > 1 else t.reshape(-1, 1)
+            n = rows.shape[0]
+            keep = min(n, max(2, share // (rows.shape[1] * t.element_size())))
+            head = keep // 2
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = np.concatenate([np.arange(head), head + np.sort(rng.choice(n - head, keep - head, replace=False))])
+            t = rows[torch.from_numpy(idx).to(rows.device)]
+        np.save(os.path.join(out_dir, re.sub(r"[^A-Za-z0-9_.-]", ".", name) + ".npy"), t.cpu().numpy())
+
+
 def timed_run(args, device, rank, world, dist, capacity_factor):
     """Build the model on this rank, (N > 1) shard it, capture the step, warm up, time `steps` steps
     between barriers; returns the max-over-ranks wall time."""
@@ -1149,7 +1197,7 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a HIP device")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args)               # (does not return: the launcher's rank 0 prints the line)
+        raise SystemExit(self_launch(args))         # (the launcher's rank 0 prints the line)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1200,6 +1248,9 @@ def main():
         del r
         torch.cuda.empty_cache()
     est, spec, feats, workload, dt, loss_v, launch = (r[k] for k in ("est", "spec", "feats", "workload", "dt", "loss", "launch"))
+    if args.dump_outputs:
+        # before anything of --full runs more steps or launches on this state
+        dump_outputs(args.dump_outputs, est, loss_v, world, rank)
 
     out = {
         "metric": "CTR examples/sec (train step fwd+bwd+TF1-Adam), batch 4096/GPU, 26 fields x emb16",
@@ -1233,7 +1284,7 @@ def main():
     if r.get("comm"):
         out["rccl_ranks"] = r["comm"]["ranks_in_all_reduce"]
         out["communication"] = r["comm"]
-    if rank == 0:
+    if rank == 0 and args.full:
         out["box"] = box_sanity(device)
         out["box"]["host_cores"] = os.cpu_count()
         out["box"]["host_cpu_quota"] = cpu_quota()       # CPUs the cgroup lets the process USE (None: no quota); host_cores = hardware threads visible
@@ -1242,7 +1293,7 @@ def main():
         pick = lambda q: cs[min(len(cs) - 1, int(q * len(cs)))]
         out["ms_per_step_p10_p50_p90"] = [pick(0.1), pick(0.5), pick(0.9)]
     ks = None
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and args.full and not args.no_kernel_timing:
         # per-kernel table in the HEADLINE's state (before the optimizer-state sweep grows the live set); the repeated
         # lr = 0 optimizer launches decay the Adam moments, so those are put back afterwards
         snap = [(a, a.m.clone(), a.v.clone()) for a in est.store.arenas.values() if a.weight is not None]
@@ -1256,7 +1307,7 @@ def main():
         if fm is not None:
             est.store.flat_m.copy_(fm); est.store.flat_v.copy_(fv)
         del snap, fm, fv
-    if world == 1 and r["graphed"] is not None:
+    if args.full and world == 1 and r["graphed"] is not None:
         # real percentiles for the headline state (the driver's --steps 20 is ONE chunk): 400 more steps on the same
         # rotating batches, a HIP event after every step
         try:
@@ -1273,7 +1324,7 @@ def main():
         except Exception as e:
             print(f"[bench] percentile run failed ({type(e).__name__}: {e})", file=sys.stderr, flush=True)
     sweep = None
-    if args.sweep_batches > 0 and world == 1:
+    if args.full and args.sweep_batches > 0 and world == 1:
         try:
             sweep = optimizer_state_sweep(args, r, device, rank, world)
         except Exception as e:          # never take the headline line down
@@ -1333,7 +1384,7 @@ def main():
             out["step_hbm"] = {"alg_bytes_hot_path_kernels": int(hb), "ms_per_step": out["ms_per_step"],
                                "achieved_GBs": round(hb / (out["ms_per_step"] * 1e-3) / 1e9, 1),
                                "frac_of_peak": round(hb / (out["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-        if args.model == "dcn" and world == 1 and not args.no_extra_models and not args.big_table_rows:
+        if args.full and args.model == "dcn" and world == 1 and not args.no_extra_models and not args.big_table_rows:
             # the other three models BASELINE.json's target names, each its own build / capture / timed run in this process
             del est, r
             torch.cuda.empty_cache()
@@ -1347,9 +1398,9 @@ def main():
                 except Exception as e:      # never take the headline line down
                     out["models"].append({"model": name, "error": f"{type(e).__name__}: {e}"})
                 torch.cuda.empty_cache()
-        if not args.no_host_fed and world == 1 and args.model == "dcn" and not args.big_table_rows:
+        if args.full and not args.no_host_fed and world == 1 and args.model == "dcn" and not args.big_table_rows:
             out["host_fed"] = host_fed(args)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -121,7 +121,8 @@ def test_bench_two_rank_code_path(capacity_factor):
     env = dict(os.environ, RECALGO_DIST_BACKEND="gloo_staged", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "4", "--warmup", "4", "--batch", "512",
-           "--max-vocab", "20000", "--data-batches", "3", "--no-tunable", "--no-cpu-baseline", "--no-host-fed", "--capacity-factor", capacity_factor]
+           "--max-vocab", "20000", "--data-batches", "3", "--no-tunable", "--no-cpu-baseline", "--no-host-fed", "--capacity-factor", capacity_factor,
+           "--full"]                                                   # (the per-kernel table: `roofline`)
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
