@@ -601,11 +601,13 @@ __global__ __launch_bounds__(256) void concat_sumsq_kernel(CatArgs A) {
 }  // namespace
 
 RECALGO_EXPORT int64_t recalgo_concat_sumsq_workspace_bytes(int B) {
-    return B > 0 ? (int64_t)(cdiv(B, 16) + 16) * 4 : 64;
+    // ticket word + padding to word 16, then one partial per workgroup (B == 0 still launches one workgroup)
+    return (int64_t)((B > 0 ? cdiv(B, 16) : 1) + 16) * 4;
 }
 RECALGO_EXPORT int recalgo_concat_sumsq(const float* const* parts, const int* widths, int n_parts, int B, float* out,
                                         float scale, float* sum_out, void* workspace, recalgo_stream_t stream) {
-    RECALGO_REQUIRE(parts && widths && n_parts >= 1 && n_parts <= kCatMaxParts && B >= 0 && out && sum_out && workspace);
+    // (an empty batch has no rows to copy: its parts and `out` may be null; the sum is still written)
+    RECALGO_REQUIRE(parts && widths && n_parts >= 1 && n_parts <= kCatMaxParts && B >= 0 && (out || B == 0) && sum_out && workspace);
     CatArgs A;
     int C = 0;
     for (int p = 0; p < kCatMaxParts; ++p) {
@@ -613,7 +615,7 @@ RECALGO_EXPORT int recalgo_concat_sumsq(const float* const* parts, const int* wi
         A.width[p] = p < n_parts ? widths[p] : 0;
         A.off[p] = C;
         if (p < n_parts) {
-            RECALGO_REQUIRE(parts[p] != nullptr && widths[p] >= 1);
+            RECALGO_REQUIRE((parts[p] != nullptr || B == 0) && widths[p] >= 1);
             C += widths[p];
         }
     }
