@@ -37,7 +37,7 @@ typedef void* recalgo_stream_t; /* hipStream_t */
 
 /* ABI version of this header (bumped on any signature change).  include/recalgo.abi records the hash of the declarations
  * each version stands for; tests/test_abi.py fails when the declarations change and this number does not. */
-#define RECALGO_ABI_VERSION 3
+#define RECALGO_ABI_VERSION 4
 int recalgo_abi_version(void);
 /* "gfx950" */
 const char* recalgo_target_arch(void);
@@ -90,11 +90,9 @@ int recalgo_scatter_rows_sorted(const int64_t* sorted_rows, const int64_t* perm,
  * algorithm/DCN/dcn.py:95,98,103 (`manual_tag_list`, shared `his_read_comment_7d_seq`).
  *   out[b, out_col:+K] = mean over valid (>=0) values of bag b of table[value, :], 0 if none.
  *   values [nnz] int64, offsets [B+1] int64, table = arena + row_base*K.
- * The sum runs sequentially in bag order in fp32 (TF SparseSegmentMean order).
+ * The sum runs sequentially in bag order in fp32 (TF SparseSegmentMean order).  The forward is
+ * recalgo_embedding_bag_mean_fwd_deferred (with deferred = NULL: the plain lookup).
  * ------------------------------------------------------------------------------------------ */
-int recalgo_embedding_bag_mean_fwd(const int64_t* values, const int64_t* offsets, const float* table,
-                                   int B, int K, float* out, int out_stride, int out_col,
-                                   recalgo_stream_t stream);
 int recalgo_embedding_bag_mean_bwd(const int64_t* values, const int64_t* offsets, const float* g,
                                    int B, int K, int g_stride, int g_col, float* grad_table,
                                    const recalgo_live_t* live, recalgo_stream_t stream);
@@ -359,6 +357,30 @@ int64_t recalgo_relu_bwd_bias_workspace_bytes(int rows, int C);
 int recalgo_relu_bwd_bias(const float* g, const float* y, int rows, int C, float* g_out, float* dbias,
                           void* workspace, recalgo_stream_t stream);
 /* ------------------------------------------------------------------------------------------
+ * tf.layers.dropout(x, rate, training=True): y = x * keep / (1 - rate), keep ~ Bernoulli(1 - rate) per element
+ * (algorithm/DeepFM/deepfm.py:208-209 — dropout_rate defaults to 0.1, :39; DIN/din.py:235-236; FiBiNET/fibinet.py:193-194;
+ * PNN/pnn.py:188-189; NFM/nfm.py:170).  The keep decision of flat element i is a counter-based hash of (seed, call, *step, i)
+ * (csrc/dropout.h) — `seed` the variable store's (+ rank), `call` the index of the dropout call inside the model_fn, `step` the
+ * optimizer's device-side int64 step counter (NULL: 0), read at run time so that a captured step draws a new mask per replay —
+ * or, keep_mask != NULL, the explicit mask (1 = keep, 0 = drop; parity tests replay the masks of the reference run).  No mask
+ * is stored: the backward is recalgo_dropout_fwd applied to the gradient with the same key.  recalgo_dropout_keep_mask writes the
+ * mask the hash stands for (tests, debugging).  n < 2^32 elements; pointers 16-byte aligned; 0 < rate < 1 (a double: TF forms
+ * 1 / (1 - rate) from the Python float and casts it to x.dtype once). */
+/* One training-mode dropout call applied by its NEIGHBOURS instead of by launches of its own (the `drop` arguments of
+ * recalgo_dense_fwd, recalgo_batchnorm_apply and recalgo_batchnorm_train_bwd; NULL: none).  Element index = row * width + column
+ * of the contiguous [rows, width] tensor, the index space of recalgo_dropout_fwd. */
+typedef struct recalgo_dropout {
+    double rate;
+    const float* keep_mask;        /* NULL: the hash */
+    unsigned seed, call;
+    const int64_t* step;           /* device step counter, NULL: 0 */
+} recalgo_dropout_t;
+int recalgo_dropout_fwd(const float* x, int64_t n, double rate, const float* keep_mask, unsigned seed, unsigned call,
+                        const int64_t* step, float* y, recalgo_stream_t stream);
+int recalgo_dropout_keep_mask(int64_t n, double rate, unsigned seed, unsigned call, const int64_t* step, float* out,
+                              recalgo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * tf.layers.dense on the fp32 matrix cores (csrc/dense.hip; v_mfma_f32_32x32x2_f32: exact fp32, a
  * k-ordered fmaf chain).  Replaces `tf.layers.dense(x, units, activation=relu)` of every model_fn
  * (algorithm/DCN/dcn.py:163-166, DeepFM/deepfm.py:206-208, xDeepFM/xdeepfm.py:178-181, DIN/din.py:226-227,
@@ -379,49 +401,46 @@ int recalgo_relu_bwd_bias(const float* g, const float* y, int rows, int C, float
  *                workspace until then).
  * The masked gradient g (.) [y > 0] is applied while tiles are staged and never materialised.
  * ------------------------------------------------------------------------------------------ */
-int recalgo_dense_fwd(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2, const float* w2, int K2,
-                      const float* bias, int M, int N, int relu, float* y, int ldy, recalgo_stream_t stream);
-/* recalgo_dense_fwd that ALSO leaves the batch moments of y for the BatchNorm layer that follows it (tf.layers.dense ->
- * [dropout 0] -> tf.layers.batch_normalization(training=True): deepfm.py:207-211, pnn.py:187-191, fibinet.py:192-196):
- * bn_partials [recalgo_batchnorm_partial_rows(M)][2 N] in the layout of recalgo_batchnorm_moments (per 64-row tile: column
- * means, then sums of squared deviations), written by the epilogue of the tile's workgroups — recalgo_batchnorm_apply then
- * runs without a moments pass over y.  bn_partials == NULL: recalgo_dense_fwd. */
-int recalgo_dense_fwd_bn(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2, const float* w2, int K2,
-                         const float* bias, int M, int N, int relu, float* y, int ldy, float* bn_partials,
-                         recalgo_stream_t stream);
-/* ... with the per-channel activation of DIN's fcn layers in between (tf.layers.dense -> dice | prelu ->
- * tf.layers.batch_normalization, /root/reference algorithm/DIN/din.py:262-266): z = x W + b is written to z [M][ldy] (the
- * activation's backward needs it), y = act(z, act_alpha) and bn_partials are the moments of y.  act_kind: RECALGO_ACT_PRELU /
- * RECALGO_ACT_DICE (needs bn_partials, relu == 0), or RECALGO_ACT_NONE: recalgo_dense_fwd_bn. */
+/* fwd, with the epilogue options for the layers that follow the GEMM (each off when NULL / RECALGO_ACT_NONE):
+ *   bn_partials  [recalgo_batchnorm_partial_rows(M)][2 N]: the batch moments of y for the training-mode BatchNorm that follows
+ *                (tf.layers.dense -> [dropout] -> tf.layers.batch_normalization: deepfm.py:207-211, pnn.py:187-191,
+ *                fibinet.py:192-196), in the layout of recalgo_batchnorm_moments (per 64-row tile: column means, then sums of
+ *                squared deviations) — recalgo_batchnorm_apply then runs without a moments pass over y.
+ *   act_kind     RECALGO_ACT_PRELU / RECALGO_ACT_DICE: the per-channel activation of DIN's fcn layers in between (tf.layers.dense
+ *                -> dice | prelu -> tf.layers.batch_normalization, din.py:262-266): z = x W + b is written to z [M][ldy] (the
+ *                activation's backward needs it), y = act(z, act_alpha) and bn_partials are the moments of y.  Needs bn_partials
+ *                and relu == 0.  RECALGO_ACT_NONE: act_alpha and z are unused.
+ *   drop         the training-mode dropout behind the layer (tf.layers.dense(relu) -> tf.layers.dropout [-> batch_normalization]):
+ *                the epilogue multiplies y by keep / (1 - rate) before the store and the BatchNorm tile moments.  ldy == N,
+ *                act_kind == RECALGO_ACT_NONE.  Its backward needs no mask of its own: y > 0 <=> relu > 0 and kept, so the
+ *                consumer that masks its input gradient with y (recalgo_batchnorm_train_bwd dx_relu) only scales it by
+ *                dx_scale = 1 / (1 - rate). */
 #define RECALGO_ACT_NONE (-1)
-int recalgo_dense_fwd_act_bn(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2, const float* w2,
-                             int K2, const float* bias, int M, int N, int relu, int act_kind, const float* act_alpha,
-                             float* z, float* y, int ldy, float* bn_partials, recalgo_stream_t stream);
+int recalgo_dense_fwd(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2, const float* w2, int K2,
+                      const float* bias, int M, int N, int relu, int act_kind, const float* act_alpha, float* z, float* y, int ldy,
+                      float* bn_partials, const recalgo_dropout_t* drop, recalgo_stream_t stream);
 int recalgo_dense_bwd_input(const float* g, int ldg, const float* y_mask, const float* w, int M, int N, int K,
                             const float* c_in, int ldc, float beta, float* dx, int lddx, int accumulate,
                             recalgo_stream_t stream);
 int64_t recalgo_dense_bwd_weights_workspace_bytes(int M, int K, int N);
 int recalgo_dense_bwd_weights(const float* x, int ldx, const float* g, int ldg, const float* y_mask, int M, int K, int N,
                               float* dw, float* dbias, void* workspace, int defer_reduce, recalgo_stream_t stream);
-/* bwd: both of the above in ONE launch (dx = ... + beta * c_in, no accumulate mode); same arguments, same results. */
+/* bwd: both of the above in ONE launch (dx = ... + beta * c_in, no accumulate mode); same arguments, same results.  Options
+ * (each off when NULL):
+ *   bn_partials  x IS the output of a training-mode BatchNorm (tf.layers.batch_normalization -> tf.layers.dense: deepfm.py:207-211,
+ *                din.py:262-266): the input-gradient tiles' epilogue also leaves the two column sums that BatchNorm's backward starts
+ *                with — bn_partials [recalgo_batchnorm_partial_rows(M)][2 K]: per 64-row tile colsum(dx) and colsum(dx * xhat),
+ *                xhat = (bn_x - bn_mean) * bn_rstd, bn_x [M][K] contiguous = that BatchNorm's INPUT — i.e. the partial rows of
+ *                recalgo_batchnorm_bwd_sums, so recalgo_batchnorm_bwd_apply (world 1) follows without a pass over dx and bn_x.
+ *   dx_relu_mask [M][ld_mask]: dx := dx_relu_mask > 0 ? dx : 0 before the beta * c_in term — the layer's input x when x IS the
+ *                ReLU output of the layer below (for units in hidden_units: net = tf.layers.dense(net, units, relu),
+ *                dcn.py:163-166): that layer's backward then receives g * [y > 0] ready-made and is called with y_mask == NULL
+ *                (no mask loads in its two GEMMs). */
 int recalgo_dense_bwd(const float* x, int ldx, const float* g, int ldg, const float* y_mask, const float* w, int M, int K,
                       int N, const float* c_in, int ldc, float beta, float* dx, int lddx, float* dw, float* dbias,
-                      void* workspace, int defer_reduce, recalgo_stream_t stream);
-/* recalgo_dense_bwd for a layer whose input x IS the output of a training-mode BatchNorm (tf.layers.batch_normalization ->
- * tf.layers.dense: deepfm.py:207-211, din.py:262-266): the input-gradient tiles' epilogue also leaves the two column sums
- * that BatchNorm's backward starts with — bn_partials [recalgo_batchnorm_partial_rows(M)][2 K]: per 64-row tile colsum(dx) and
- * colsum(dx * xhat), xhat = (bn_x - bn_mean) * bn_rstd, bn_x [M][K] contiguous = that BatchNorm's INPUT — i.e. the partial
- * rows of recalgo_batchnorm_bwd_sums, so recalgo_batchnorm_bwd_apply (world 1) follows without a pass over dx and bn_x.
- * bn_partials == NULL: recalgo_dense_bwd.
- * dx_relu_mask (may be NULL) [M][ld_mask]: dx := dx_relu_mask > 0 ? dx : 0 before the beta * c_in term — the layer's input x
- * when x IS the ReLU output of the layer below (for units in hidden_units: net = tf.layers.dense(net, units, relu),
- * dcn.py:163-166): that layer's backward then receives g * [y > 0] ready-made and is called with y_mask == NULL (no mask
- * loads in its two GEMMs). */
-int recalgo_dense_bwd_bn(const float* x, int ldx, const float* g, int ldg, const float* y_mask, const float* w, int M, int K,
-                         int N, const float* c_in, int ldc, float beta, float* dx, int lddx, float* dw, float* dbias,
-                         void* workspace, int defer_reduce, const float* bn_x, const float* bn_mean, const float* bn_rstd,
-                         float* bn_partials, const float* dx_relu_mask, int ld_mask, recalgo_stream_t stream);
-/* recalgo_dense_bwd_bn carrying RIDERS in the same launch: work of OTHER layers over the same M examples whose operands are ready
+                      void* workspace, int defer_reduce, const float* bn_x, const float* bn_mean, const float* bn_rstd,
+                      float* bn_partials, const float* dx_relu_mask, int ld_mask, recalgo_stream_t stream);
+/* recalgo_dense_bwd carrying RIDERS in the same launch: work of OTHER layers over the same M examples whose operands are ready
  * and which nothing in this launch depends on.  Either may be absent (r_x == NULL / c_x0 == NULL), not both.
  *   weight-gradient rider:  r_dw [r_K][r_N] = r_x^T r_g,  r_dbias [r_N] = colsum(r_g)   (r_g arrives masked: no mask is staged)
  *       as recalgo_dense_bwd_weights(r_x, r_ldx, r_g, r_ldg, NULL, M, r_K, r_N, r_dw, r_dbias, r_workspace, defer_reduce = 1, ..):
@@ -472,43 +491,42 @@ int recalgo_dense_bwd_weights_reduce(const recalgo_dense_split_t* jobs, int n_jo
  *   moving_mean/var <- moving * momentum + batch * (1 - momentum)   (updated in place; may be NULL)
  *   save_mean, save_rstd [C] are kept for the backward, which returns
  *   dbeta = colsum(g), dgamma = colsum(g * xhat), dx = gamma * rstd / rows * (rows*g - dbeta - xhat*dgamma).
- * workspace: recalgo_batchnorm_workspace_bytes(rows, C) for both directions.  C % 4 == 0; x, y, g, dx and every [C]
- * vector 16-byte aligned.  Two launches each way (per-tile moments / partial sums, then merge + apply). */
-int64_t recalgo_batchnorm_workspace_bytes(int rows, int C);
-int recalgo_batchnorm_train_fwd(const float* x, const float* gamma, const float* beta, int rows, int C,
-                                float eps, float momentum, float* moving_mean, float* moving_var,
-                                float* y, float* save_mean, float* save_rstd, void* workspace,
-                                recalgo_stream_t stream);
-/* dx_relu != 0 (the three backward entry points): x IS the output of a ReLU (tf.layers.dense(..., relu) ->
- * tf.layers.batch_normalization, deepfm.py:206-211) — dx is zeroed where x <= 0, i.e. the dense layer's backward receives
- * g * [y > 0] ready-made and runs without mask loads (see recalgo_dense_bwd_bn). */
-int recalgo_batchnorm_train_bwd(const float* x, const float* gamma, const float* save_mean,
-                                const float* save_rstd, const float* g, int rows, int C, float* dx,
-                                float* dgamma, float* dbeta, void* workspace, int dx_relu, recalgo_stream_t stream);
-/* The same backward, continued through the per-channel activation that produced x = act(act_z, act_alpha) (DIN's dense ->
- * dice | prelu -> batch_norm, din.py:262-266; see recalgo_activation_bwd): dx is then dL/d(act_z), dalpha [C] = dL/d(alpha).
- * dalpha == NULL: the recalgo_batchnorm_partial_rows(rows) partial rows [C] of dalpha are left at float offset
- * partial_rows * 2 * C of the workspace for the caller to sum (a job of recalgo_dense_bwd_weights_reduce).
- * workspace: recalgo_batchnorm_bwd_act_workspace_bytes(rows, C).  act_kind == RECALGO_ACT_NONE: recalgo_batchnorm_train_bwd.
- * sums (or NULL): the [partial_rows][2 C] rows (colsum g | colsum g * xhat per 64-row tile) when the kernel that produced g has
- * already left them (recalgo_dense_bwd_bn) — the first of the two launches is then skipped. */
-int64_t recalgo_batchnorm_bwd_act_workspace_bytes(int rows, int C);
-int recalgo_batchnorm_train_bwd_act(const float* x, const float* gamma, const float* save_mean, const float* save_rstd,
-                                    const float* g, const float* sums, int rows, int C, int act_kind, const float* act_z, const float* act_alpha,
-                                    float* dx, float* dgamma, float* dbeta, float* dalpha, void* workspace, int dx_relu,
-                                    recalgo_stream_t stream);
+ * C % 4 == 0; x, y, g, dx and every [C] vector 16-byte aligned.  Two launches each way (per-tile moments / partial sums, then
+ * merge + apply): the forward is recalgo_batchnorm_moments -> recalgo_batchnorm_apply (world 1), below.
+ * recalgo_batchnorm_train_bwd options (each off when NULL / 0 / RECALGO_ACT_NONE / 1.0):
+ *   sums      the [partial_rows][2 C] rows (colsum g | colsum g * xhat per 64-row tile) when the kernel that produced g has
+ *             already left them (recalgo_dense_bwd bn_partials) — the first of the two launches is then skipped.
+ *   act_kind  RECALGO_ACT_PRELU / RECALGO_ACT_DICE: the backward continues through the per-channel activation that produced
+ *             x = act(act_z, act_alpha) (DIN's dense -> dice | prelu -> batch_norm, din.py:262-266; see recalgo_activation_bwd):
+ *             dx is then dL/d(act_z), dalpha [C] = dL/d(alpha).  dalpha == NULL: the recalgo_batchnorm_partial_rows(rows) partial
+ *             rows [C] of dalpha are left at float offset partial_rows * 2 * C of the workspace for the caller to sum (a job of
+ *             recalgo_dense_bwd_weights_reduce).
+ *   dx_relu   x IS the output of a ReLU (tf.layers.dense(..., relu) -> tf.layers.batch_normalization, deepfm.py:206-211) — dx is
+ *             zeroed where x <= 0, i.e. the dense layer's backward receives g * [y > 0] ready-made and runs without mask loads
+ *             (see recalgo_dense_bwd dx_relu_mask).  Not with act_kind.  The same for recalgo_batchnorm_bwd_apply.
+ *   dx_scale  dx scaled where dx_relu lets it through: the dropout IN FRONT of the BatchNorm (recalgo_dense_fwd drop).
+ *   g_drop    the dropout BEHIND the BatchNorm: g is read as g * keep / (1 - rate).  sums must be NULL (sums left by a dgrad
+ *             epilogue are those of the un-dropped gradient).
+ * workspace: recalgo_batchnorm_bwd_workspace_bytes(rows, C). */
+int64_t recalgo_batchnorm_bwd_workspace_bytes(int rows, int C);
+int recalgo_batchnorm_train_bwd(const float* x, const float* gamma, const float* save_mean, const float* save_rstd,
+                                const float* g, const float* sums, int rows, int C, int act_kind, const float* act_z,
+                                const float* act_alpha, float* dx, float* dgamma, float* dbeta, float* dalpha, void* workspace,
+                                int dx_relu, float dx_scale, const recalgo_dropout_t* g_drop, recalgo_stream_t stream);
 /* Sync-BatchNorm building blocks (data parallel, N > 1, `sync_batch_norm`): the two launches of each direction as separate
  * entry points, so that the per-tile partials of all ranks — [recalgo_batchnorm_partial_rows(rows)][2][C] floats per rank:
  * (tile mean | tile M2) forward, (colsum g | colsum g * xhat) backward — can be all-gathered rank-major in between.
  * `partials` of _apply / _bwd_apply: [world][partial_rows][2][C]; every rank holds `rows` examples; the statistics are those
  * of the world * rows examples (== tf.layers.batch_normalization on the concatenated batch, bit-identical to the one-rank
  * kernels on it when rows % 64 == 0).  _bwd_apply: dx uses the sums over all ranks, dgamma / dbeta receive THIS rank's
- * share (the data-parallel all-reduce of the dense gradients adds the ranks up).  world = 1 == the fused entry points. */
+ * share (the data-parallel all-reduce of the dense gradients adds the ranks up).  world = 1: the one-rank BatchNorm.
+ * _apply's out_drop: the dropout BEHIND the BatchNorm (tf.layers.batch_normalization -> tf.layers.dropout, din.py:233-236),
+ * applied in the store: y is multiplied by keep / (1 - rate). */
 int recalgo_batchnorm_partial_rows(int rows);
 int recalgo_batchnorm_moments(const float* x, int rows, int C, float* partials, recalgo_stream_t stream);
 int recalgo_batchnorm_apply(const float* x, const float* gamma, const float* beta, const float* partials, int world, int rows,
-                            int C, float eps, float momentum, float* moving_mean, float* moving_var, float* y,
-                            float* save_mean, float* save_rstd, recalgo_stream_t stream);
+                            int C, float eps, float momentum, float* moving_mean, float* moving_var, float* y, float* save_mean,
+                            float* save_rstd, const recalgo_dropout_t* out_drop, recalgo_stream_t stream);
 int recalgo_batchnorm_bwd_sums(const float* x, const float* save_mean, const float* save_rstd, const float* g, int rows, int C,
                                float* partials, recalgo_stream_t stream);
 int recalgo_batchnorm_bwd_apply(const float* x, const float* gamma, const float* save_mean, const float* save_rstd,
@@ -556,7 +574,7 @@ int recalgo_sigmoid_ce_fwd_bwd(const float* logits, const float* labels, int B, 
  *   prob, mean sigmoid-CE as recalgo_sigmoid_ce_fwd_bwd;  dlogit[b] = d loss / d logit * grad_scale
  *   dx_p[b, :] = dlogit[b] * w_p          (dx_parts[p] may be NULL);  relu_parts (host array of n_parts flags, may be NULL):
  *              dx_p[b, j] = 0 where x_p[b, j] <= 0 — part p IS a ReLU output (the last hidden layer, dcn.py:166-170) and the
- *              layer that produced it gets its gradient already masked (see recalgo_dense_bwd_bn)
+ *              layer that produced it gets its gradient already masked (see recalgo_dense_bwd dx_relu_mask)
  *   partials [recalgo_logit_loss_partial_rows(B)][C + 2], C = sum of widths: per-workgroup partial sums of
  *   [dw over the C concatenated columns | d bias | loss]; their fixed-order column sums (recalgo_colsum_t jobs of
  *   recalgo_dense_bwd_weights_reduce) are dw_p, d bias and the loss value.  bias, addend0/1 may be NULL.
@@ -575,7 +593,7 @@ int recalgo_logit_loss_fwd_bwd(const float* const* x_parts, const float* const* 
  *   prob, mean sigmoid-CE, dlogit as recalgo_logit_loss_fwd_bwd;  d_side = dlogit w_side (d_side may be NULL)
  *   dz3 [B, N3] = dlogit w_h3 where h3 > 0, else 0        the gradient at the layer's pre-activation: its weight gradient is
  *                                                         recalgo_dense_bwd_weights(h2, dz3, mask NULL, ..), a launch of its own
- *   dh2 [B, K2] = (dz3 w3^T) where h2 > 0, else 0         (already masked for the layer that produced h2, see recalgo_dense_bwd_bn)
+ *   dh2 [B, K2] = (dz3 w3^T) where h2 > 0, else 0         (already masked for the layer below: recalgo_dense_bwd dx_relu_mask)
  *   partials [recalgo_tail_partial_rows(B)][Cs + N3 + 2]: [dw over the head's concatenated columns | d bias | loss] per
  *   workgroup, as recalgo_logit_loss_fwd_bwd's; side_first != 0: the head's columns are [side | h3] (dcn.py:171), else [h3 | side].
  * h3 never reaches HBM.  Served shapes: recalgo_tail_dense_head_supported(K2, N3, Cs) (N3 == 128, K2 in {128, 256, 384, 512},
@@ -729,53 +747,6 @@ int recalgo_activation_bwd(const float* x, const float* alpha, const float* gy, 
                            recalgo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * tf.layers.dropout(x, rate, training=True): y = x * keep / (1 - rate), keep ~ Bernoulli(1 - rate) per element
- * (algorithm/DeepFM/deepfm.py:208-209 — dropout_rate defaults to 0.1, :39; DIN/din.py:235-236; FiBiNET/fibinet.py:193-194;
- * PNN/pnn.py:188-189; NFM/nfm.py:170).  The keep decision of flat element i is a counter-based hash of (seed, call, *step, i)
- * (csrc/dropout.h) — `seed` the variable store's (+ rank), `call` the index of the dropout call inside the model_fn, `step` the
- * optimizer's device-side int64 step counter (NULL: 0), read at run time so that a captured step draws a new mask per replay —
- * or, keep_mask != NULL, the explicit mask (1 = keep, 0 = drop; parity tests replay the masks of the reference run).  No mask
- * is stored: the backward is the same map applied to the gradient with the same key.  recalgo_dropout_keep_mask writes the
- * mask the hash stands for (tests, debugging).  n < 2^32 elements; pointers 16-byte aligned; 0 < rate < 1 (a double: TF forms
- * 1 / (1 - rate) from the Python float and casts it to x.dtype once). */
-typedef struct recalgo_dropout {   /* one training-mode dropout call for the kernels that apply it themselves (the *_drop entry points) */
-    double rate;
-    const float* keep_mask;        /* NULL: the hash */
-    unsigned seed, call;
-    const int64_t* step;           /* device step counter, NULL: 0 */
-} recalgo_dropout_t;
-int recalgo_dropout_fwd(const float* x, int64_t n, double rate, const float* keep_mask, unsigned seed, unsigned call,
-                        const int64_t* step, float* y, recalgo_stream_t stream);
-int recalgo_dropout_bwd(const float* g, int64_t n, double rate, const float* keep_mask, unsigned seed, unsigned call,
-                        const int64_t* step, float* dx, recalgo_stream_t stream);
-int recalgo_dropout_keep_mask(int64_t n, double rate, unsigned seed, unsigned call, const int64_t* step, float* out,
-                              recalgo_stream_t stream);
-/* The dropout applied by its NEIGHBOURS instead of by launches of its own (element index = row * width + column of the contiguous
- * [rows, width] tensor, the index space of recalgo_dropout_fwd; drop == NULL: the plain entry point):
- *   recalgo_dense_fwd_drop             recalgo_dense_fwd_bn whose epilogue multiplies y = act(x w + b) by keep / (1 - rate) before
- *                                      the store and the BatchNorm tile moments — tf.layers.dense(relu) -> tf.layers.dropout
- *                                      [-> tf.layers.batch_normalization], deepfm.py:207-211 / pnn.py:187-191 / fibinet.py:192-196.
- *                                      ldy == N.  Its backward needs no mask of its own: y > 0 <=> relu > 0 and kept, so the
- *                                      consumer that masks its input gradient with y (recalgo_batchnorm_train_bwd_drop dx_relu)
- *                                      only has to scale it by dx_scale = 1 / (1 - rate);
- *   recalgo_batchnorm_apply_drop       recalgo_batchnorm_apply whose store multiplies by keep / (1 - rate) — tf.layers.
- *                                      batch_normalization -> tf.layers.dropout, din.py:233-236;
- *   recalgo_batchnorm_train_bwd_drop   recalgo_batchnorm_train_bwd_act with g read as g * keep / (1 - rate) (g_drop: the dropout
- *                                      BEHIND the BatchNorm; sums must be NULL — sums left by a dgrad epilogue are those of the
- *                                      un-dropped gradient) and / or dx scaled where dx_relu lets it through (dx_scale: the
- *                                      dropout IN FRONT of the BatchNorm). */
-int recalgo_dense_fwd_drop(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2, const float* w2, int K2,
-                           const float* bias, int M, int N, int relu, float* y, int ldy, float* bn_partials,
-                           const recalgo_dropout_t* drop, recalgo_stream_t stream);
-int recalgo_batchnorm_apply_drop(const float* x, const float* gamma, const float* beta, const float* partials, int world, int rows,
-                                 int C, float eps, float momentum, float* moving_mean, float* moving_var, float* y, float* save_mean,
-                                 float* save_rstd, const recalgo_dropout_t* out_drop, recalgo_stream_t stream);
-int recalgo_batchnorm_train_bwd_drop(const float* x, const float* gamma, const float* save_mean, const float* save_rstd,
-                                     const float* g, const float* sums, int rows, int C, int act_kind, const float* act_z,
-                                     const float* act_alpha, float* dx, float* dgamma, float* dbeta, float* dalpha, void* workspace,
-                                     int dx_relu, float dx_scale, const recalgo_dropout_t* g_drop, recalgo_stream_t stream);
-
-/* ------------------------------------------------------------------------------------------
  * a15 / a16 / f1  Row-gradient scatter without float atomics, fused with the sparse optimizer.
  * Replaces, for every embedding variable, TF autodiff's IndexedSlices gradient of the lookup plus
  * tf.train.AdamOptimizer(...).minimize (algorithm/DeepFM/deepfm.py:246-250, same in all six hot-path models;
@@ -891,7 +862,7 @@ typedef struct {
     int64_t rows;
 } recalgo_scatter_companion_t;
 /* The forward lookups on an arena with deferred-Adam state: identical to recalgo_embedding_gather_fwd /
- * _embedding_bag_mean_fwd / _sequence_gather_fwd / _deepfm_sparse_fwd, except that a row whose state lags
+ * the K1m bag mean / _sequence_gather_fwd / _deepfm_sparse_fwd, except that a row whose state lags
  * (last_step[row] < step_dev[0] + step_offset) is read AS OF that step: the missed g = 0 updates are replayed in registers
  * (bit-identical to the dense optimizer pass) and nothing is written back — the optimizer's `apply` / the sweep do the real
  * catch-up.  deferred = NULL: the plain lookup.  table_row_base = arena row of row 0 of `table` (m, v, last_step are arena

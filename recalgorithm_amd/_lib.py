@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RECALGO_HIP_LIB") or os.path.join(_HERE, "librecalgo_hip.so")
 
 P = c_void_p  # device pointer / stream
-ABI_VERSION = 3  # == RECALGO_ABI_VERSION of include/recalgo.h (bumped on any signature change)
+ABI_VERSION = 4  # == RECALGO_ABI_VERSION of include/recalgo.h (bumped on any signature change)
 
 # name -> (restype, argtypes); must list every function of include/recalgo.h
 SIGNATURES = {
@@ -24,7 +24,6 @@ SIGNATURES = {
     "recalgo_embedding_gather_fwd": (c_int, [P, P, P, c_int, c_int, c_int, P, c_int, c_int, P]),
     "recalgo_embedding_gather_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
     "recalgo_scatter_rows_sorted": (c_int, [P, P, P, c_int64, c_int, P, P]),
-    "recalgo_embedding_bag_mean_fwd": (c_int, [P, P, P, c_int, c_int, P, c_int, c_int, P]),
     "recalgo_embedding_bag_mean_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P, P, P]),
     "recalgo_sequence_gather_fwd": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
     "recalgo_sequence_gather_bwd": (c_int, [P, P, P, c_int, c_int, c_int, P, P, P]),
@@ -61,22 +60,15 @@ SIGNATURES = {
     "recalgo_mlp_width_supported": (c_int, [c_int]),
     "recalgo_relu_bwd_bias_workspace_bytes": (c_int64, [c_int, c_int]),
     "recalgo_relu_bwd_bias": (c_int, [P, P, c_int, c_int, P, P, P, P]),
-    "recalgo_batchnorm_workspace_bytes": (c_int64, [c_int, c_int]),
-    "recalgo_batchnorm_train_fwd": (c_int, [P, P, P, c_int, c_int, c_float, c_float, P, P, P, P, P, P, P]),
-    "recalgo_batchnorm_train_bwd": (c_int, [P, P, P, P, P, c_int, c_int, P, P, P, P, c_int, P]),
-    "recalgo_batchnorm_bwd_act_workspace_bytes": (c_int64, [c_int, c_int]),
-    "recalgo_batchnorm_train_bwd_act": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, P]),
+    "recalgo_batchnorm_bwd_workspace_bytes": (c_int64, [c_int, c_int]),
+    "recalgo_batchnorm_train_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, c_float, P, P]),
     "recalgo_batchnorm_partial_rows": (c_int, [c_int]),
     "recalgo_batchnorm_moments": (c_int, [P, c_int, c_int, P, P]),
-    "recalgo_batchnorm_apply": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P]),
+    "recalgo_batchnorm_apply": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P, P]),
     "recalgo_batchnorm_bwd_sums": (c_int, [P, P, P, P, c_int, c_int, P, P]),
     "recalgo_batchnorm_bwd_apply": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, P, c_int, P]),
     "recalgo_dropout_fwd": (c_int, [P, c_int64, c_double, P, c_int, c_int, P, P, P]),
-    "recalgo_dropout_bwd": (c_int, [P, c_int64, c_double, P, c_int, c_int, P, P, P]),
     "recalgo_dropout_keep_mask": (c_int, [c_int64, c_double, c_int, c_int, P, P, P]),
-    "recalgo_dense_fwd_drop": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, P, P]),
-    "recalgo_batchnorm_apply_drop": (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P, P]),
-    "recalgo_batchnorm_train_bwd_drop": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P, P, c_int, c_float, P, P]),
     "recalgo_sigmoid_ce_fwd_bwd": (c_int, [P, P, c_int, c_float, P, P, P, P]),
     "recalgo_adam_tf1_dense": (c_int, [P, P, P, P, c_int64, c_float, P, c_float, c_float, c_float, c_int, P]),
     "recalgo_adam_tf1_rows": (c_int, [P, P, P, P, P, c_int64, c_int, c_float, P, c_float, c_float, c_float, c_int, P]),
@@ -97,15 +89,12 @@ SIGNATURES = {
     "recalgo_adam_tf1_advance": (c_int, [P, c_float, c_float, c_float, P, P]),
     "recalgo_cross_layer_fwd": (c_int, [P, P, c_int, P, P, c_int, c_int, P, c_int, P]),
     "recalgo_cross_layer_bwd": (c_int, [P, P, c_int, P, P, P, c_int, c_int, c_int, P, P, P, P, P, P]),
-    "recalgo_dense_fwd": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P]),
-    "recalgo_dense_fwd_bn": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, P, c_int, P, P]),
-    "recalgo_dense_fwd_act_bn": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P]),
+    "recalgo_dense_fwd": (c_int, [P, c_int, P, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P, P, P, c_int, P, P, P]),
     "recalgo_dense_bwd_input": (c_int, [P, c_int, P, P, c_int, c_int, c_int, P, c_int, c_float, P, c_int, c_int, P]),
     "recalgo_dense_bwd_weights_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "recalgo_dense_bwd_weights": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, P, P, P, c_int, P]),
-    "recalgo_dense_bwd": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, c_int, c_float, P, c_int, P, P, P, c_int, P]),
-    "recalgo_dense_bwd_bn": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, c_int, c_float, P, c_int, P, P, P, c_int,
-                                     P, P, P, P, P, c_int, P]),
+    "recalgo_dense_bwd": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, c_int, c_float, P, c_int, P, P, P, c_int,
+                                  P, P, P, P, P, c_int, P]),
     "recalgo_dense_bwd_rider_supported": (c_int, [P, c_int, P, c_int, P, P, c_int, c_int, c_int, P, c_int, P, c_int, P, c_int,
                                                   c_int, c_int]),
     "recalgo_dense_bwd_cross_rider_supported": (c_int, [c_int, c_int]),

@@ -870,45 +870,17 @@ inline size_t wgrad_slab(int K, int N) { return ((size_t)K * N + N + 3) / 4 * 4;
 // =============================================================================================
 // C-ABI
 // =============================================================================================
-RECALGO_EXPORT int recalgo_dense_fwd(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2,
-                                     const float* w2, int K2, const float* bias, int M, int N, int relu, float* y,
-                                     int ldy, recalgo_stream_t stream) {
-    return recalgo_dense_fwd_bn(x, ldx, w, K, x2, ldx2, w2, K2, bias, M, N, relu, y, ldy, nullptr, stream);
-}
-
-RECALGO_EXPORT int recalgo_dense_fwd_bn(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2,
-                                        const float* w2, int K2, const float* bias, int M, int N, int relu, float* y,
-                                        int ldy, float* bn_partials, recalgo_stream_t stream) {
-    return recalgo_dense_fwd_act_bn(x, ldx, w, K, x2, ldx2, w2, K2, bias, M, N, relu, RECALGO_ACT_NONE, nullptr, nullptr, y, ldy,
-                                    bn_partials, stream);
-}
-
-static int dense_fwd_impl(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2, const float* w2, int K2,
-                          const float* bias, int M, int N, int relu, int act_kind, const float* act_alpha, float* z, float* y, int ldy,
-                          float* bn_partials, const recalgo_dropout_t* drop, recalgo_stream_t stream);
-
-RECALGO_EXPORT int recalgo_dense_fwd_act_bn(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2,
-                                            const float* w2, int K2, const float* bias, int M, int N, int relu, int act_kind,
-                                            const float* act_alpha, float* z, float* y, int ldy, float* bn_partials,
-                                            recalgo_stream_t stream) {
-    return dense_fwd_impl(x, ldx, w, K, x2, ldx2, w2, K2, bias, M, N, relu, act_kind, act_alpha, z, y, ldy, bn_partials, nullptr, stream);
-}
-
-RECALGO_EXPORT int recalgo_dense_fwd_drop(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2,
-                                          const float* w2, int K2, const float* bias, int M, int N, int relu, float* y, int ldy,
-                                          float* bn_partials, const recalgo_dropout_t* drop, recalgo_stream_t stream) {
-    RECALGO_REQUIRE(drop == nullptr || (ldy == N && (int64_t)M * N < ((int64_t)1 << 32) && recalgo_drop::abi_ok(drop)));
-    return dense_fwd_impl(x, ldx, w, K, x2, ldx2, w2, K2, bias, M, N, relu, RECALGO_ACT_NONE, nullptr, nullptr, y, ldy, bn_partials, drop, stream);
-}
-
-static int dense_fwd_impl(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2, const float* w2, int K2,
-                          const float* bias, int M, int N, int relu, int act_kind, const float* act_alpha, float* z, float* y, int ldy,
-                          float* bn_partials, const recalgo_dropout_t* drop, recalgo_stream_t stream) {
+RECALGO_EXPORT int recalgo_dense_fwd(const float* x, int ldx, const float* w, int K, const float* x2, int ldx2, const float* w2,
+                                     int K2, const float* bias, int M, int N, int relu, int act_kind, const float* act_alpha,
+                                     float* z, float* y, int ldy, float* bn_partials, const recalgo_dropout_t* drop,
+                                     recalgo_stream_t stream) {
     RECALGO_REQUIRE(M >= 0 && N > 0 && K > 0 && y != nullptr && ldy >= N);
     RECALGO_REQUIRE(act_kind == RECALGO_ACT_NONE || ((act_kind == RECALGO_ACT_PRELU || act_kind == RECALGO_ACT_DICE) &&
                                                      act_alpha != nullptr && z != nullptr && bn_partials != nullptr && !relu));
     RECALGO_REQUIRE(x != nullptr && ldx >= K && w != nullptr);
     RECALGO_REQUIRE(x2 == nullptr || (ldx2 >= K2 && K2 > 0 && w2 != nullptr));
+    RECALGO_REQUIRE(drop == nullptr || (act_kind == RECALGO_ACT_NONE && ldy == N && (int64_t)M * N < ((int64_t)1 << 32) &&
+                                        recalgo_drop::abi_ok(drop)));
     if (M == 0) return 0;
     FwdArgs P;
     P.seg[0] = Segment{operand(x, nullptr, ldx, M, K), operand(w, nullptr, N, K, N), K};
@@ -1031,30 +1003,33 @@ RECALGO_EXPORT int recalgo_dense_bwd_weights(const float* x, int ldx, const floa
     return finish_wgrad(S, defer_reduce, K, N, dw, dbias, workspace, st);
 }
 
-RECALGO_EXPORT int recalgo_dense_bwd(const float* x, int ldx, const float* g, int ldg, const float* y_mask, const float* w,
-                                     int M, int K, int N, const float* c_in, int ldc, float beta, float* dx, int lddx,
-                                     float* dw, float* dbias, void* workspace, int defer_reduce, recalgo_stream_t stream) {
-    return recalgo_dense_bwd_bn(x, ldx, g, ldg, y_mask, w, M, K, N, c_in, ldc, beta, dx, lddx, dw, dbias, workspace, defer_reduce,
-                                nullptr, nullptr, nullptr, nullptr, nullptr, 0, stream);
-}
-
-RECALGO_EXPORT int recalgo_dense_bwd_bn(const float* x, int ldx, const float* g, int ldg, const float* y_mask, const float* w,
-                                        int M, int K, int N, const float* c_in, int ldc, float beta, float* dx, int lddx,
-                                        float* dw, float* dbias, void* workspace, int defer_reduce, const float* bn_x,
-                                        const float* bn_mean, const float* bn_rstd, float* bn_partials,
-                                        const float* dx_relu_mask, int ld_mask, recalgo_stream_t stream) {
-    DgradArgs D;
-    WgradArgs W;
-    RECALGO_REQUIRE(M > 0 && build_dgrad(D, g, ldg, y_mask, w, M, N, K, c_in, ldc, beta, dx, lddx, 0));
-    RECALGO_REQUIRE(bn_partials == nullptr || (bn_x != nullptr && bn_mean != nullptr && bn_rstd != nullptr));
-    RECALGO_REQUIRE(dx_relu_mask == nullptr || ld_mask >= K);
+// The layer's own two GEMMs of recalgo_dense_bwd / _rider / _rider_supported, with the bn_* and dx_relu_mask options of the
+// input-gradient tiles' epilogue -> number of weight-gradient splits (>= 1), or 0 on bad arguments
+static int build_bwd(DgradArgs& D, WgradArgs& W, const float* x, int ldx, const float* g, int ldg, const float* y_mask,
+                     const float* w, int M, int K, int N, const float* c_in, int ldc, float beta, float* dx, int lddx, float* dw,
+                     float* dbias, void* workspace, const float* bn_x, const float* bn_mean, const float* bn_rstd,
+                     float* bn_partials, const float* dx_relu_mask, int ld_mask) {
+    if (!(M > 0 && build_dgrad(D, g, ldg, y_mask, w, M, N, K, c_in, ldc, beta, dx, lddx, 0))) return 0;
+    if (!(bn_partials == nullptr || (bn_x != nullptr && bn_mean != nullptr && bn_rstd != nullptr))) return 0;
+    if (!(dx_relu_mask == nullptr || ld_mask >= K)) return 0;
     D.dx_mask = dx_relu_mask; D.ld_mask = ld_mask;
     if (dx_relu_mask != nullptr && !(aligned16(dx_relu_mask) && ld_mask % 4 == 0)) D.vec_store = 0;
     D.bn_x = bn_x; D.bn_mean = bn_mean; D.bn_rstd = bn_rstd; D.bn_partials = bn_partials;
-    const int S = build_wgrad(W, x, ldx, g, ldg, y_mask, M, K, N, dw, dbias, workspace);
+    D.tiles_per_block = bwd_balance(M, K, N).tiles_per_block;
+    return build_wgrad(W, x, ldx, g, ldg, y_mask, M, K, N, dw, dbias, workspace);
+}
+
+RECALGO_EXPORT int recalgo_dense_bwd(const float* x, int ldx, const float* g, int ldg, const float* y_mask, const float* w,
+                                     int M, int K, int N, const float* c_in, int ldc, float beta, float* dx, int lddx,
+                                     float* dw, float* dbias, void* workspace, int defer_reduce, const float* bn_x,
+                                     const float* bn_mean, const float* bn_rstd, float* bn_partials,
+                                     const float* dx_relu_mask, int ld_mask, recalgo_stream_t stream) {
+    DgradArgs D;
+    WgradArgs W;
+    const int S = build_bwd(D, W, x, ldx, g, ldg, y_mask, w, M, K, N, c_in, ldc, beta, dx, lddx, dw, dbias, workspace, bn_x,
+                            bn_mean, bn_rstd, bn_partials, dx_relu_mask, ld_mask);
     RECALGO_REQUIRE(S >= 1);
     hipStream_t st = as_stream(stream);
-    D.tiles_per_block = bwd_balance(M, K, N).tiles_per_block;
     const int gd = cdiv(cdiv(M, BM) * cdiv(K, BN), D.tiles_per_block), gw = cdiv(K, BM) * cdiv(N, BN) * S;
     const bool fast = dgrad_fast(D) && wgrad_fast(W);
     if (fast && y_mask) hipLaunchKernelGGL((dense_bwd_kernel<true, true>), dim3(gd + gw), dim3(kThreads), 0, st, D, W, gd);
@@ -1082,14 +1057,9 @@ RECALGO_EXPORT int recalgo_dense_bwd_rider(const float* x, int ldx, const float*
                                            recalgo_stream_t stream) {
     DgradArgs D;
     WgradArgs W, R;
-    RECALGO_REQUIRE(M > 0 && build_dgrad(D, g, ldg, y_mask, w, M, N, K, c_in, ldc, beta, dx, lddx, 0));
-    RECALGO_REQUIRE(bn_partials == nullptr || (bn_x != nullptr && bn_mean != nullptr && bn_rstd != nullptr));
-    RECALGO_REQUIRE(dx_relu_mask == nullptr || ld_mask >= K);
     RECALGO_REQUIRE(r_x != nullptr || c_x0 != nullptr);
-    D.dx_mask = dx_relu_mask; D.ld_mask = ld_mask;
-    if (dx_relu_mask != nullptr && !(aligned16(dx_relu_mask) && ld_mask % 4 == 0)) D.vec_store = 0;
-    D.bn_x = bn_x; D.bn_mean = bn_mean; D.bn_rstd = bn_rstd; D.bn_partials = bn_partials;
-    const int S = build_wgrad(W, x, ldx, g, ldg, y_mask, M, K, N, dw, dbias, workspace);
+    const int S = build_bwd(D, W, x, ldx, g, ldg, y_mask, w, M, K, N, c_in, ldc, beta, dx, lddx, dw, dbias, workspace, bn_x,
+                            bn_mean, bn_rstd, bn_partials, dx_relu_mask, ld_mask);
     RECALGO_REQUIRE(S >= 1);
     // the riders' partials are always left to recalgo_dense_bwd_weights_reduce (a weight-gradient rider with a single split writes dw itself)
     int gr = 0;
@@ -1110,7 +1080,6 @@ RECALGO_EXPORT int recalgo_dense_bwd_rider(const float* x, int ldx, const float*
                        (unsigned)cross_rider_blocks(M)};
     }
     hipStream_t st = as_stream(stream);
-    D.tiles_per_block = bwd_balance(M, K, N).tiles_per_block;
     const int gd = cdiv(cdiv(M, BM) * cdiv(K, BN), D.tiles_per_block), gw = cdiv(K, BM) * cdiv(N, BN) * S;
     RECALGO_REQUIRE(dgrad_fast(D) && wgrad_fast(W));
     const dim3 grid(gd + gw + gr + (int)C.blocks), block(kThreads);
@@ -1140,13 +1109,13 @@ RECALGO_EXPORT int recalgo_dense_bwd_rider(const float* x, int ldx, const float*
 RECALGO_EXPORT int recalgo_dense_bwd_rider_supported(const float* x, int ldx, const float* g, int ldg, const float* y_mask,
                                                      const float* w, int M, int K, int N, float* dx, int lddx, const float* r_x,
                                                      int r_ldx, const float* r_g, int r_ldg, int r_K, int r_N) {
-    if (!(M > 0 && K > 0 && N > 0 && x && g && w && dx)) return 0;
     DgradArgs D;
     WgradArgs W, R;
     static float dummy[4];
     alignas(16) static char ws[16];
-    if (!build_dgrad(D, g, ldg, y_mask, w, M, N, K, nullptr, 0, 0.f, dx, lddx, 0)) return 0;
-    if (build_wgrad(W, x, ldx, g, ldg, y_mask, M, K, N, dummy, nullptr, ws) < 1) return 0;
+    if (build_bwd(D, W, x, ldx, g, ldg, y_mask, w, M, K, N, nullptr, 0, 0.f, dx, lddx, dummy, nullptr, ws, nullptr, nullptr, nullptr,
+                  nullptr, nullptr, 0) < 1)
+        return 0;
     if (!(dgrad_fast(D) && wgrad_fast(W))) return 0;
     if (r_x != nullptr) {
         if (!(r_K > 0 && r_N > 0 && r_g)) return 0;

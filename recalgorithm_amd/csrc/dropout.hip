@@ -1,7 +1,7 @@
 // tf.layers.dropout(x, rate, training=True) (algorithm/DeepFM/deepfm.py:208-209, DIN/din.py:235-236, FiBiNET/fibinet.py:193-194,
 // PNN/pnn.py:188-189, NFM/nfm.py:170): y = x * keep / (1 - rate), keep ~ Bernoulli(1 - rate) per element.  The keep decision
 // is the counter-based hash of dropout.h (or an explicit mask: parity tests replay the masks of the reference run), so the
-// backward needs no stored mask: dx = g * keep / (1 - rate) from the same key.  HBM-bound elementwise passes, float4.
+// backward needs no stored mask: it is recalgo_dropout_fwd on the gradient, same key.  HBM-bound elementwise passes, float4.
 #include "common.h"
 #include "dropout.h"
 
@@ -53,12 +53,6 @@ RECALGO_EXPORT int recalgo_dropout_fwd(const float* x, int64_t n, double rate, c
     hipLaunchKernelGGL(dropout_kernel, dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), x, n,
                        make_spec(rate, keep_mask, seed, call, step), y);
     RECALGO_RETURN_LAST();
-}
-
-// the backward is the same map applied to the gradient
-RECALGO_EXPORT int recalgo_dropout_bwd(const float* g, int64_t n, double rate, const float* keep_mask, unsigned seed, unsigned call,
-                                       const int64_t* step, float* dx, recalgo_stream_t stream) {
-    return recalgo_dropout_fwd(g, n, rate, keep_mask, seed, call, step, dx, stream);
 }
 
 RECALGO_EXPORT int recalgo_dropout_keep_mask(int64_t n, double rate, unsigned seed, unsigned call, const int64_t* step, float* out,

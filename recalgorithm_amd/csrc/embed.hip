@@ -648,13 +648,6 @@ RECALGO_EXPORT int recalgo_embedding_gather_bwd(const int64_t* ids, const float*
     RECALGO_RETURN_LAST();
 }
 
-RECALGO_EXPORT int recalgo_embedding_bag_mean_fwd(const int64_t* values, const int64_t* offsets,
-                                                  const float* table, int B, int K, float* out,
-                                                  int out_stride, int out_col,
-                                                  recalgo_stream_t stream) {
-    return recalgo_embedding_bag_mean_fwd_deferred(values, offsets, table, B, K, out, out_stride, out_col, nullptr, 0, nullptr, 0, stream);
-}
-
 RECALGO_EXPORT int recalgo_embedding_bag_mean_fwd_deferred(const int64_t* values, const int64_t* offsets, const float* table, int B,
                                                            int K, float* out, int out_stride, int out_col,
                                                            const recalgo_deferred_adam_t* deferred, int64_t table_row_base,

@@ -290,7 +290,7 @@ __global__ __launch_bounds__(kThreads) void bn_bwd_sum_apply_kernel(
     // batch_norm, deepfm.py:207-211; x = relu * keep / (1 - rate), so x > 0 <=> relu > 0 and kept): dx := dx / (1 - rate) there.
     // g_drop: a dropout AFTER this BatchNorm (see bn_bwd_reduce_kernel)
     // dx_relu: x IS a ReLU output (tf.layers.dense(..., relu) -> tf.layers.batch_normalization, deepfm.py:206-211): dx is zeroed where
-    // x <= 0, so that the dense layer's backward gets its gradient already masked (see recalgo_dense_bwd_bn dx_relu_mask)
+    // x <= 0, so that the dense layer's backward gets its gradient already masked (see recalgo_dense_bwd dx_relu_mask)
     // nblk = world * nblk_local partial rows (see bn_finalize_apply_kernel).  dx uses the sums over ALL ranks' tiles;
     // dbeta / dgamma get THIS rank's share (the data-parallel all-reduce of the dense gradients adds the ranks up)
     __shared__ float4 sh[2][16][17];
@@ -511,7 +511,7 @@ struct TailArgs {
     const float* w[kHeadMaxParts];      // one weight vector per part (xDeepFM sums three one-unit heads)
     float* dx[kHeadMaxParts];           // may be null per part
     int width[kHeadMaxParts];
-    int relu[kHeadMaxParts];            // part p is a ReLU output: dx_p := 0 where x_p <= 0 (see recalgo_dense_bwd_bn)
+    int relu[kHeadMaxParts];            // part p is a ReLU output: dx_p := 0 where x_p <= 0 (see recalgo_dense_bwd dx_relu_mask)
     int n;
     const float* bias;                  // [1] or null
     const float* addend[2];             // [B] extra logit terms or null (DeepFM: FM first / second order)
@@ -716,60 +716,16 @@ RECALGO_EXPORT int recalgo_relu_bwd_bias(const float* g, const float* y, int row
     RECALGO_RETURN_LAST();
 }
 
-RECALGO_EXPORT int64_t recalgo_batchnorm_workspace_bytes(int rows, int C) {
-    if (rows <= 0 || !width_ok(C)) return 0;
-    return (int64_t)nblk_of(rows) * 2 * C * (int64_t)sizeof(float);
-}
-
-RECALGO_EXPORT int recalgo_batchnorm_train_fwd(const float* x, const float* gamma, const float* beta, int rows, int C,
-                                               float eps, float momentum, float* moving_mean, float* moving_var,
-                                               float* y, float* save_mean, float* save_rstd, void* workspace,
-                                               recalgo_stream_t stream) {
-    RECALGO_REQUIRE(rows > 0 && width_ok(C) && x && gamma && beta && y && save_mean && save_rstd && workspace);
-    RECALGO_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr));
-    hipStream_t st = as_stream(stream);
-    const int nb = nblk_of(rows);
-    const unsigned C4 = C / 4;
-    float* partials = static_cast<float*>(workspace);
-    hipLaunchKernelGGL(bn_moments_kernel, dim3(cdiv(C4, 16), nb), dim3(kThreads), 0, st, reinterpret_cast<const float4*>(x),
-                       (unsigned)rows, C4, reinterpret_cast<float4*>(partials));
-    hipLaunchKernelGGL(bn_finalize_apply_kernel, dim3(cdiv(C4, 16), nb), dim3(kThreads), 0, st,
-                       reinterpret_cast<const float4*>(x), reinterpret_cast<const float4*>(gamma),
-                       reinterpret_cast<const float4*>(beta), reinterpret_cast<const float4*>(partials), (unsigned)nb,
-                       (unsigned)nb, (unsigned)rows, C4, eps, momentum, reinterpret_cast<float4*>(moving_mean),
-                       reinterpret_cast<float4*>(moving_var), reinterpret_cast<float4*>(save_mean),
-                       reinterpret_cast<float4*>(save_rstd), reinterpret_cast<float4*>(y), recalgo_drop::disabled());
-    RECALGO_RETURN_LAST();
-}
-
-RECALGO_EXPORT int recalgo_batchnorm_train_bwd(const float* x, const float* gamma, const float* save_mean,
-                                               const float* save_rstd, const float* g, int rows, int C, float* dx,
-                                               float* dgamma, float* dbeta, void* workspace, int dx_relu,
-                                               recalgo_stream_t stream) {
-    return recalgo_batchnorm_train_bwd_act(x, gamma, save_mean, save_rstd, g, nullptr, rows, C, RECALGO_ACT_NONE, nullptr, nullptr, dx,
-                                           dgamma, dbeta, nullptr, workspace, dx_relu, stream);
-}
-
-RECALGO_EXPORT int64_t recalgo_batchnorm_bwd_act_workspace_bytes(int rows, int C) {
+RECALGO_EXPORT int64_t recalgo_batchnorm_bwd_workspace_bytes(int rows, int C) {
     if (rows <= 0 || !width_ok(C)) return 0;
     return (int64_t)nblk_of(rows) * 3 * C * (int64_t)sizeof(float);
 }
 
-RECALGO_EXPORT int recalgo_batchnorm_train_bwd_act(const float* x, const float* gamma, const float* save_mean,
-                                                   const float* save_rstd, const float* g, const float* sums, int rows, int C,
-                                                   int act_kind,
-                                                   const float* act_z, const float* act_alpha, float* dx, float* dgamma,
-                                                   float* dbeta, float* dalpha, void* workspace, int dx_relu,
-                                                   recalgo_stream_t stream) {
-    return recalgo_batchnorm_train_bwd_drop(x, gamma, save_mean, save_rstd, g, sums, rows, C, act_kind, act_z, act_alpha, dx, dgamma, dbeta,
-                                            dalpha, workspace, dx_relu, 1.0f, nullptr, stream);
-}
-
-RECALGO_EXPORT int recalgo_batchnorm_train_bwd_drop(const float* x, const float* gamma, const float* save_mean,
-                                                    const float* save_rstd, const float* g, const float* sums, int rows, int C,
-                                                    int act_kind, const float* act_z, const float* act_alpha, float* dx,
-                                                    float* dgamma, float* dbeta, float* dalpha, void* workspace, int dx_relu,
-                                                    float dx_scale, const recalgo_dropout_t* g_drop, recalgo_stream_t stream) {
+RECALGO_EXPORT int recalgo_batchnorm_train_bwd(const float* x, const float* gamma, const float* save_mean, const float* save_rstd,
+                                               const float* g, const float* sums, int rows, int C, int act_kind, const float* act_z,
+                                               const float* act_alpha, float* dx, float* dgamma, float* dbeta, float* dalpha,
+                                               void* workspace, int dx_relu, float dx_scale, const recalgo_dropout_t* g_drop,
+                                               recalgo_stream_t stream) {
     RECALGO_REQUIRE(recalgo_drop::abi_ok(g_drop) && (g_drop == nullptr || (sums == nullptr && (int64_t)rows * C < ((int64_t)1 << 32))));
     const recalgo_drop::Spec gd = recalgo_drop::from_abi(g_drop);
     RECALGO_REQUIRE(rows > 0 && width_ok(C) && x && gamma && save_mean && save_rstd && g && dx && dgamma && dbeta &&
@@ -782,7 +738,7 @@ RECALGO_EXPORT int recalgo_batchnorm_train_bwd_drop(const float* x, const float*
     float* ws = static_cast<float*>(workspace);
     float* act_partials = ws + (size_t)nb * 2 * C;              // [nb][C]: the tile rows' terms of dalpha
     // sums: the partial rows (colsum g | colsum g * xhat per 64-row tile) are already there — left by the epilogue of the
-    // kernel that produced g (recalgo_dense_bwd_bn) — and the pass over g and x that computes them is skipped
+    // kernel that produced g (recalgo_dense_bwd bn_partials) — and the pass over g and x that computes them is skipped
     const float* partials = sums ? sums : ws;
     if (sums == nullptr)
         hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(cdiv(C4, 16), nb), dim3(kThreads), 0, st, reinterpret_cast<const float4*>(x),
@@ -818,18 +774,10 @@ RECALGO_EXPORT int recalgo_batchnorm_moments(const float* x, int rows, int C, fl
     RECALGO_RETURN_LAST();
 }
 
-RECALGO_EXPORT int recalgo_batchnorm_apply(const float* x, const float* gamma, const float* beta, const float* partials,
-                                           int world, int rows, int C, float eps, float momentum, float* moving_mean,
-                                           float* moving_var, float* y, float* save_mean, float* save_rstd,
+RECALGO_EXPORT int recalgo_batchnorm_apply(const float* x, const float* gamma, const float* beta, const float* partials, int world,
+                                           int rows, int C, float eps, float momentum, float* moving_mean, float* moving_var,
+                                           float* y, float* save_mean, float* save_rstd, const recalgo_dropout_t* out_drop,
                                            recalgo_stream_t stream) {
-    return recalgo_batchnorm_apply_drop(x, gamma, beta, partials, world, rows, C, eps, momentum, moving_mean, moving_var, y, save_mean,
-                                        save_rstd, nullptr, stream);
-}
-
-RECALGO_EXPORT int recalgo_batchnorm_apply_drop(const float* x, const float* gamma, const float* beta, const float* partials,
-                                                int world, int rows, int C, float eps, float momentum, float* moving_mean,
-                                                float* moving_var, float* y, float* save_mean, float* save_rstd,
-                                                const recalgo_dropout_t* out_drop, recalgo_stream_t stream) {
     RECALGO_REQUIRE(recalgo_drop::abi_ok(out_drop) && (out_drop == nullptr || (int64_t)rows * C < ((int64_t)1 << 32)));
     RECALGO_REQUIRE(rows > 0 && world >= 1 && width_ok(C) && x && gamma && beta && partials && y && save_mean && save_rstd);
     RECALGO_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr));

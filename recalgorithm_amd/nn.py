@@ -104,7 +104,7 @@ def _bn_link_of(x: torch.Tensor):
 
 class ReluSource:
     """Rides on the output tensor of a tf.layers.dense(..., relu) (`_recalgo_relu_src`).  A consumer whose backward kernel can
-    mask its input gradient with that tensor itself — the next dense layer (recalgo_dense_bwd_bn dx_relu_mask), the fused
+    mask its input gradient with that tensor itself — the next dense layer (recalgo_dense_bwd dx_relu_mask), the fused
     loss tail (recalgo_logit_loss_fwd_bwd relu_parts) — does so and leaves the gradient tensor here; the producing layer's
     backward skips its own mask (the mask loads of both of its GEMMs) when the gradient autograd hands it IS that tensor.
     Any other consumer of the activation makes autograd sum into a new tensor (the reference held here keeps the engine from

@@ -19,6 +19,7 @@ from . import _lib, sparse
 from .variables import EmbeddingArena, Variable, VariableStore
 
 _ACT = {"prelu": 0, "dice": 1}
+_ACT_NONE = -1                               # include/recalgo.h RECALGO_ACT_NONE
 
 
 def _lib_():
@@ -278,7 +279,7 @@ class _BagMeanFn(Function):
         rb0 = 0 if table_name == "__staged__" else arena.tables[table_name][0]
         _lib.check(_lib_().recalgo_embedding_bag_mean_fwd_deferred(
             _p(values), _p(offsets), _p(table), B, K, _p(out), K, 0, dv, rb0, stp, 0, _stream(offsets)),
-            "recalgo_embedding_bag_mean_fwd")
+            "recalgo_embedding_bag_mean_fwd_deferred")
         ctx.args = (values, offsets, arena, table_name)
         return out
 
@@ -1250,8 +1251,9 @@ def dense_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], re
               x2: Optional[torch.Tensor] = None, w2: Optional[torch.Tensor] = None,
               bn_partials: Optional[torch.Tensor] = None, drop: Optional["DropSpec"] = None) -> torch.Tensor:
     """act(x @ w (+ x2 @ w2) + bias) on the fp32 matrix cores (include/recalgo.h recalgo_dense_fwd).  bn_partials
-    [bn_partial_rows(M), 2 N]: the launch also leaves the per-tile batch moments of the result there (recalgo_dense_fwd_bn),
-    for the BatchNorm layer that consumes it (batchnorm_train_fwd(..., partials=))."""
+    [bn_partial_rows(M), 2 N]: the launch also leaves the per-tile batch moments of the result there, for the BatchNorm
+    layer that consumes it (batchnorm_train_fwd(..., partials=)).  drop: the dropout behind the layer rides in the
+    epilogue — y, and the moments, are those of the dropped tensor."""
     x, w = _mat(x, "x"), _mat(w, "w")
     M, K = x.shape
     N = w.shape[1]
@@ -1265,23 +1267,18 @@ def dense_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], re
     if bn_partials is not None and (tuple(bn_partials.shape) != (bn_partial_rows(M), 2 * N) or not bn_partials.is_contiguous()):
         raise ValueError("dense_fwd: bn_partials must be a contiguous [bn_partial_rows(M), 2 N] tensor")
     if drop is not None:
-        # the dropout behind the layer rides in the epilogue (recalgo_dense_fwd_drop): y, and the moments, are those of the dropped tensor
         drop.check_mask((M, N))
-        cd, _keep = _cdrop(drop)
-        _lib.check(_lib_().recalgo_dense_fwd_drop(
-            _p(x), x.stride(0), _p(w), K, _p(x2), 0 if x2 is None else x2.stride(0), _p(w2), 0 if x2 is None else x2.shape[1],
-            _p(bias), M, N, int(relu), _p(y), N, _p(bn_partials), cd, _stream(x)), "recalgo_dense_fwd_drop")
-        return y
-    _lib.check(_lib_().recalgo_dense_fwd_bn(
+    cd, _keep = _cdrop(drop)
+    _lib.check(_lib_().recalgo_dense_fwd(
         _p(x), x.stride(0), _p(w), K, _p(x2), 0 if x2 is None else x2.stride(0), _p(w2), 0 if x2 is None else x2.shape[1],
-        _p(bias), M, N, int(relu), _p(y), N, _p(bn_partials), _stream(x)), "recalgo_dense_fwd")
+        _p(bias), M, N, int(relu), _ACT_NONE, None, None, _p(y), N, _p(bn_partials), cd, _stream(x)), "recalgo_dense_fwd")
     return y
 
 
 def dense_fwd_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], kind: int, alpha: torch.Tensor,
                   bn_partials: torch.Tensor):
     """z = x @ w + bias, y = prelu | dice (z, alpha) and the per-tile batch moments of y in ONE launch
-    (recalgo_dense_fwd_act_bn): the forward of DIN's dense -> activation -> batch_norm layers up to the BatchNorm merge.
+    (recalgo_dense_fwd): the forward of DIN's dense -> activation -> batch_norm layers up to the BatchNorm merge.
     -> (z, y)"""
     x, w = _mat(x, "x"), _mat(w, "w")
     M, K = x.shape
@@ -1292,9 +1289,9 @@ def dense_fwd_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
         raise ValueError("dense_fwd_act: bn_partials must be a contiguous [bn_partial_rows(M), 2 N] tensor")
     z = torch.empty(M, N, device=x.device, dtype=torch.float32)
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    _lib.check(_lib_().recalgo_dense_fwd_act_bn(
+    _lib.check(_lib_().recalgo_dense_fwd(
         _p(x), x.stride(0), _p(w), K, None, 0, None, 0, _p(bias), M, N, 0, int(kind), _p(alpha), _p(z), _p(y), N,
-        _p(bn_partials), _stream(x)), "recalgo_dense_fwd_act_bn")
+        _p(bn_partials), None, _stream(x)), "recalgo_dense_fwd")
     return z, y
 
 
@@ -1392,7 +1389,7 @@ def dense_bwd(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], 
     premask [M, K] (rows contiguous): dx is zeroed where premask <= 0 (before the beta * c_in term) — x itself when x is the
     ReLU output of the layer below, whose backward then needs no mask (nn.ReluSource).
     bn = (bn_x [M, K] contiguous, mean [K], rstd [K], partials [bn_partial_rows(M), 2 K]): x is the output of a training-mode
-    BatchNorm over bn_x — the launch also leaves the sums that BatchNorm's backward starts with (recalgo_dense_bwd_bn)."""
+    BatchNorm over bn_x — the launch also leaves the sums that BatchNorm's backward starts with."""
     x, g, w = _mat(x, "x"), _mat(g, "g"), _mat(w, "w")
     M, K = x.shape
     N = g.shape[1]
@@ -1420,6 +1417,10 @@ def dense_bwd(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], 
         bnp = (_p(bx), _p(bmean), _p(brstd), _p(bpart))
     if premask is not None and (tuple(premask.shape) != (M, K) or premask.stride(1) != 1 or premask.dtype != torch.float32):
         raise ValueError("dense_bwd: premask must be [M, K] fp32 with contiguous rows")
+    # the layer's own arguments of recalgo_dense_bwd, which recalgo_dense_bwd_rider starts with
+    main = (_p(x), x.stride(0), _p(g), g.stride(0), _p(y_mask), _p(w), M, K, N, _p(c_in), 0 if c_in is None else c_in.stride(0),
+            float(beta), _p(dx), K, _p(dw), _p(dbias), _p(ws), int(defer), *bnp, _p(premask),
+            0 if premask is None else premask.stride(0))
     rider = _take_wgrad_rider(M, x.device) if defer else None
     crider = _take_cross_rider(M, x.device) if (defer and cross_rider and y_mask is None) else None
     if rider is not None or crider is not None:
@@ -1432,11 +1433,9 @@ def dense_bwd(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], 
             cargs, cdone = (None, 0, None, None, None, 0, 0, 0, None, None), None
             if crider is not None:
                 cargs, cdone = _cross_rider_args(*crider)
-            _lib.check(lib.recalgo_dense_bwd_rider(_p(x), x.stride(0), _p(g), g.stride(0), _p(y_mask), _p(w), M, K, N, _p(c_in),
-                                                   0 if c_in is None else c_in.stride(0), float(beta), _p(dx), K, _p(dw), _p(dbias),
-                                                   _p(ws), int(defer), *bnp, _p(premask), 0 if premask is None else premask.stride(0),
-                                                   _p(rx), 0 if rx is None else rx.stride(0), _p(rg), 0 if rg is None else rg.stride(0),
-                                                   rK, rN, _p(rdw), _p(rdb), _p(rws), *cargs, _stream(x)), "recalgo_dense_bwd_rider")
+            _lib.check(lib.recalgo_dense_bwd_rider(*main, _p(rx), 0 if rx is None else rx.stride(0), _p(rg),
+                                                   0 if rg is None else rg.stride(0), rK, rN, _p(rdw), _p(rdb), _p(rws), *cargs,
+                                                   _stream(x)), "recalgo_dense_bwd_rider")
             _dense_pending.append((M, K, N, ws, dw, dbias))
             if rider is not None:
                 rider_stats["wgrad"] += 1
@@ -1450,10 +1449,7 @@ def dense_bwd(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], 
             dense_bwd_weights(rx, rg, None, rdw, rdb, defer=True)          # (not on the vectorised tile paths: a launch of its own)
         if crider is not None:
             _cross_rider.append(crider)                                    # (left to the cross node's own backward)
-    _lib.check(lib.recalgo_dense_bwd_bn(_p(x), x.stride(0), _p(g), g.stride(0), _p(y_mask), _p(w), M, K, N, _p(c_in),
-                                        0 if c_in is None else c_in.stride(0), float(beta), _p(dx), K, _p(dw), _p(dbias), _p(ws),
-                                        int(defer), *bnp, _p(premask), 0 if premask is None else premask.stride(0), _stream(x)),
-               "recalgo_dense_bwd")
+    _lib.check(lib.recalgo_dense_bwd(*main, _stream(x)), "recalgo_dense_bwd")
     if defer:
         _dense_pending.append((M, K, N, ws, dw, dbias))
     return dx
@@ -1620,8 +1616,8 @@ def dense1_bwd(parts, w: torch.Tensor, g: torch.Tensor, dxs, dw: torch.Tensor, d
 
 def batchnorm_train_fwd(x, gamma, beta, moving_mean, moving_var, momentum: float, eps: float, partials=None,
                         out_drop: Optional["DropSpec"] = None):
-    """partials: the per-tile moments of x when its producer has already left them (dense_fwd(bn_partials=)): ONE launch
-    (merge + apply) instead of two.  out_drop: the dropout BEHIND the BatchNorm rides in the store (recalgo_batchnorm_apply_drop)."""
+    """Per-tile moments, then merge + apply.  partials: the per-tile moments of x when its producer has already left them
+    (dense_fwd(bn_partials=)): ONE launch instead of two.  out_drop: the dropout BEHIND the BatchNorm rides in the store."""
     rows, C = x.shape
     lib = _lib_()
     y = torch.empty_like(x)
@@ -1629,33 +1625,23 @@ def batchnorm_train_fwd(x, gamma, beta, moving_mean, moving_var, momentum: float
     rstd = torch.empty(C, device=x.device, dtype=torch.float32)
     if out_drop is not None:
         out_drop.check_mask((rows, C))
-        if partials is None:
-            partials = torch.empty(bn_partial_rows(rows), 2 * C, device=x.device, dtype=torch.float32)
-            _lib.check(lib.recalgo_batchnorm_moments(_p(x), rows, C, _p(partials), _stream(x)), "recalgo_batchnorm_moments")
-        cd, _keep = _cdrop(out_drop)
-        _lib.check(lib.recalgo_batchnorm_apply_drop(_p(x), _p(gamma), _p(beta), _p(partials), 1, rows, C, eps, momentum,
-                                                    _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(rstd), cd, _stream(x)),
-                   "recalgo_batchnorm_apply_drop")
-        return y, mean, rstd
-    if partials is not None:
-        _lib.check(lib.recalgo_batchnorm_apply(_p(x), _p(gamma), _p(beta), _p(partials), 1, rows, C, eps, momentum,
-                                               _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(rstd), _stream(x)),
-                   "recalgo_batchnorm_apply")
-        return y, mean, rstd
-    ws = _workspace(lib.recalgo_batchnorm_workspace_bytes(rows, C), x.device)
-    _lib.check(lib.recalgo_batchnorm_train_fwd(_p(x), _p(gamma), _p(beta), rows, C, eps, momentum, _p(moving_mean),
-                                               _p(moving_var), _p(y), _p(mean), _p(rstd), _p(ws), _stream(x)),
-               "recalgo_batchnorm_train_fwd")
+    if partials is None:
+        partials = _workspace(bn_partial_rows(rows) * 2 * C * 4, x.device)
+        _lib.check(lib.recalgo_batchnorm_moments(_p(x), rows, C, _p(partials), _stream(x)), "recalgo_batchnorm_moments")
+    cd, _keep = _cdrop(out_drop)
+    _lib.check(lib.recalgo_batchnorm_apply(_p(x), _p(gamma), _p(beta), _p(partials), 1, rows, C, eps, momentum, _p(moving_mean),
+                                           _p(moving_var), _p(y), _p(mean), _p(rstd), cd, _stream(x)), "recalgo_batchnorm_apply")
     return y, mean, rstd
 
 
 def batchnorm_train_bwd_act(x, gamma, mean, rstd, g, dgamma, dbeta, kind: int, z, alpha, dalpha, defer: bool,
                             sums=None, g_drop: Optional["DropSpec"] = None) -> torch.Tensor:
-    """BatchNorm backward continued through the per-channel activation x = act(z, alpha) (recalgo_batchnorm_train_bwd_act):
-    -> dL/dz; dgamma / dbeta / dalpha are overwritten (`defer`: dalpha by the step's deferred-sum launch)."""
+    """BatchNorm backward continued through the per-channel activation x = act(z, alpha) (recalgo_batchnorm_train_bwd):
+    -> dL/dz; dgamma / dbeta / dalpha are overwritten (`defer`: dalpha by the step's deferred-sum launch).  g_drop: the
+    BatchNorm's output went through a dropout — g is read as g * keep / (1 - rate) (sums of the un-dropped g are of no use)."""
     rows, C = x.shape
     lib = _lib_()
-    nbytes = int(lib.recalgo_batchnorm_bwd_act_workspace_bytes(rows, C))
+    nbytes = int(lib.recalgo_batchnorm_bwd_workspace_bytes(rows, C))
     dz = torch.empty_like(x)
     if defer:
         key = ("bn_act", x.device.type, x.device.index, rows, C, dalpha.data_ptr())
@@ -1664,16 +1650,10 @@ def batchnorm_train_bwd_act(x, gamma, mean, rstd, g, dgamma, dbeta, kind: int, z
             ws = _dense_ws[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
     else:
         ws = _workspace(nbytes, x.device)
-    if g_drop is not None:
-        # the BatchNorm's output went through a dropout: g is read as g * keep / (1 - rate) (sums of the un-dropped g are of no use)
-        cd, _keep = _cdrop(g_drop)
-        _lib.check(lib.recalgo_batchnorm_train_bwd_drop(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), None, rows, C, int(kind), _p(z), _p(alpha),
-                                                        _p(dz), _p(dgamma), _p(dbeta), None if defer else _p(dalpha), _p(ws), 0, 1.0,
-                                                        cd, _stream(x)), "recalgo_batchnorm_train_bwd_drop")
-    else:
-        _lib.check(lib.recalgo_batchnorm_train_bwd_act(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), _p(sums), rows, C, int(kind), _p(z), _p(alpha),
-                                                       _p(dz), _p(dgamma), _p(dbeta), None if defer else _p(dalpha), _p(ws), 0,
-                                                       _stream(x)), "recalgo_batchnorm_train_bwd_act")
+    cd, _keep = _cdrop(g_drop)
+    _lib.check(lib.recalgo_batchnorm_train_bwd(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), None if g_drop is not None else _p(sums),
+                                               rows, C, int(kind), _p(z), _p(alpha), _p(dz), _p(dgamma), _p(dbeta),
+                                               None if defer else _p(dalpha), _p(ws), 0, 1.0, cd, _stream(x)), "recalgo_batchnorm_train_bwd")
     if defer:
         nb = bn_partial_rows(rows)
         _colsum_pending.append((ws.view(torch.float32), nb * 2 * C, nb, C, C, dalpha))
@@ -1715,7 +1695,7 @@ def batchnorm_sync_fwd(x, gamma, beta, moving_mean, moving_var, momentum: float,
     mean = torch.empty(C, device=x.device, dtype=torch.float32)
     rstd = torch.empty(C, device=x.device, dtype=torch.float32)
     _lib.check(lib.recalgo_batchnorm_apply(_p(x), _p(gamma), _p(beta), _p(parts), world, rows, C, eps, momentum,
-                                           _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(rstd), _stream(x)),
+                                           _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(rstd), None, _stream(x)),
                "recalgo_batchnorm_apply")
     return y, mean, rstd
 
@@ -1745,20 +1725,15 @@ def batchnorm_train_bwd(x, gamma, mean, rstd, g, dgamma, dbeta, sums=None, relu_
     rows, C = x.shape
     lib = _lib_()
     dx = torch.empty_like(x)
-    if relu_scale != 1.0 or g_drop is not None:
-        ws = _workspace(lib.recalgo_batchnorm_bwd_act_workspace_bytes(rows, C), x.device)
-        cd, _keep = _cdrop(g_drop)
-        _lib.check(lib.recalgo_batchnorm_train_bwd_drop(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), None if g_drop is not None else _p(sums),
-                                                        rows, C, -1, None, None, _p(dx), _p(dgamma), _p(dbeta), None, _p(ws),
-                                                        int(relu_x), float(relu_scale), cd, _stream(x)), "recalgo_batchnorm_train_bwd_drop")
-        return dx
-    if sums is not None:
+    if sums is not None and relu_scale == 1.0 and g_drop is None:
         _lib.check(lib.recalgo_batchnorm_bwd_apply(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), _p(sums), 1, 0, rows, C, _p(dx),
                                                    _p(dgamma), _p(dbeta), int(relu_x), _stream(x)), "recalgo_batchnorm_bwd_apply")
         return dx
-    ws = _workspace(lib.recalgo_batchnorm_workspace_bytes(rows, C), x.device)
-    _lib.check(lib.recalgo_batchnorm_train_bwd(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), rows, C, _p(dx), _p(dgamma),
-                                               _p(dbeta), _p(ws), int(relu_x), _stream(x)), "recalgo_batchnorm_train_bwd")
+    ws = _workspace(lib.recalgo_batchnorm_bwd_workspace_bytes(rows, C), x.device)
+    cd, _keep = _cdrop(g_drop)
+    _lib.check(lib.recalgo_batchnorm_train_bwd(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), None if g_drop is not None else _p(sums),
+                                               rows, C, _ACT_NONE, None, None, _p(dx), _p(dgamma), _p(dbeta), None, _p(ws), int(relu_x),
+                                               float(relu_scale), cd, _stream(x)), "recalgo_batchnorm_train_bwd")
     return dx
 
 
@@ -2135,9 +2110,10 @@ def _cdrop(d: Optional["DropSpec"]):
     return ctypes.byref(c), c
 
 
-def _dropout_launch(fn_name: str, x: torch.Tensor, d: DropSpec) -> torch.Tensor:
+def _dropout_launch(x: torch.Tensor, d: DropSpec) -> torch.Tensor:
     y = torch.empty_like(x)
-    _lib.check(getattr(_lib_(), fn_name)(_p(x), x.numel(), d.rate, _p(d.mask), d.seed, d.call, _p(d.step), _p(y), _stream(x)), fn_name)
+    _lib.check(_lib_().recalgo_dropout_fwd(_p(x), x.numel(), d.rate, _p(d.mask), d.seed, d.call, _p(d.step), _p(y), _stream(x)),
+               "recalgo_dropout_fwd")
     return y
 
 
@@ -2145,11 +2121,12 @@ class _DropoutFn(Function):
     @staticmethod
     def forward(ctx, x, d: DropSpec):
         ctx.d = d
-        return _dropout_launch("recalgo_dropout_fwd", x.contiguous(), d)
+        return _dropout_launch(x.contiguous(), d)
 
     @staticmethod
     def backward(ctx, g):
-        return _dropout_launch("recalgo_dropout_bwd", g.contiguous(), ctx.d), None
+        # the gradient of the keep-mask scale is the same scale: the same map with the same key
+        return _dropout_launch(g.contiguous(), ctx.d), None
 
 
 def dropout(x: torch.Tensor, d: DropSpec) -> torch.Tensor:

@@ -143,9 +143,10 @@ def test_dense_merged_bwd_is_bit_identical_to_the_two_launches(dev, M, K, N):
 
 @pytest.mark.parametrize("M,K,N", [(4096, 416, 512), (4096, 512, 256), (300, 82, 100), (65, 48, 8), (64, 33, 68)])
 def test_dense_fwd_leaves_the_batchnorm_moments_of_its_tiles(dev, M, K, N):
-    """recalgo_dense_fwd_bn: the epilogue's per-tile (mean, sum of squared deviations) rows are what recalgo_batchnorm_moments
-    computes from y in a pass of its own (same layout, same two-pass definition), y itself is unchanged, and BatchNorm fed
-    with them equals BatchNorm computing its own moments (dense -> batch_normalization, deepfm.py:207-211)."""
+    """recalgo_dense_fwd(bn_partials=): the epilogue's per-tile (mean, sum of squared deviations) rows are what
+    recalgo_batchnorm_moments computes from y in a pass of its own (same layout, same two-pass definition), y itself is
+    unchanged, and BatchNorm fed with them equals BatchNorm computing its own moments (dense -> batch_normalization,
+    deepfm.py:207-211)."""
     import ctypes
     from recalgorithm_amd import _lib
     lib = _lib.load()
@@ -183,8 +184,8 @@ def test_dense_fwd_leaves_the_batchnorm_moments_of_its_tiles(dev, M, K, N):
 @pytest.mark.parametrize("M,K,N", [(4096, 416, 512), (300, 82, 100), (65, 48, 8)])
 def test_dense_activation_batchnorm_as_one_node(dev, M, K, N, kind):
     """The hidden layer of DIN's fcn scope (dense -> dice | prelu -> batch_normalization, din.py:262-266) as the fused launches
-    (recalgo_dense_fwd_act_bn, recalgo_batchnorm_train_bwd_act) against the three layers' own kernels one after the other —
-    and both against the definition in fp64."""
+    (recalgo_dense_fwd and recalgo_batchnorm_train_bwd with act_kind) against the three layers' own kernels one after the
+    other — and both against the definition in fp64."""
     import ctypes
     from recalgorithm_amd import _lib
     lib = _lib.load()
@@ -272,9 +273,10 @@ def test_dense_activation_batchnorm_as_one_node(dev, M, K, N, kind):
 
 @pytest.mark.parametrize("M,K,N", [(4096, 512, 256), (4096, 256, 128), (300, 100, 52), (65, 8, 48)])
 def test_dense_bwd_leaves_the_batchnorm_backward_sums(dev, M, K, N):
-    """recalgo_dense_bwd_bn: a layer whose input is a BatchNorm's output (batch_normalization -> dense, deepfm.py:207-211)
-    leaves, per 64-row tile of its input gradient, colsum(dx) and colsum(dx * xhat) — what recalgo_batchnorm_bwd_sums computes
-    from dx in a pass of its own — with dx / dw / dbias unchanged; BatchNorm's backward fed with them equals the two-launch one."""
+    """recalgo_dense_bwd(bn_partials=): a layer whose input is a BatchNorm's output (batch_normalization -> dense,
+    deepfm.py:207-211) leaves, per 64-row tile of its input gradient, colsum(dx) and colsum(dx * xhat) — what
+    recalgo_batchnorm_bwd_sums computes from dx in a pass of its own — with dx / dw / dbias unchanged; BatchNorm's backward
+    fed with them equals the two-launch one."""
     import ctypes
     from recalgorithm_amd import _lib
     lib = _lib.load()
@@ -313,7 +315,7 @@ def test_dense_bwd_leaves_the_batchnorm_backward_sums(dev, M, K, N):
 
 @pytest.mark.parametrize("M,K,N,with_bn", [(4096, 512, 256, False), (300, 100, 52, False), (65, 82, 50, False), (4096, 256, 128, True)])
 def test_dense_bwd_masks_its_input_gradient_with_the_relu_output_below(dev, M, K, N, with_bn):
-    """recalgo_dense_bwd_bn(dx_relu_mask=): dx = (g * [y > 0]) W^T zeroed where the mask tensor is <= 0 (the row-wise
+    """recalgo_dense_bwd(dx_relu_mask=): dx = (g * [y > 0]) W^T zeroed where the mask tensor is <= 0 (the row-wise
     epilogue, the element-wise one for widths that are not float4-addressable, the BatchNorm-sums epilogue); dW / db unchanged."""
     gen = torch.Generator().manual_seed(M + K + N)
     x = torch.randn(M, K, generator=gen).clamp(min=0).to(dev)       # a ReLU output: the mask IS the layer's input

@@ -168,8 +168,9 @@ def test_captured_step_with_dropout_equals_eager(dev, model):
 @pytest.mark.parametrize("M,K,N", [(4096, 416, 512), (300, 82, 52), (65, 48, 8)])
 @pytest.mark.parametrize("explicit", [False, True])
 def test_dropout_in_the_dense_epilogue_and_the_batchnorm_kernels_equals_the_separate_launches(dev, M, K, N, explicit):
-    """recalgo_dense_fwd_drop / recalgo_batchnorm_apply_drop / recalgo_batchnorm_train_bwd_drop against the same layers with the
-    dropout as launches of its own (ops.dropout): bit-identical outputs, tile moments of the DROPPED tensor, and gradients."""
+    """The `drop` options of recalgo_dense_fwd / recalgo_batchnorm_apply / recalgo_batchnorm_train_bwd against the same
+    layers with the dropout as launches of its own (ops.dropout): bit-identical outputs, tile moments of the DROPPED tensor,
+    and gradients."""
     gen = torch.Generator().manual_seed(M + N)
     x = torch.randn(M, K, generator=gen).to(dev)
     w = (torch.randn(K, N, generator=gen) / K ** 0.5).to(dev)
