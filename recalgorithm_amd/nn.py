@@ -702,12 +702,9 @@ class _L2RegFn(Function):
         # ops overwrite .grad during their own backward, in autograd order.  To be order independent
         # the regulariser's contribution is parked and added by `apply_parked_grads` (called by the
         # optimizer before the update).
-        for v in ctx.vars:
-            _PARKED.append((v, ctx.scale, g))
+        from . import ops
+        ops._parked_l2.extend((v, ctx.scale, g) for v in ctx.vars)
         return None, None, None
-
-
-_PARKED = []
 
 
 def apply_parked_grads(step_dev=None):
@@ -716,8 +713,8 @@ def apply_parked_grads(step_dev=None):
     grad += scale * g * w for every parked l2 term."""
     from . import ops
     ops.flush_dense_splits(step_dev)
-    while _PARKED:
-        v, scale, g = _PARKED.pop()
+    while ops._parked_l2:
+        v, scale, g = ops._parked_l2.pop()
         v.grad.add_(v.data * (scale * g))
 
 

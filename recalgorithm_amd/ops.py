@@ -55,14 +55,33 @@ def _chk(t: torch.Tensor, dtype, name: str):
 _ws_cache = {}
 
 
-def arena_row_base(arena, table_name: str, device) -> torch.Tensor:
-    """int64 [1] device tensor holding the first arena row of `table_name`.  Cached ON the arena object: a
-    module-level cache keyed by id(arena) hands a dead arena's row bases to a new arena that re-uses its address."""
-    cache = arena.__dict__.setdefault("_row_base_1", {})
-    t = cache.get(table_name)
-    if t is None or t.device != torch.device(device):
-        t = cache[table_name] = torch.tensor([arena.tables[table_name][0]], dtype=torch.int64, device=device)
-    return t
+# Work a training step leaves for a later launch of the same step: what each entry holds, who fills it, who drains it.  The
+# first two are drained inside the forward / backward that filled them; the rest by the optimizer's nn.apply_parked_grads
+# -> flush_dense_splits().  A step whose backward stopped with an exception is never drained: discard_step_work() drops all
+# of it when the next forward begins.
+_lazy_gathers: list = []     # (out, ids, arena, row_base): embedding_gather inside gather_feeds_cross; taken by cross_stack,
+#                              or launched by flush_lazy_gathers()
+_cross_rider = None          # (cross node, g): the CrossNet backward the fused tail hands over early (defer_cross_rider); taken
+#                              by the next deferred dense_bwd without a GradJoin, or cleared by the node's own backward
+_wgrad_rider = None          # (x, g, dw, dbias): the fused tail's weight gradient (defer_wgrad_rider); taken by the next deferred
+#                              dense_bwd over the same batch, or launched on its own by launch_wgrad_rider() (flush, next rider)
+_dense_pending = []          # (M, K, N, ws, dw, dbias): split reductions of dense_bwd / dense_bwd_weights(defer=True)
+_colsum_pending = []         # (partials, element offset, rows, row_stride, n, out): plain column sums of partial rows
+_dlogit_partials = {}        # dlogit.data_ptr() -> (partials, column, rows, row_stride, B): the loss tail's sums of
+#                              d(loss)/d(logit), read by colsum_of_dlogit
+_parked_l2 = []              # (variable, scale, g): nn.l2_regularization's backward; added by nn.apply_parked_grads
+
+
+def discard_step_work() -> None:
+    """Drop the deferred work of a step that never reached its drain.  Launches nothing: nobody reads the outputs of a
+    dropped gather or sum (VariableStore.begin_call: a model_fn invocation starts)."""
+    global _wgrad_rider, _cross_rider
+    _lazy_gathers.clear()
+    _wgrad_rider = _cross_rider = None
+    _dense_pending.clear()
+    _colsum_pending.clear()
+    _dlogit_partials.clear()
+    _parked_l2.clear()
 
 
 def anchor_store(anchor):
@@ -144,7 +163,6 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
 LAZY_GATHER = True                           # module hook (tests / A-B): False = every gather is its own launch
 _lazy_gather_on = False
 _lazy_hit = False
-_lazy_gathers: list = []
 
 
 class gather_feeds_cross:
@@ -153,7 +171,6 @@ class gather_feeds_cross:
 
     def __enter__(self):
         global _lazy_gather_on
-        flush_lazy_gathers()                 # (nothing is pending here unless an earlier model_fn call ended in an exception)
         self._prev, _lazy_gather_on = _lazy_gather_on, bool(LAZY_GATHER)
         self._kept = False
         return self
@@ -495,12 +512,14 @@ class _CrossFn(Function):
 
     @staticmethod
     def backward(ctx, g):
+        global _cross_rider
         w, b = ctx.vars
         (x0p,) = ctx.saved_tensors
         B, dp = x0p.shape
         d = ctx.d
         L = w.data.shape[0]
-        _cross_rider[:] = [e for e in _cross_rider if e[0] is not ctx]      # (nobody gave it a ride: computed here, as always)
+        if _cross_rider is not None and _cross_rider[0] is ctx:
+            _cross_rider = None                                           # (nobody gave it a ride: computed here, as always)
         early, ctx.early = getattr(ctx, "early", None), None
         stale_dx = None
         if early is not None:
@@ -1312,32 +1331,7 @@ def dense_bwd_input(g: torch.Tensor, y_mask: Optional[torch.Tensor], w: torch.Te
     return dx
 
 
-_side_streams = {}
-_side_keepalive = []         # tensors a side-stream kernel still reads (kept alive until the streams are joined)
-_side_dirty = set()          # devices whose side stream has un-joined work
-
-
-def side_stream(device) -> "torch.cuda.Stream":
-    """The second HIP stream of the step (one per device): the weight-gradient GEMMs run on it, concurrently with the
-    input-gradient chain on the main stream (they only meet again in the step's deferred-sum launch)."""
-    key = (device.type, device.index)
-    st = _side_streams.get(key)
-    if st is None:
-        st = _side_streams[key] = torch.cuda.Stream(device=device)
-    return st
-
-
-def join_side_streams() -> None:
-    """Make the current stream wait for the side-stream work of this step."""
-    for dev in list(_side_dirty):
-        torch.cuda.current_stream(dev).wait_stream(side_stream(dev))
-    _side_dirty.clear()
-    _side_keepalive.clear()
-
-
 _dense_ws = {}
-_dense_pending = []          # deferred split reductions of this backward pass: (M, K, N, ws, dw, dbias)
-_colsum_pending = []         # deferred plain column sums: (partials, element offset, rows, row_stride, n, out)
 
 
 class _ColSum(ctypes.Structure):              # include/recalgo.h recalgo_colsum_t
@@ -1390,6 +1384,7 @@ def dense_bwd(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], 
     ReLU output of the layer below, whose backward then needs no mask (nn.ReluSource).
     bn = (bn_x [M, K] contiguous, mean [K], rstd [K], partials [bn_partial_rows(M), 2 K]): x is the output of a training-mode
     BatchNorm over bn_x — the launch also leaves the sums that BatchNorm's backward starts with."""
+    global _cross_rider
     x, g, w = _mat(x, "x"), _mat(g, "g"), _mat(w, "w")
     M, K = x.shape
     N = g.shape[1]
@@ -1448,68 +1443,66 @@ def dense_bwd(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], 
         if rider is not None:
             dense_bwd_weights(rx, rg, None, rdw, rdb, defer=True)          # (not on the vectorised tile paths: a launch of its own)
         if crider is not None:
-            _cross_rider.append(crider)                                    # (left to the cross node's own backward)
+            _cross_rider = crider                                          # (left to the cross node's own backward)
     _lib.check(lib.recalgo_dense_bwd(*main, _stream(x)), "recalgo_dense_bwd")
     if defer:
         _dense_pending.append((M, K, N, ws, dw, dbias))
     return dx
 
 
-# A weight gradient waiting for a launch to ride in (recalgo_dense_bwd_rider): left by the fused tail's backward (its layer's
-# operands are ready, the layer below runs its merged backward next), taken by the next deferred dense_bwd over the same batch;
-# whatever is still here when the deferred sums are flushed (or another rider arrives) is launched on its own.
-_wgrad_rider = []
-
-
+# A weight gradient waiting for a launch to ride in (recalgo_dense_bwd_rider): the fused tail's backward leaves it (its layer's
+# operands are ready, the layer below runs its merged backward next).
 def defer_wgrad_rider(x: torch.Tensor, g: torch.Tensor, dw: torch.Tensor, dbias: Optional[torch.Tensor]) -> None:
+    global _wgrad_rider
     launch_wgrad_rider()
-    _wgrad_rider.append((_mat(x, "x"), _mat(g, "g"), dw, dbias))
+    _wgrad_rider = (_mat(x, "x"), _mat(g, "g"), dw, dbias)
 
 
 def _take_wgrad_rider(M: int, device):
-    if not _wgrad_rider:
+    global _wgrad_rider
+    r = _wgrad_rider
+    if r is None or r[0].shape[0] != M or r[0].device != device or r[3] is None or not r[2].is_contiguous():
         return None
-    rx, rg, rdw, rdb = _wgrad_rider[0]
-    if rx.shape[0] != M or rx.device != device or rdb is None or not rdw.is_contiguous():
-        return None
-    return _wgrad_rider.pop()
+    _wgrad_rider = None
+    return r
 
 
 def launch_wgrad_rider() -> None:
-    while _wgrad_rider:
-        rx, rg, rdw, rdb = _wgrad_rider.pop()
+    global _wgrad_rider
+    if _wgrad_rider is not None:
+        (rx, rg, rdw, rdb), _wgrad_rider = _wgrad_rider, None
         dense_bwd_weights(rx, rg, None, rdw, rdb, defer=True)
 
 
-# The CrossNet backward waiting for a ride (recalgo_dense_bwd_rider's c_* arguments): left by the fused tail's backward, which
-# produces the cross branch's upstream gradient long before autograd runs the cross node (created first, it runs last); taken by
-# the next deferred dense_bwd WITHOUT a GradJoin of its own (the layer that shares x0 with the cross network needs the result).
-_cross_rider = []
+# The CrossNet backward waiting for a ride (recalgo_dense_bwd_rider's c_* arguments): the fused tail's backward produces the
+# cross branch's upstream gradient long before autograd runs the cross node (created first, it runs last); the layer that
+# shares x0 with the cross network needs the result, so only a dense_bwd WITHOUT a GradJoin of its own takes it.
 rider_stats = {"wgrad": 0, "cross": 0}       # launches that carried a rider (tests / bench read it)
 
 
 def defer_cross_rider(node, g: torch.Tensor) -> None:
     """node: the _CrossFn node of the cross output whose gradient g [B, d] the caller has just produced."""
-    _cross_rider.clear()
+    global _cross_rider
+    _cross_rider = None
     if getattr(node, "grad_join", None) is None or not cross_riders_enabled:
         return
     w, _ = node.vars
     L = int(w.data.shape[0])
     if (g.dim() == 2 and g.is_contiguous() and g.dtype == torch.float32 and g.shape[1] == node.d and node.d % 4 == 0
             and g.data_ptr() % 16 == 0 and _lib_().recalgo_dense_bwd_cross_rider_supported(int(node.d), L)):
-        _cross_rider.append((node, g))
+        _cross_rider = (node, g)
 
 
 cross_riders_enabled = True
 
 
 def _take_cross_rider(M: int, device):
-    if not _cross_rider:
+    global _cross_rider
+    r = _cross_rider
+    if r is None or r[1].shape[0] != M or r[1].device != device:
         return None
-    node, g = _cross_rider[0]
-    if g.shape[0] != M or g.device != device:
-        return None
-    return _cross_rider.pop()
+    _cross_rider = None
+    return r
 
 
 def _cross_rider_args(node, g):
@@ -1549,8 +1542,8 @@ def flush_dense_splits(step_dev: Optional[torch.Tensor] = None) -> None:
     """Finish every deferred sum of the step in ONE launch: the weight-gradient split reductions of `dense`, the column
     sums the loss tail left behind, and (`step_dev`, the optimizer's int64 step counter) the step increment — the
     optimizer kernel that follows then only reads the counter."""
-    join_side_streams()
     launch_wgrad_rider()
+    _dlogit_partials.clear()                 # (keyed by an address: no entry may outlive its step's deferred-sum launch)
     if not _dense_pending and not _colsum_pending and step_dev is None:
         return
     jobs = (_DenseSplit * max(len(_dense_pending), 1))()
@@ -1998,9 +1991,6 @@ def concat_sumsq(parts, scale: float, joins=None):
     """-> (concat(parts, -1) [B, C], scale * sum(concat^2) as a detached [1] tensor); 1..4 fp32 [B, w] device tensors.
     joins {part index: nn.GradJoin}: that part's gradient block is parked for its other consumer's backward kernel."""
     return _ConcatSumsqFn.apply(float(scale), joins, *parts)
-
-
-_dlogit_partials = {}
 
 
 def colsum_of_dlogit(g: torch.Tensor, out: torch.Tensor) -> bool:

@@ -135,12 +135,14 @@ class VariableStore:
             self._scope.pop()
 
     def begin_call(self):
-        """A model_fn invocation == a fresh TF graph: auto-naming counters restart."""
+        """A model_fn invocation == a fresh TF graph: auto-naming counters restart, and what an earlier invocation left
+        undrained (its backward stopped with an exception) is dropped."""
         self._auto.clear()
         self._scope.clear()
         self._drop_calls = 0
-        from . import sparse
+        from . import ops, sparse
         sparse.new_forward(self)
+        ops.discard_step_work()
 
     def ensure_opt_state(self) -> dict:
         """The optimizer's device-side state {step int64[1], lr_t float[1]}: created on first use (the optimizer's first

@@ -543,3 +543,86 @@ def test_nfm_batched_lookups_with_an_unused_lookup_are_bit_identical(dev):
     assert runs[True][0] == runs[False][0]
     for k in runs[False][1]:
         assert_bit_exact(runs[True][1][k], runs[False][1][k], what=f"nfm {k}: batched lookups vs separate prepares")
+
+
+class _AbandonedStep(Exception):
+    pass
+
+
+def _step_work():
+    from recalgorithm_amd import ops
+    return {"lazy_gathers": bool(ops._lazy_gathers), "cross_rider": ops._cross_rider is not None,
+            "wgrad_rider": ops._wgrad_rider is not None, "dense_pending": bool(ops._dense_pending),
+            "colsum_pending": bool(ops._colsum_pending), "dlogit_partials": bool(ops._dlogit_partials),
+            "parked_l2": bool(ops._parked_l2)}
+
+
+def _abandon_case(model, dev):
+    """-> (estimator, four batches of one size).  No BatchNorm: a training-mode forward updates the moving averages by
+    design, also in a step that is abandoned later."""
+    if model != "pnn":
+        kw = dict(hidden=("256", "256", "128")) if model == "dcn" else dict(batch_norm=False)     # (dcn: fused tail + both riders)
+        est, _, feats, labels = make(model, dev, **kw)
+        spec = synth.SynthSpec(n_fields=8, max_vocab=400, seed=11, oov_frac=0.05)
+        return est, [(feats, labels)] + [synth.device_features(spec, 300, dev, batch_index=i)[:2] for i in (1, 2, 3)]
+    from recalgorithm_amd.algorithm.PNN.pnn import pnn_model_fn
+    spec = synth.SynthSpec(n_fields=7, max_vocab=300, seed=23, oov_frac=0.05)
+    cats = [fc.categorical_column_with_identity(n, v) for n, v in zip(spec.names, spec.vocabs)]
+    params = {"category_feature_columns": [fc.embedding_column(c, 8) for c in cats], "hidden_units": ["32", "16"],
+              "dropout_rate": 0.0, "batch_norm": False, "learning_rate": 0.005, "output_dimension": 48,
+              "product_method": "IPNN", "weight_regularizer": 0.01, "embedding_dim": 8}
+    est = Estimator(pnn_model_fn, params, RunConfig(device=dev, seed=5))
+    batches = [synth.device_features(spec, 170, dev, batch_index=i)[:2] for i in range(4)]
+    est.build(*batches[0])
+    return est, batches
+
+
+@pytest.mark.parametrize("model,abort_at,left", [
+    ("dcn", "first", {"wgrad_rider", "cross_rider", "colsum_pending", "dlogit_partials"}),
+    ("dcn", "last", {"dense_pending", "colsum_pending", "dlogit_partials"}),
+    ("deepfm", "last", {"dense_pending", "colsum_pending", "dlogit_partials"}),
+    ("pnn", "last", {"dense_pending", "parked_l2"})], ids=["dcn-first", "dcn-last", "deepfm", "pnn"])
+def test_abandoned_step_leaves_nothing_to_the_next(dev, monkeypatch, model, abort_at, left):
+    """A step whose backward stops with an exception (raised in host code at its first or last dense_bwd) never reaches the
+    optimizer's drain.  The next forward drops what it left (ops.discard_step_work), each normal step drains everything, and
+    the steps that follow are BIT-identical to those of an estimator that never ran the abandoned one."""
+    from recalgorithm_amd import ops
+    a, batches = _abandon_case(model, dev)
+    b, _ = _abandon_case(model, dev)
+    real = ops.dense_bwd
+    calls = {"n": 0, "at": None, "left": None}
+
+    def dense_bwd(*args, **kw):
+        calls["n"] += 1
+        if calls["n"] == calls["at"]:
+            calls["left"] = {k for k, v in _step_work().items() if v}
+            raise _AbandonedStep()
+        return real(*args, **kw)
+    monkeypatch.setattr(ops, "dense_bwd", dense_bwd)
+    b.train_step(*batches[1])                    # (counts the dense_bwd calls of a step)
+    n_calls, calls["n"] = calls["n"], 0
+    assert n_calls > 1
+    a.train_step(*batches[1])
+    calls["n"], calls["at"] = 0, 1 if abort_at == "first" else n_calls
+    with pytest.raises(_AbandonedStep):
+        a.train_step(*batches[0])
+    assert calls["left"] is not None and left <= calls["left"], calls["left"]
+    calls["at"] = None
+    for est in (a, b):
+        for bt in (batches[2], batches[0], batches[3]):
+            est.train_step(*bt)
+            assert not any(_step_work().values()), _step_work()
+    torch.cuda.synchronize()
+    assert int(a.store.opt_state["step"]) == int(b.store.opt_state["step"]) == 4
+    a.store.sync()
+    b.store.sync()
+    A, B_ = a.store.named_arrays(), b.store.named_arrays()
+    assert set(A) == set(B_)
+    for k in B_:
+        assert_bit_exact(A[k], B_[k], f"{model} {k}")
+    for n, ar in b.store.arenas.items():
+        if ar.m is not None:
+            assert_bit_exact(a.store.arenas[n].m, ar.m, f"{model} arena {n}.m")
+            assert_bit_exact(a.store.arenas[n].v, ar.v, f"{model} arena {n}.v")
+    assert_bit_exact(a.store.flat_m, b.store.flat_m, f"{model} dense m")
+    assert_bit_exact(a.store.flat_v, b.store.flat_v, f"{model} dense v")
