@@ -37,7 +37,7 @@ typedef void* recalgo_stream_t; /* hipStream_t */
 
 /* ABI version of this header (bumped on any signature change).  include/recalgo.abi records the hash of the declarations
  * each version stands for; tests/test_abi.py fails when the declarations change and this number does not. */
-#define RECALGO_ABI_VERSION 4
+#define RECALGO_ABI_VERSION 5
 int recalgo_abi_version(void);
 /* "gfx950" */
 const char* recalgo_target_arch(void);
@@ -922,6 +922,49 @@ int recalgo_scatter_apply(const recalgo_scatter_source_t* sources, int n_sources
                           float beta2, float eps, recalgo_stream_t stream);
 int recalgo_adam_deferred_sweep(const recalgo_deferred_adam_t* deferred, int K, int64_t row_begin, int64_t row_end,
                                 const int64_t* step_dev, int step_offset, recalgo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * MMoE gate-mix: the bias-free softmax gates and the mix of the expert outputs, one streaming launch each way.
+ * Replaces the G tf.layers.dense(x, n, activation=tf.nn.softmax, use_bias=False) gates, the [B, E, H] tf.concat of
+ * the experts and the per-task tf.matmul(experts, gate, transpose_a=True) + tf.squeeze of algorithm/MMOE/mmoe.py:208-232
+ * (and, through the selection table, the per-task / shared gates of algorithm/PLE/extraction_network.py).
+ *   z_g = x Wg (x [B, In] with row stride ldx; gate_kernels[g] [In, n_sel[g]], HOST array of G device pointers)
+ *   p_g = softmax(z_g), max-subtracted;  p [B, sum n_sel] keeps every gate's probabilities (columns in gate order)
+ *   outs[g][b, :] = sum_j p_g[b, j] * experts[sel_g[j]][b, :]        experts: HOST array of E device pointers, each a
+ *                   contiguous [B, H]; sel: HOST array of sum n_sel expert indices, gate after gate (MMoE: 0..E-1 for each)
+ * backward (d_outs[g] NULL: that gate received no gradient; d_experts / d_experts[e] / dx may be NULL):
+ *   d_experts[e] = sum_{g, j: sel_g[j] = e} p_g[j] * d_outs[g]       relu_experts != 0: zeroed where experts[e] <= 0 (the
+ *                  experts are ReLU outputs: the layer that made them gets its pre-activation gradient)
+ *   dp_g[j] = <d_outs[g], experts[sel_g[j]]>;  dz_g = p_g * (dp_g - sum_j p_g[j] dp_g[j])
+ *   dx [B, In] (row stride lddx) = sum_g dz_g Wg^T                    the gates' share of d x only
+ *   partials [recalgo_gate_mix_partial_rows(B)][In * sum n_sel]: per-workgroup sums of x^T dz_g; gate g's [In, n_sel[g]]
+ *   gradient is the run of In * n_sel[g] columns that starts at In * (n_sel[0] + .. + n_sel[g-1]).  Their fixed-order column
+ *   sums (recalgo_colsum_t jobs of recalgo_dense_bwd_weights_reduce) are the gate kernels' gradients: no float atomics.
+ * Served (recalgo_gate_mix_supported, n_total = sum n_sel; anything else returns hipErrorInvalidValue): H % 4 == 0,
+ * E, G, n_sel[g] <= RECALGO_GATE_MIX_MAX, In <= 512, and the staged gate kernels within their LDS budget of 16 KiB:
+ * In * (n_total | 1) <= 4096 floats.  Experts, outputs and their gradients on 16-byte aligned bases use 16-byte accesses;
+ * any unaligned base selects the scalar-access arm of the same kernels.
+ * ------------------------------------------------------------------------------------------ */
+#define RECALGO_GATE_MIX_MAX 16
+int recalgo_gate_mix_supported(int In, int E, int G, int H, int n_total);
+int recalgo_gate_mix_partial_rows(int B);
+int recalgo_gate_mix_fwd(const float* x, int ldx, const float* const* gate_kernels, const int* n_sel, const int* sel,
+                         const float* const* experts, int B, int In, int E, int G, int H, float* const* outs, float* p,
+                         recalgo_stream_t stream);
+int recalgo_gate_mix_bwd(const float* x, int ldx, const float* const* gate_kernels, const int* n_sel, const int* sel,
+                         const float* const* experts, const float* p, const float* const* d_outs, int B, int In, int E, int G,
+                         int H, int relu_experts, float* const* d_experts, float* dx, int lddx, float* partials,
+                         recalgo_stream_t stream);
+
+/* The loss tail of a multi-task model in ONE launch.  Replaces, per task, tf.sigmoid + tf.reduce_mean(
+ * tf.nn.sigmoid_cross_entropy_with_logits) and the tf.add_n of the task losses: algorithm/MMOE/mmoe.py:235,247-249.
+ *   logits, labels: HOST arrays of T (<= RECALGO_GATE_MIX_MAX) device pointers to [B] vectors
+ *   prob [B, T];  losses [T]: every task's mean sigmoid-CE, the value recalgo_sigmoid_ce_fwd_bwd gives for that task bit
+ *   for bit (same loop, same reduction tree);  total [1] = ((losses[0] + losses[1]) + ..)
+ *   dlogit [T, B] (may be NULL): d total / d logit_t * grad_scale */
+int recalgo_multitask_sigmoid_ce_fwd_bwd(const float* const* logits, const float* const* labels, int T, int B,
+                                         float grad_scale, float* prob, float* losses, float* total, float* dlogit,
+                                         recalgo_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RECALGO_HIP_LIB") or os.path.join(_HERE, "librecalgo_hip.so")
 
 P = c_void_p  # device pointer / stream
-ABI_VERSION = 4  # == RECALGO_ABI_VERSION of include/recalgo.h (bumped on any signature change)
+ABI_VERSION = 5  # == RECALGO_ABI_VERSION of include/recalgo.h (bumped on any signature change)
 
 # name -> (restype, argtypes); must list every function of include/recalgo.h
 SIGNATURES = {
@@ -134,6 +134,11 @@ SIGNATURES = {
     "recalgo_scatter_apply": (c_int, [P, c_int, P, c_int, P, c_int64, c_int, c_int, P, P, P, P, P, c_int64, P, P, c_int,
                                       c_float, c_float, c_float, c_float, P]),
     "recalgo_adam_deferred_sweep": (c_int, [P, c_int, c_int64, c_int64, P, c_int, P]),
+    "recalgo_gate_mix_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),
+    "recalgo_gate_mix_partial_rows": (c_int, [c_int]),
+    "recalgo_gate_mix_fwd": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P]),
+    "recalgo_gate_mix_bwd": (c_int, [P, c_int, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int, P, P]),
+    "recalgo_multitask_sigmoid_ce_fwd_bwd": (c_int, [P, P, c_int, c_int, c_float, P, P, P, P, P]),
 }
 
 _lib = None

@@ -107,8 +107,9 @@ def write_predictions(estimator, example_parser, out_csv="predictions.csv"):
             w.writerow(row)
 
 
-def run_estimator(model_fn, params, example_parser):
-    """main() body shared by the scripts: train_and_evaluate, evaluate, predict."""
+def run_estimator(model_fn, params, example_parser, predictions_writer=None):
+    """main() body shared by the scripts: train_and_evaluate, evaluate, predict (predictions_writer: a script whose
+    prediction keys are not `probabilities` writes its own predictions.csv)."""
     print(params)
     estimator = Estimator(model_fn=model_fn, params=params,
                           config=RunConfig(model_dir=FLAGS.model_dir,
@@ -137,7 +138,7 @@ def run_estimator(model_fn, params, example_parser):
         filepath=FLAGS.eval_data, example_parser=example_parser, batch_size=FLAGS.batch_size))
     for key in sorted(metrics):
         print("%s: %s" % (key, metrics[key]))
-    write_predictions(estimator, example_parser)
+    (predictions_writer or write_predictions)(estimator, example_parser)
     return estimator
 
 

@@ -2,6 +2,7 @@
 #include "deferred.h"
 #include "act.h"
 #include "plan_scan.h"
+#include "sigmoid_ce.h"
 
 namespace {
 
@@ -14,32 +15,11 @@ __global__ __launch_bounds__(1024) void sigmoid_ce_kernel(
     float grad_scale, float* __restrict__ prob, float* __restrict__ loss,
     float* __restrict__ dlogit) {
     __shared__ float red[16];
-    float acc = 0.f;
-    const float invB = 1.0f / (float)B;
-    for (unsigned i = threadIdx.x; i < B; i += 1024) {
-        float x = logits[i], z = labels[i];
-        float ax = fabsf(x);
-        float e = expf(-ax);
-        // tf.nn.sigmoid_cross_entropy_with_logits: max(x,0) - x*z + log1p(exp(-|x|))
-        acc += fmaxf(x, 0.f) - x * z + log1pf(e);
-        float r = e / (1.0f + e);
-        float p = x >= 0.f ? 1.0f / (1.0f + e) : r;
-        prob[i] = p;
-        // d/dx in the form TF's autodiff of the three terms produces:
-        //   [x>=0] - z -/+ e/(1+e)     (keeps 1e-13-size gradients at |x| ~ 30)
-        if (dlogit) {
-            float d = ((x >= 0.f ? 1.0f : 0.f) - z) + (x >= 0.f ? -r : r);
-            dlogit[i] = d * grad_scale * invB;
-        }
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float v = threadIdx.x < 16 ? red[threadIdx.x] : 0.f;
-        v = wave_sum(v);
-        if (threadIdx.x == 0) loss[0] = v * invB;
-    }
+    // (the loop and the reduction tree: sigmoid_ce.h, shared with the multi-task tail of csrc/mmoe.hip)
+    const float l = sigmoid_ce_task(
+        logits, labels, B, grad_scale, dlogit != nullptr, red, [&](unsigned i, float p) { prob[i] = p; },
+        [&](unsigned i, float d) { dlogit[i] = d; });
+    if (threadIdx.x == 0) loss[0] = l;
 }
 
 // ---------------------------------------------------------------------------------------

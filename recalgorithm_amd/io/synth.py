@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -122,12 +122,15 @@ def make_id_batch(spec: SynthSpec, B: int, batch_index: int = 0, names: Optional
     return ids, labels, dense, hist, tags
 
 
-def device_features(spec: SynthSpec, B: int, device, batch_index: int = 0, sorted_layout: bool = True):
+def device_features(spec: SynthSpec, B: int, device, batch_index: int = 0, sorted_layout: bool = True,
+                    extra_labels: Sequence[str] = ()):
     """Already-encoded, device-resident (features, labels) for the throughput configs.  The id
     matrix is laid out in sorted(column-name) order so that fc.input_layer can hand it to the
     gather kernel without a copy; features[name] are column views of it.  With a history (the DIN layout) the target
     `feedid` is a sequence column looked up on its own: it gets its own contiguous [B] vector after the matrix of the other
-    fields, so that both lookups read the batch in place."""
+    fields, so that both lookups read the batch in place.
+    extra_labels (multi-task models): further keys of LABELS the label dict carries besides `read_comment`, each a [B, 1]
+    float tensor of its own drawn from its own stream (2 % positives, as write_tfrecord's); the default batch is unchanged."""
     from ..feature_column import Ragged
     names = sorted(spec.names) if sorted_layout else list(spec.names)
     ids, labels, dense, hist, tags = make_id_batch(spec, B, batch_index, names)
@@ -174,6 +177,11 @@ def device_features(spec: SynthSpec, B: int, device, batch_index: int = 0, sorte
     if tags is not None:
         feats["manual_tag_list"] = Ragged(piece(k), piece(k + 1))
     lab = {"read_comment": piece(1).view(B, 1)}
+    for nm in extra_labels:
+        if nm not in LABELS[1:]:
+            raise ValueError(f"device_features: extra label {nm!r} is not one of {LABELS[1:]}")
+        rng = np.random.default_rng([spec.seed, batch_index, 11, LABELS.index(nm)])
+        lab[nm] = torch.from_numpy((rng.random((B, 1)) < 0.02).astype(np.float32)).to(device)
     return feats, lab, feats_meta
 
 

@@ -76,3 +76,36 @@ def finish_model_fn(mode, logit: torch.Tensor, labels, params,
     optimizer = opt_cls(learning_rate=params["learning_rate"], beta1=0.9, beta2=0.999, epsilon=1e-8)
     train_op = optimizer.minimize(loss=loss)
     return EstimatorSpec(mode, loss=loss, train_op=train_op, predictions={"probabilities": prob})
+
+
+def finish_multitask_model_fn(mode, logits: Dict[str, torch.Tensor], labels, params) -> EstimatorSpec:
+    """The tail of a multi-task model_fn (/root/reference algorithm/MMOE/mmoe.py:234-262): `logits` maps task name -> [B, 1]
+    logit, in task order.  PREDICT: {"<task>_probabilities"}; EVAL: the summed loss and eval_<task>_accuracy / eval_<task>_auc;
+    TRAIN: Adam on the sum of the tasks' mean sigmoid-CE (one loss launch: ops.multitask_sigmoid_cross_entropy).
+    The single-logit fused tails (LazyLogit, ops.tail_dense_head, the riders) hold ONE head per step — one rider slot, one
+    `_dlogit_partials` entry — so every tower logit is evaluated by its own head kernel (LazyLogit.materialize) here."""
+    from .nn import LazyLogit
+    names = list(logits)
+    ts = [t.materialize() if isinstance(t, LazyLogit) else t for t in logits.values()]
+    if mode == ModeKeys.PREDICT:
+        preds = {f"{n}_probabilities": torch.sigmoid(t) for n, t in zip(names, ts)}
+        return EstimatorSpec(mode, predictions=preds, export_outputs={"prediction": preds})
+
+    ys = [labels[n] for n in names]
+    if current_store().building:            # variable-registration pass: nothing is launched
+        loss, probs = ts[0].new_zeros(()), [torch.zeros_like(t) for t in ts]
+    else:
+        loss, _, prob = ops.multitask_sigmoid_cross_entropy(ts, ys)
+        probs = [prob[:, i:i + 1] for i in range(len(names))]
+    if mode == ModeKeys.EVAL:
+        acc = {f"eval_{n}_accuracy": metrics.accuracy(labels=y, predictions=(p >= 0.5).to(torch.float32))
+               for n, y, p in zip(names, ys, probs)}
+        auc = {f"eval_{n}_auc": metrics.auc(labels=y, predictions=p) for n, y, p in zip(names, ys, probs)}
+        return EstimatorSpec(mode, loss=loss, eval_metric_ops={**acc, **auc})
+
+    assert mode == ModeKeys.TRAIN
+    opt_cls = LazyAdamOptimizer if params.get("lazy_adam") else AdamOptimizer      # lazy_adam: labelled deviation (§8f-1)
+    optimizer = opt_cls(learning_rate=params["learning_rate"], beta1=0.9, beta2=0.999, epsilon=1e-8)
+    train_op = optimizer.minimize(loss=loss)
+    return EstimatorSpec(mode, loss=loss, train_op=train_op,
+                         predictions={f"{n}_probabilities": p for n, p in zip(names, probs)})

@@ -452,6 +452,117 @@ def dense_relu_dropout_bn(x, units, dropout_rate, batch_norm: bool, training: bo
     return net
 
 
+class InputGradChain:
+    """A tensor that feeds the MMoE gates AND the E expert layers (mmoe.py:197-215) receives the sum of 1 + E input
+    gradients.  Shared by `gate_mix` and `expert_layers`: the gates' backward (it runs first: it consumes the experts)
+    offers its share here instead of returning it, and the expert layers add theirs one after the other through the beta * C
+    epilogue of their input-gradient GEMM (ops.dense_bwd c_in) and return the total — no elementwise add launches.  Made per
+    model_fn invocation, so an abandoned backward leaves nothing behind.
+    An offer is accepted only when a consumer that WILL return the input gradient has registered in its forward
+    (`expert_layers` over an input that needs a gradient, called before `gate_mix`): otherwise the gates return their share to
+    autograd as any op does, and nothing can be dropped."""
+
+    def __init__(self):
+        self.first: Optional[torch.Tensor] = None
+        self.closed = False
+        self.consumers = 0
+
+    def register_consumer(self) -> None:
+        self.consumers += 1
+
+    def offer(self, dx: torch.Tensor) -> bool:
+        if self.consumers == 0 or self.closed or self.first is not None:
+            return False
+        self.first = dx
+        return True
+
+    def take(self) -> Optional[torch.Tensor]:
+        t, self.first, self.closed = self.first, None, True
+        return t
+
+
+class _ExpertsFn(Function):
+    """E sibling tf.layers.dense(x, units, relu) over ONE input as one autograd node: E GEMM launches each way; the input
+    gradients are chained through the dgrad GEMM's beta * C term, starting with what the InputGradChain holds."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, chain: Optional[InputGradChain], srcs, *kb):
+        from . import ops
+        ctx.set_materialize_grads(False)
+        x2 = x if x.stride(1) == 1 else x.contiguous()
+        ks, bs = kb[0::2], kb[1::2]
+        ys = [ops.dense_fwd(x2, k.data, b.data, True) for k, b in zip(ks, bs)]
+        ctx.vars, ctx.chain, ctx.srcs = (ks, bs), chain, srcs
+        if chain is not None and ctx.needs_input_grad[1]:
+            chain.register_consumer()        # (this node's backward returns d x: it takes what the chain holds)
+        else:
+            ctx.chain = None
+        ctx.save_for_backward(x2, *ys)
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *gs):
+        from . import ops
+        x2, *ys = ctx.saved_tensors
+        ks, bs = ctx.vars
+        need_x = ctx.needs_input_grad[1]
+        dx = ctx.chain.take() if ctx.chain is not None else None
+        if dx is not None and (tuple(dx.shape) != tuple(x2.shape) or dx.stride(1) != 1):
+            raise ValueError("expert_layers: the chained input gradient does not have the input's shape")
+        for k, b, y, g, src in zip(ks, bs, ys, gs, ctx.srcs):
+            if g is None:
+                continue
+            g2 = g if g.is_contiguous() else g.contiguous()
+            mask = None if src.take(g2) else y       # (ops.gate_mix masked the gradient it wrote: nn.ReluSource)
+            if need_x:
+                dx = ops.dense_bwd(x2, g2, mask, k.data, k.grad, b.grad, c_in=dx, beta=0.0 if dx is None else 1.0, defer=True,
+                                   cross_rider=False)
+            else:
+                ops.dense_bwd_weights(x2, g2, mask, k.grad, b.grad, defer=True)
+        return (None, dx if need_x else None, None, None) + (None,) * (2 * len(ks))
+
+
+def expert_layers(x: torch.Tensor, units, num_experts: int, chain: Optional[InputGradChain] = None):
+    """[tf.layers.dense(x, units, activation=tf.nn.relu, name=f"expert_{i}") for i in range(num_experts)] (mmoe.py:199-202):
+    variables <scope>/expert_<i>/{kernel,bias}.  -> the list of expert outputs [B, units]."""
+    store = current_store()
+    units = int(units)
+    kb = []
+    for i in range(int(num_experts)):
+        with store.variable_scope(f"expert_{i}"):
+            kb.append(store.get_variable("kernel", (x.shape[-1], units), glorot_uniform))
+            kb.append(store.get_variable("bias", (units,), zeros))
+    if store.building:
+        return [x.new_zeros(x.shape[0], units) for _ in range(int(num_experts))]
+    if not (x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and _mfma_dense(x.shape[1])):
+        raise NotImplementedError("expert_layers: a 2-D fp32 device input of up to DENSE_MAX_K features")
+    srcs = [ReluSource() for _ in range(int(num_experts))]
+    outs = list(_ExpertsFn.apply(store.anchor, x, chain, srcs, *kb))
+    for o, src in zip(outs, srcs):
+        o._recalgo_relu_src = src
+    return outs
+
+
+def gate_mix(x: torch.Tensor, experts, num_gates: int, selection=None, chain: Optional[InputGradChain] = None):
+    """The `gates` scope and the per-task mix of mmoe.py:208-232: num_gates bias-free softmax gates
+    tf.layers.dense(x, n_g, activation=tf.nn.softmax, use_bias=False, name=f"gate_{i}") and, per gate,
+    tf.squeeze(tf.matmul(experts, gate[..., None], transpose_a=True), -1) — one kernel each way (ops.gate_mix).
+    Variables: <scope>/gate_<i>/kernel.  -> (the num_gates mixed tensors [B, H], the gate probabilities [B, sum n_g])."""
+    from . import ops
+    store = current_store()
+    experts = list(experts)
+    E = len(experts)
+    selection = [list(range(E)) for _ in range(int(num_gates))] if selection is None else [list(s) for s in selection]
+    kernels = []
+    for i, sel in enumerate(selection):
+        with store.variable_scope(f"gate_{i}"):
+            kernels.append(store.get_variable("kernel", (x.shape[-1], len(sel)), glorot_uniform))
+    if store.building:
+        return [torch.zeros_like(experts[0]) for _ in selection], x.new_zeros(x.shape[0], sum(len(s) for s in selection))
+    return ops.gate_mix(x if x.stride(-1) == 1 else x.contiguous(), kernels, experts, selection, x_grad_sink=chain,
+                        anchor=store.anchor, return_gates=True)
+
+
 def dense_with(x: torch.Tensor, kernel: Variable, bias: Optional[Variable] = None, relu: bool = False) -> torch.Tensor:
     """tf.matmul(x, kernel) (+ bias) (+ relu) on variables the model created itself with tf.get_variable (AFM's attention
     network, afm.py:168-190): the same kernels as `dense` (one-unit outputs go through the head kernel)."""

@@ -2019,6 +2019,193 @@ def logit_loss(store, labels: torch.Tensor, heads, bias, parts, addends, loss_ad
 
 
 # =============================================================================================
+# MMoE (csrc/mmoe.hip): softmax gates + expert mix, the multi-task loss tail
+# =============================================================================================
+GATE_MIX_MAX = 16                            # include/recalgo.h RECALGO_GATE_MIX_MAX
+
+
+def _colsum_now(jobs, device_tensor: torch.Tensor) -> None:
+    """The fixed-order column sums of `jobs` (entries as in _colsum_pending) in a launch of their own."""
+    sums = (_ColSum * len(jobs))()
+    for i, (part, off, rows, stride, n, out) in enumerate(jobs):
+        sums[i] = _ColSum(part.data_ptr() + 4 * off, out.data_ptr(), rows, stride, n)
+    _lib.check(_lib_().recalgo_dense_bwd_weights_reduce((_DenseSplit * 1)(), 0, sums, len(jobs), None, _stream(device_tensor)),
+               "recalgo_dense_bwd_weights_reduce")
+
+
+class GateMixSpec:
+    """What `_GateMixFn` needs besides its tensors: the gate kernels (Variables: the gradient goes to Variable.grad through the
+    step's deferred column sums; tensors: returned by backward), the selection table, whether the experts are ReLU outputs
+    whose gradient this op masks, and where the gates' share of d x goes (x_grad_sink.first instead of autograd)."""
+
+    def __init__(self, kernels, selection, relu_sources, x_grad_sink):
+        self.kernels, self.selection, self.relu_sources, self.x_grad_sink = kernels, selection, relu_sources, x_grad_sink
+        self.n_sel = (ctypes.c_int * len(selection))(*[len(s) for s in selection])
+        flat = [int(e) for s in selection for e in s]
+        self.sel = (ctypes.c_int * len(flat))(*flat)
+        self.n_total = len(flat)
+
+
+class _GateMixFn(Function):
+    """include/recalgo.h recalgo_gate_mix_fwd / recalgo_gate_mix_bwd: G outputs [B, H]."""
+
+    @staticmethod
+    def forward(ctx, anchor, spec: GateMixSpec, x, *tensors):
+        ctx.set_materialize_grads(False)     # a gate nobody differentiates: NULL upstream gradient, no zero tensor
+        G = len(spec.kernels)
+        experts, gate_ts = tensors[:len(tensors) - G], tensors[len(tensors) - G:]
+        ws = [k.data if isinstance(k, Variable) else t for k, t in zip(spec.kernels, gate_ts)]
+        B, In = x.shape
+        E, H = len(experts), experts[0].shape[1]
+        outs = [torch.empty(B, H, device=x.device, dtype=torch.float32) for _ in range(G)]
+        p = torch.empty(B, spec.n_total, device=x.device, dtype=torch.float32)
+        _lib.check(_lib_().recalgo_gate_mix_fwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts),
+                                                B, In, E, G, H, _ptr_array(outs), _p(p), _stream(x)), "recalgo_gate_mix_fwd")
+        ctx.spec, ctx.ws, ctx.E = spec, ws, E
+        ctx.save_for_backward(x, p, *experts)
+        ctx.mark_non_differentiable(p)
+        return (*outs, p)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        spec, ws, E = ctx.spec, ctx.ws, ctx.E
+        x, p, *experts = ctx.saved_tensors
+        G = len(ws)
+        gs = [None if g is None else (g if g.is_contiguous() else g.contiguous()) for g in grads[:G]]
+        B, In = x.shape
+        H = experts[0].shape[1]
+        lib = _lib_()
+        need_x = ctx.needs_input_grad[2]
+        need_e = ctx.needs_input_grad[3:3 + E]
+        dx = torch.empty(B, In, device=x.device, dtype=torch.float32) if need_x else None
+        dex = [torch.empty_like(t) if nd else None for t, nd in zip(experts, need_e)]
+        rows = int(lib.recalgo_gate_mix_partial_rows(B))
+        partials = torch.empty(rows, In * spec.n_total, device=x.device, dtype=torch.float32)
+        relu = spec.relu_sources is not None
+        _lib.check(lib.recalgo_gate_mix_bwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts), _p(p),
+                                            _ptr_array(gs), B, In, E, G, H, int(relu), _ptr_array(dex), _p(dx), In, _p(partials),
+                                            _stream(x)), "recalgo_gate_mix_bwd")
+        if relu:
+            for src, d in zip(spec.relu_sources, dex):
+                src.premasked = d            # (nn.ReluSource: the expert layers' backward then runs without mask loads)
+        # gate kernel gradients: fixed-order column sums of the per-workgroup partial rows
+        dws, now, off = [], [], 0
+        for k, w, nd in zip(spec.kernels, ws, ctx.needs_input_grad[3 + E:]):
+            n = In * w.shape[1]
+            if isinstance(k, Variable):
+                _colsum_pending.append((partials, off, rows, In * spec.n_total, n, k.grad))
+                dws.append(None)
+            elif nd:
+                dw = torch.empty_like(w)
+                now.append((partials, off, rows, In * spec.n_total, n, dw))
+                dws.append(dw)
+            else:
+                dws.append(None)
+            off += n
+        if now:
+            _colsum_now(now, x)
+        if need_x and spec.x_grad_sink is not None and spec.x_grad_sink.offer(dx):
+            dx = None                        # (the other consumers of x add it in their input-gradient epilogue)
+        return (None, None, dx, *dex, *dws)
+
+
+def gate_mix_supported(In: int, E: int, G: int, H: int, n_total: int) -> bool:
+    return bool(_lib_().recalgo_gate_mix_supported(int(In), int(E), int(G), int(H), int(n_total)))
+
+
+def gate_mix(x: torch.Tensor, gate_kernels, experts, selection=None, x_grad_sink=None, anchor=None, return_gates: bool = False):
+    """MMoE / CGC block behind the expert layers (mmoe.py:208-232): for every gate g,
+        out_g = sum_j softmax(x @ gate_kernels[g])[:, j, None] * experts[selection[g][j]]
+    x [B, In]; gate_kernels: G bias-free [In, n_g] kernels (Variables or tensors); experts: E [B, H] tensors;
+    selection[g]: the n_g expert indices gate g mixes (default: every gate over all E experts, MMoE).
+    -> the G outputs [B, H] (and the gate probabilities [B, sum n_g] with return_gates).
+    Experts that carry an nn.ReluSource (outputs of ReLU expert layers) get their gradient already masked.
+    x_grad_sink: an nn.InputGradChain shared with the other consumers of x — the gates' share of d x is handed to it instead
+    of to autograd.  Outside the kernel's limits (recalgo_gate_mix_supported): NotImplementedError."""
+    gate_kernels, experts = list(gate_kernels), list(experts)
+    E, G = len(experts), len(gate_kernels)
+    selection = [list(range(E)) for _ in range(G)] if selection is None else [list(s) for s in selection]
+    ws = [k.data if isinstance(k, Variable) else k for k in gate_kernels]
+    if x.dim() != 2 or len(selection) != G or any(tuple(w.shape) != (x.shape[1], len(s)) for w, s in zip(ws, selection)):
+        raise ValueError("gate_mix: one [In, n_g] gate kernel per selection row")
+    if any(len(s) < 1 for s in selection) or any(e < 0 or e >= E for s in selection for e in s):
+        raise ValueError("gate_mix: every gate selects at least one expert, indices in [0, E)")
+    if E < 1 or any(t.dim() != 2 or t.shape != experts[0].shape or t.shape[0] != x.shape[0] for t in experts):
+        raise ValueError("gate_mix: experts must be E same-shaped [B, H] tensors")
+    H = experts[0].shape[1]
+    n_total = sum(len(s) for s in selection)
+    if max(len(s) for s in selection) > GATE_MIX_MAX or not gate_mix_supported(x.shape[1], E, G, H, n_total):
+        raise NotImplementedError(
+            f"gate_mix serves H % 4 == 0, E, G, n_g <= {GATE_MIX_MAX}, In <= 512 and In * (sum n_g | 1) <= 4096; got In={x.shape[1]} "
+            f"E={E} G={G} H={H} sum n_g={n_total}")
+    if x.shape[0] == 0:
+        raise NotImplementedError("gate_mix: empty batch")
+    x = _mat(x, "x")
+    for w in ws:
+        _chk(w, torch.float32, "gate kernel")
+    srcs = [getattr(t, "_recalgo_relu_src", None) if getattr(t, "_recalgo_relu_scale", 1.0) == 1.0 else None for t in experts]
+    srcs = srcs if all(s is not None for s in srcs) else None
+    experts = [_mat(t if t.is_contiguous() else t.contiguous(), "expert") for t in experts]
+    spec = GateMixSpec(gate_kernels, selection, srcs, x_grad_sink)
+    gate_ts = [None if isinstance(k, Variable) else k for k in gate_kernels]
+    *outs, p = _GateMixFn.apply(anchor, spec, x, *experts, *gate_ts)
+    return (outs, p) if return_gates else outs
+
+
+class _MultiTaskCEFn(Function):
+    """include/recalgo.h recalgo_multitask_sigmoid_ce_fwd_bwd: T sigmoid-CE tails and their sum in one launch."""
+
+    @staticmethod
+    def forward(ctx, labels, *logits):
+        ctx.set_materialize_grads(False)
+        ctx.seed = _loss_seed
+        T, B = len(logits), logits[0].numel()
+        lgs = [t.contiguous().view(-1) for t in logits]
+        lbs = [t.contiguous().view(-1).to(torch.float32) for t in labels]
+        dev = lgs[0].device
+        prob = torch.empty(B, T, device=dev, dtype=torch.float32)
+        losses = torch.empty(T, device=dev, dtype=torch.float32)
+        total = torch.empty(1, device=dev, dtype=torch.float32)
+        dlogit = torch.empty(T, B, device=dev, dtype=torch.float32)
+        _lib.check(_lib_().recalgo_multitask_sigmoid_ce_fwd_bwd(
+            _ptr_array(lgs), _ptr_array(lbs), T, B, 1.0 if ctx.seed is None else ctx.seed, _p(prob), _p(losses), _p(total),
+            _p(dlogit), _stream(lgs[0])), "recalgo_multitask_sigmoid_ce_fwd_bwd")
+        ctx.save_for_backward(dlogit)
+        ctx.shapes = [t.shape for t in logits]
+        ctx.mark_non_differentiable(prob)
+        return total.view(()), losses, prob
+
+    @staticmethod
+    def backward(ctx, gtotal, glosses, _gprob):
+        (dlogit,) = ctx.saved_tensors
+        if gtotal is None and glosses is None:
+            return (None,) * (1 + len(ctx.shapes))
+        if ctx.seed is not None and glosses is None:
+            return (None, *[dlogit[t].view(s) for t, s in enumerate(ctx.shapes)])     # (the seed is baked in: ops.loss_seed)
+        out = []
+        for t, s in enumerate(ctx.shapes):
+            g = glosses[t] if glosses is not None else 0.0
+            g = g + gtotal if gtotal is not None else g
+            out.append((dlogit[t] * g).view(s))
+        return (None, *out)
+
+
+def multitask_sigmoid_cross_entropy(logits, labels):
+    """T logits [B, 1] and T labels -> (sum of the tasks' mean sigmoid-CE (scalar), the T task losses [T], probabilities
+    [B, T]); mmoe.py:235,247-249.  Every task's loss is `sigmoid_cross_entropy`'s value bit for bit."""
+    logits, labels = list(logits), list(labels)
+    if not 1 <= len(logits) <= GATE_MIX_MAX or len(labels) != len(logits):
+        raise NotImplementedError(f"multitask_sigmoid_cross_entropy: 1..{GATE_MIX_MAX} tasks, one label tensor each")
+    if any(t.numel() != logits[0].numel() for t in logits + labels) or logits[0].numel() == 0:
+        raise ValueError("multitask_sigmoid_cross_entropy: T logits and T labels of one batch size")
+    for t in logits:
+        if t.dtype != torch.float32:
+            raise TypeError("multitask_sigmoid_cross_entropy: fp32 logits")
+        _stream(t)
+    return _MultiTaskCEFn.apply(labels, *logits)
+
+
+# =============================================================================================
 # a12: PReLU / Dice
 # =============================================================================================
 class _ActFn(Function):
