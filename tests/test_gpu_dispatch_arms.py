@@ -50,16 +50,20 @@ def _st():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _shifted(t, dev):
-    """A contiguous device copy of `t` one float past a fresh allocation: passes ops._chk, is not 16-byte aligned."""
-    v = torch.empty(t.numel() + 1, device=dev, dtype=t.dtype)[1:].view(t.shape)
-    v.copy_(t)
+def _shifted(t, dev, place=None):
+    """A contiguous device copy of `t` one float past a fresh allocation: passes ops._chk, is not 16-byte aligned.
+    `place(t, dev, shifted=True)`: another way to put it there (tests/redzone.py's guard.input, test_gpu_redzone.py)."""
+    if place is not None:
+        v = place(t, dev, shifted=True)
+    else:
+        v = torch.empty(t.numel() + 1, device=dev, dtype=t.dtype)[1:].view(t.shape)
+        v.copy_(t)
     assert v.is_contiguous() and v.data_ptr() % 16 != 0
     return v
 
 
-def _aligned(t, dev):
-    v = t.to(dev)
+def _aligned(t, dev, place=None):
+    v = t.to(dev) if place is None else place(t, dev)
     assert v.data_ptr() % 16 == 0
     return v
 

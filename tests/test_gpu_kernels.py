@@ -57,6 +57,30 @@ def test_gather_empty_batch(dev):
     assert out.shape == (0, 32)
 
 
+@pytest.mark.parametrize("rows,K,M", [(7, 1, 1), (50, 16, 300), (301, 8, 257), (1000, 1, 4097), (90, 6, 1000)])
+def test_scatter_rows_sorted_against_index_add(dev, rows, K, M):
+    """ops.scatter_rows_sorted (recalgo_scatter_rows_sorted; DeepFM's arena that is not on the owner-computes path while its
+    partner is): grad[rows[i]] += vals[i], rows < 0 skipped, on top of what the gradient arena holds; the fp64 index_add is
+    the reference.  Deterministic: a second arena fed the same requests ends bit-identical."""
+    gen = torch.Generator().manual_seed(rows + M)
+    ids = zipf_ids(gen, M, rows, 0.05)
+    vals = torch.randn(M, K, generator=gen)
+    base = torch.randn(rows, K, generator=gen)
+    ref = base.double().index_add(0, ids[ids >= 0], vals[ids >= 0].double())
+    ref32 = base.index_add(0, ids[ids >= 0], vals[ids >= 0])
+    grads = []
+    for _ in range(2):
+        ar, _ = make_arena([rows], K, dev)
+        ar.grad.copy_(base)
+        ops.scatter_rows_sorted(ar, ids.to(dev), vals.to(dev))
+        grads.append(ar.grad.clone())
+    assert_close(grads[0], ref, what="sorted scatter", reduced=True, ref32=ref32)
+    assert_bit_exact(grads[1], grads[0], "sorted scatter is reproducible")
+    untouched = torch.ones(rows, dtype=torch.bool)
+    untouched[ids[ids >= 0]] = False
+    assert_bit_exact(grads[0].cpu()[untouched], base[untouched], "rows without a request")
+
+
 def _bags(gen, B, vocab, maxlen, oov=0.1):
     lens = torch.randint(0, maxlen + 1, (B,), generator=gen)
     lens[0] = 0

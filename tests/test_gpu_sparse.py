@@ -172,6 +172,63 @@ def test_scatter_sources_ragged_and_broadcast(dev):
     assert_close(w1.grad, ref1, what="broadcast gradient rows (first-order weights)", reduced=True)
 
 
+@pytest.mark.parametrize("B,K,T", [(1, 4, 1), (130, 8, 5), (300, 16, 12)])
+def test_batched_lookups_equal_one_launch_per_lookup(dev, B, K, T):
+    """sparse.batch_lookups: three TRAIN lookups of one arena issued in a block share ONE prepare launch
+    (recalgo_scatter_prepare_multi) and the two plain gathers ONE forward launch (recalgo_lookup_multi_fwd).  Outputs, sequence
+    lengths and the summed row gradients are bit-identical to one launch per lookup; the outputs are the exact table rows
+    and the gradient is the fp64 scatter-add of the three gradient matrices."""
+    import contextlib
+    from oracle import ref_ops as R
+    from recalgorithm_amd import ops, sparse
+    from recalgorithm_amd.variables import EmbeddingArena, VariableStore
+    gen = torch.Generator().manual_seed(B + K)
+    vocabs = [50, 301, 7]
+    ids_a = torch.stack([torch.randint(-1, v, (B,), generator=gen) for v in vocabs], 1)
+    ids_b = torch.stack([torch.randint(-1, v, (B,), generator=gen) for v in vocabs], 1)
+    lens = torch.randint(0, T + 1, (B,), generator=gen)
+    lens[-1] = T
+    offs = torch.cat([torch.zeros(1, dtype=torch.int64), lens.cumsum(0)])
+    vals = torch.randint(-1, vocabs[1], (int(lens.sum()),), generator=gen)
+    ga, gb = torch.randn(B, 3 * K, generator=gen), torch.randn(B, 3 * K, generator=gen)
+    gs = torch.randn(B, T, K, generator=gen)
+    runs = []
+    for batched in (False, True):
+        ar = EmbeddingArena("t", K, dev, seed=4)
+        for i, v in enumerate(vocabs):
+            ar.add_table(f"t{i}", v)
+        ar.materialize()
+        rb = torch.tensor([ar.tables[f"t{i}"][0] for i in range(3)], dtype=torch.int64, device=dev)
+        store = VariableStore(dev)
+        merged = dict(sparse.prepare_stats)
+        with (sparse.batch_lookups() if batched else contextlib.nullcontext()), torch.enable_grad():
+            a = ops.embedding_gather(store, ids_a.to(dev), ar, rb)
+            b = ops.embedding_gather(store, ids_b.to(dev), ar, rb)
+            s, sl = ops.sequence_gather(store, vals.to(dev), offs.to(dev), ar, "t1", T)
+        if batched:
+            assert sparse.prepare_stats["merged"] - merged["merged"] == 2, "one prepare launch for the three lookups"
+            assert sparse.prepare_stats["merged_lookups"] - merged["merged_lookups"] >= 1, "the plain gathers share a launch"
+        torch.autograd.backward([a, b, s], [ga.to(dev), gb.to(dev), gs.to(dev)])
+        runs.append((a.detach(), b.detach(), s.detach(), sl, ar.grad.clone(), ar.weight.cpu(), rb.cpu()))
+    for x, y, nm in zip(runs[0][:5], runs[1][:5], ("gather a", "gather b", "sequence", "sequence length", "row gradients")):
+        assert_bit_exact(y, x, f"batched vs one launch per lookup: {nm}")
+    a, b, s, sl, grad, w, rb = runs[1]
+    tabs = [w[int(rb[f]):int(rb[f]) + vocabs[f]] for f in range(3)]
+    for out, ids, nm in ((a, ids_a, "a"), (b, ids_b, "b")):
+        assert_bit_exact(out, torch.cat([R.embedding_lookup_single(ids[:, f], tabs[f]) for f in range(3)], 1), f"gather {nm}")
+    seq_ref, len_ref = R.sequence_lookup(vals, offs, tabs[1], T)
+    assert_bit_exact(s, seq_ref, "sequence gather")
+    assert torch.equal(sl.cpu().long(), len_ref)
+
+    def table_grad(dt):
+        wt = w.to(dt).requires_grad_(True)
+        tb = [wt[int(rb[f]):int(rb[f]) + vocabs[f]] for f in range(3)]
+        outs = [torch.cat([R.embedding_lookup_single(ids[:, f], tb[f]) for f in range(3)], 1) for ids in (ids_a, ids_b)]
+        torch.autograd.backward(outs + [R.sequence_lookup(vals, offs, tb[1], T)[0]], [ga.to(dt), gb.to(dt), gs.to(dt)])
+        return wt.grad
+    assert_close(grad, table_grad(torch.float64), what="batched lookups: row gradients", reduced=True, ref32=table_grad(torch.float32))
+
+
 @pytest.mark.parametrize("rows,K,F,period", [(3001, 16, 3, 4), (777, 8, 1, 3), (2000, 2, 2, 5), (1500, 1, 2, 4), (300, 64, 1, 2),
                                              (40000, 16, 4, 32), (3_000_000, 4, 1, 2)])     # (the last: sweep groups walk 16 rows each)
 def test_deferred_adam_is_bit_identical_to_dense_tf1_adam(dev, rows, K, F, period, monkeypatch):
