@@ -8,41 +8,19 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
+from ctypes import c_void_p
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 
+from .. import _abi
+
 _HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_HERE, "librecalgo_host.so")
 
-SIGNATURES = {
-    "recalgo_host_abi_version": (c_int, []),
-    "recalgo_crc32c": (c_uint32, [c_void_p, c_uint64]),
-    "recalgo_vocab_open": (c_void_p, [c_char_p]),
-    "recalgo_vocab_size": (c_int64, [c_void_p]),
-    "recalgo_vocab_lookup": (c_int64, [c_void_p, c_char_p, c_uint64]),
-    "recalgo_vocab_close": (None, [c_void_p]),
-    "recalgo_reader_open": (c_void_p, [c_char_p, c_int]),
-    "recalgo_reader_close": (None, [c_void_p]),
-    "recalgo_reader_rewind": (c_int, [c_void_p]),
-    "recalgo_reader_configure": (None, [c_void_p, c_int64, c_int64, c_uint64]),
-    "recalgo_reader_error": (c_char_p, [c_void_p]),
-    "recalgo_reader_next_batch": (c_int64, [c_void_p, c_int64]),
-    "recalgo_reader_float_feature": (c_int, [c_void_p, c_char_p, c_int, c_float, c_int, c_void_p]),
-    "recalgo_reader_id_feature": (c_int64, [c_void_p, c_char_p, c_void_p, c_void_p, c_void_p, c_int64]),
-    "recalgo_reader_id_matrix": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
-    "recalgo_pipeline_open": (c_void_p, [c_char_p, c_int, c_int64, c_int64, c_uint64, c_int64, c_int, c_void_p, c_void_p, c_int,
-                                         c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int]),
-    "recalgo_pipeline_next": (c_int64, [c_void_p, c_void_p]),
-    "recalgo_pipeline_release": (None, [c_void_p, c_int]),
-    "recalgo_pipeline_ids": (c_void_p, [c_void_p, c_int]),
-    "recalgo_pipeline_floats": (c_void_p, [c_void_p, c_int]),
-    "recalgo_pipeline_error": (c_char_p, [c_void_p]),
-    "recalgo_pipeline_threads": (c_int, [c_void_p]),
-    "recalgo_pipeline_close": (None, [c_void_p]),
-}
+ABI = _abi.read("recalgo_host.h")      # include/recalgo_host.h is the one statement of this ABI
+SIGNATURES = ABI.functions             # name -> (restype, argtypes) of every function of the header
 
 _lib = None
 
@@ -57,7 +35,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args
-    if lib.recalgo_host_abi_version() != 1:
+    if lib.recalgo_host_abi_version() != ABI.constants["RECALGO_HOST_ABI_VERSION"]:
         raise RuntimeError("librecalgo_host.so ABI version mismatch")
     _lib = lib
     return lib

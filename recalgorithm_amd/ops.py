@@ -18,8 +18,12 @@ from torch.autograd import Function
 from . import _lib, sparse
 from .variables import EmbeddingArena, Variable, VariableStore
 
-_ACT = {"prelu": 0, "dice": 1}
-_ACT_NONE = -1                               # include/recalgo.h RECALGO_ACT_NONE
+_C = _lib.CONSTANTS                          # the RECALGO_* #defines of include/recalgo.h
+_ACT = {"prelu": _C["RECALGO_ACT_PRELU"], "dice": _C["RECALGO_ACT_DICE"]}
+_ACT_NONE = _C["RECALGO_ACT_NONE"]
+# the structs of include/recalgo.h (ctypes classes derived from the header, fields in its order)
+_Live, _ColSum, _DenseSplit = (_lib.STRUCTS[n] for n in ("recalgo_live_t", "recalgo_colsum_t", "recalgo_dense_split_t"))
+_CDrop, _AdamArena = _lib.STRUCTS["recalgo_dropout_t"], _lib.STRUCTS["recalgo_adam_arena_t"]
 
 
 def _lib_():
@@ -42,7 +46,7 @@ def copy_bytes(dst: torch.Tensor, src: torch.Tensor) -> None:
     n = dst.numel() * dst.element_size()
     if n != src.numel() * src.element_size() or not dst.is_contiguous() or not src.is_contiguous() or dst.device != src.device:
         raise ValueError("copy_bytes: contiguous tensors of equal byte length on one device")
-    _lib.check(_lib_().recalgo_copy_bytes(_p(dst), _p(src), n, _stream(dst)), "recalgo_copy_bytes")
+    _lib_().recalgo_copy_bytes(_p(dst), _p(src), n, _stream(dst))
 
 
 def _chk(t: torch.Tensor, dtype, name: str):
@@ -103,13 +107,7 @@ def mark_live_rows(arena, ids: torch.Tensor, row_base: Optional[torch.Tensor], F
     if not getattr(arena, "tracks_live_rows", False):
         return
     live, lst, cnt = arena.live_state()
-    _lib.check(_lib_().recalgo_mark_live_rows(_p(ids), _p(row_base), ids.numel(), int(F), _p(live), _p(lst), _p(cnt),
-                                              _stream(ids)), "recalgo_mark_live_rows")
-
-
-class _Live(ctypes.Structure):          # include/recalgo.h recalgo_live_t
-    _fields_ = [("row_live", ctypes.c_void_p), ("live_list", ctypes.c_void_p), ("live_count", ctypes.c_void_p),
-                ("row_offset", ctypes.c_int64)]
+    _lib_().recalgo_mark_live_rows(_p(ids), _p(row_base), ids.numel(), int(F), _p(live), _p(lst), _p(cnt), _stream(ids))
 
 
 def _live(arena, row_offset: int = 0):
@@ -128,8 +126,7 @@ def scatter_rows_sorted(arena, rows: torch.Tensor, vals: torch.Tensor) -> None:
     rows = rows.reshape(-1).contiguous()
     vals = vals.reshape(rows.numel(), -1).contiguous()
     srt, perm = torch.sort(rows, stable=True)
-    _lib.check(_lib_().recalgo_scatter_rows_sorted(_p(srt), _p(perm), _p(vals), rows.numel(), vals.shape[1], _p(arena.grad),
-                                                   _stream(vals)), "recalgo_scatter_rows_sorted")
+    _lib_().recalgo_scatter_rows_sorted(_p(srt), _p(perm), _p(vals), rows.numel(), vals.shape[1], _p(arena.grad), _stream(vals))
     mark_live_rows(arena, rows, None, 1)
 
 
@@ -191,8 +188,8 @@ def flush_lazy_gathers() -> None:
         out, ids, arena, row_base = _lazy_gathers.pop()
         out._recalgo_lazy_gather = None
         B, F = ids.shape
-        _lib.check(_lib_().recalgo_embedding_gather_fwd(_p(ids), _p(arena.weight), _p(row_base), B, F, arena.K, _p(out), F * arena.K, 0,
-                                                        _stream(ids)), "recalgo_embedding_gather_fwd")
+        _lib_().recalgo_embedding_gather_fwd(_p(ids), _p(arena.weight), _p(row_base), B, F, arena.K, _p(out), F * arena.K, 0,
+                                             _stream(ids))
 
 
 def _take_lazy_gather(x0: torch.Tensor):
@@ -229,9 +226,8 @@ class _GatherFn(Function):
             return out
 
         def launch():
-            _lib.check(_lib_().recalgo_embedding_gather_fwd_deferred(
-                _p(ids), _p(arena.weight), _p(row_base), B, F, K, _p(out), F * K, 0, dv, stp, 0, _stream(ids)),
-                "recalgo_embedding_gather_fwd")
+            _lib_().recalgo_embedding_gather_fwd_deferred(
+                _p(ids), _p(arena.weight), _p(row_base), B, F, K, _p(out), F * K, 0, dv, stp, 0, _stream(ids))
         if batched:
             # behind the block's one `prepare` launch (the rows it catches up are read here); a plain lookup: it may share its
             # launch with the block's other plain lookups
@@ -249,9 +245,8 @@ class _GatherFn(Function):
             ctx.src.set_grad(g)              # summed per row (and applied) by the optimizer's recalgo_scatter_apply
             return None, None, None, None, None, None
         g = g.contiguous()
-        _lib.check(_lib_().recalgo_embedding_gather_bwd(
-            _p(ids), _p(g), _p(ctx.row_base), B, F, arena.K, F * arena.K, 0, _p(arena.grad), _live(arena),
-            _stream(ids)), "recalgo_embedding_gather_bwd")
+        _lib_().recalgo_embedding_gather_bwd(_p(ids), _p(g), _p(ctx.row_base), B, F, arena.K, F * arena.K, 0, _p(arena.grad),
+                                             _live(arena), _stream(ids))
         _flush(arena)
         return None, None, None, None, None, None
 
@@ -294,9 +289,8 @@ class _BagMeanFn(Function):
                                           values.numel(), 1, training)
         dv, stp = (None, None) if table_name == "__staged__" else sparse.view_for(ctx.src, arena, anchor_store(anchor))
         rb0 = 0 if table_name == "__staged__" else arena.tables[table_name][0]
-        _lib.check(_lib_().recalgo_embedding_bag_mean_fwd_deferred(
-            _p(values), _p(offsets), _p(table), B, K, _p(out), K, 0, dv, rb0, stp, 0, _stream(offsets)),
-            "recalgo_embedding_bag_mean_fwd_deferred")
+        _lib_().recalgo_embedding_bag_mean_fwd_deferred(
+            _p(values), _p(offsets), _p(table), B, K, _p(out), K, 0, dv, rb0, stp, 0, _stream(offsets))
         ctx.args = (values, offsets, arena, table_name)
         return out
 
@@ -313,9 +307,8 @@ class _BagMeanFn(Function):
             ctx.src.set_grad(g[bag] / cnt[bag].unsqueeze(1))
             return None, None, None, None, None, None
         gt = arena.grad[rb:rb + vocab]
-        _lib.check(_lib_().recalgo_embedding_bag_mean_bwd(
-            _p(values), _p(offsets), _p(g), B, arena.K, arena.K, 0, _p(gt), _live(arena, rb), _stream(offsets)),
-            "recalgo_embedding_bag_mean_bwd")
+        _lib_().recalgo_embedding_bag_mean_bwd(
+            _p(values), _p(offsets), _p(g), B, arena.K, arena.K, 0, _p(gt), _live(arena, rb), _stream(offsets))
         _flush(arena)
         return None, None, None, None, None, None
 
@@ -346,9 +339,8 @@ class _SeqGatherFn(Function):
         rb0 = 0 if table_name == "__staged__" else arena.tables[table_name][0]
 
         def launch():
-            _lib.check(_lib_().recalgo_sequence_gather_fwd_deferred(
-                _p(values), _p(offsets), _p(table), B, T, K, _p(out), _p(seq_len), dv, rb0, stp, 0, _stream(offsets)),
-                "recalgo_sequence_gather_fwd")
+            _lib_().recalgo_sequence_gather_fwd_deferred(
+                _p(values), _p(offsets), _p(table), B, T, K, _p(out), _p(seq_len), dv, rb0, stp, 0, _stream(offsets))
         if ctx.src is not None and getattr(ctx.src, "deferred", False):
             # (sparse.batch_lookups: behind the block's one `prepare` launch, possibly sharing ONE forward launch)
             job = (1, values, offsets, table, B, T, K, out, 0, 0, seq_len) if (dv is None and values.is_contiguous()) else None
@@ -372,9 +364,8 @@ class _SeqGatherFn(Function):
             return None, None, None, None, None, None, None
         g = g.contiguous()
         gt = arena.grad[rb:rb + vocab]
-        _lib.check(_lib_().recalgo_sequence_gather_bwd(
-            _p(values), _p(offsets), _p(g), B, T, arena.K, _p(gt), _live(arena, rb), _stream(offsets)),
-            "recalgo_sequence_gather_bwd")
+        _lib_().recalgo_sequence_gather_bwd(
+            _p(values), _p(offsets), _p(g), B, T, arena.K, _p(gt), _live(arena, rb), _stream(offsets))
         _flush(arena)
         return None, None, None, None, None, None, None
 
@@ -406,10 +397,9 @@ class _DeepFMSparseFn(Function):
         ctx.src, ctx.src1 = sparse.begin_lookup_pair(arena, w1, st, ids, row_base, B, F, training)
         dv, stp = sparse.view_for(ctx.src, arena, st)
         dv1, stp1 = sparse.view_for(ctx.src1, w1, st)
-        _lib.check(_lib_().recalgo_deepfm_sparse_fwd_deferred(
+        _lib_().recalgo_deepfm_sparse_fwd_deferred(
             _p(ids), _p(arena.weight), _p(w1.weight), _p(bias.data), _p(row_base), B, F, K,
-            _p(emb), _p(fm1), _p(fm2), _p(fsum), dv, dv1, stp if stp is not None else stp1, 0, _stream(ids)),
-            "recalgo_deepfm_sparse_fwd")
+            _p(emb), _p(fm1), _p(fm2), _p(fsum), dv, dv1, stp if stp is not None else stp1, 0, _stream(ids))
         ctx.args = (ids, arena, w1, bias, row_base)
         ctx.save_for_backward(emb, fsum)
         ctx.set_materialize_grads(False)      # (FwFM never uses fm2: no zero "gradient" is filled for it, one launch less)
@@ -448,9 +438,8 @@ class _DeepFMSparseFn(Function):
             if not colsum_of_dlogit(g_fm1, bias.grad.view(1)):      # (TRAIN step: a job of the step's deferred-sum launch)
                 torch.sum(g_fm1, dim=0, out=bias.grad.view(1))
             return None, None, None, None, None, None, None
-        _lib.check(_lib_().recalgo_deepfm_sparse_bwd(
-            _p(ids), _p(emb), _p(fsum), _p(g_emb), _p(g_fm1), _p(g_fm2), _p(row_base), B, F, arena.K,
-            _p(arena.grad), _p(w1.grad), _live(arena), _live(w1), _stream(ids)), "recalgo_deepfm_sparse_bwd")
+        _lib_().recalgo_deepfm_sparse_bwd(_p(ids), _p(emb), _p(fsum), _p(g_emb), _p(g_fm1), _p(g_fm2), _p(row_base), B, F, arena.K,
+                                          _p(arena.grad), _p(w1.grad), _live(arena), _live(w1), _stream(ids))
         _flush(arena)
         _flush(w1)
         torch.sum(g_fm1, dim=0, out=bias.grad.view(1))
@@ -494,17 +483,15 @@ class _CrossFn(Function):
         out = torch.empty(B, dp, device=x0.device, dtype=torch.float32)
         if lz is not None and dp == d and x0.is_contiguous():
             ids, arena, row_base = lz
-            _lib.check(_lib_().recalgo_gather_cross_fwd(_p(ids), _p(arena.weight), _p(row_base), B, ids.shape[1], arena.K, _p(wp), _p(bp), L,
-                                                        _p(x0), d, _p(out), dp, _stream(x0)), "recalgo_gather_cross_fwd")
+            _lib_().recalgo_gather_cross_fwd(_p(ids), _p(arena.weight), _p(row_base), B, ids.shape[1], arena.K, _p(wp), _p(bp), L,
+                                             _p(x0), d, _p(out), dp, _stream(x0))
         else:
             if lz is not None:               # (cannot be fused after all: the plain gather first)
                 ids, arena, row_base = lz
-                _lib.check(_lib_().recalgo_embedding_gather_fwd(_p(ids), _p(arena.weight), _p(row_base), B, ids.shape[1], arena.K, _p(x0),
-                                                                ids.shape[1] * arena.K, 0, _stream(ids)), "recalgo_embedding_gather_fwd")
+                _lib_().recalgo_embedding_gather_fwd(_p(ids), _p(arena.weight), _p(row_base), B, ids.shape[1], arena.K, _p(x0),
+                                                     ids.shape[1] * arena.K, 0, _stream(ids))
                 x0p = _pad4(x0)
-            _lib.check(_lib_().recalgo_cross_fwd(
-                _p(x0p), dp, _p(wp), _p(bp), B, dp, L, _p(out), dp, _stream(x0)),
-                "recalgo_cross_fwd")
+            _lib_().recalgo_cross_fwd(_p(x0p), dp, _p(wp), _p(bp), B, dp, L, _p(out), dp, _stream(x0))
         ctx.vars = (w, b)
         ctx.d = d
         ctx.save_for_backward(x0p)
@@ -559,9 +546,8 @@ class _CrossFn(Function):
         # the gradient the MLP branch parked for x0 is added in this kernel's epilogue (no separate add launch)
         extra = ctx.grad_join.take() if ctx.grad_join is not None else None
         fused_extra = extra is not None and dp == d and extra.is_contiguous() and tuple(extra.shape) == (B, d)
-        _lib.check(lib.recalgo_cross_bwd(
-            _p(x0p), dp, _p(wp), _p(bp), _p(g), dp, _p(extra) if fused_extra else None, B, dp, L, _p(dx0), _p(dw),
-            _p(db), _p(ws), int(defer), _stream(x0p)), "recalgo_cross_bwd")
+        lib.recalgo_cross_bwd(_p(x0p), dp, _p(wp), _p(bp), _p(g), dp, _p(extra) if fused_extra else None, B, dp, L, _p(dx0), _p(dw),
+                              _p(db), _p(ws), int(defer), _stream(x0p))
         if defer:
             rows, wsf = int(lib.recalgo_cross_bwd_partial_rows(B)), ws.view(torch.float32)
             _colsum_pending.append((wsf, 0, rows, 2 * L * dp, L * dp, dw))
@@ -598,9 +584,7 @@ class _CrossLayerFn(Function):
         wp, bp = _pad4(w.data.reshape(1, d)), _pad4(b.data.reshape(1, d))
         dp = x0p.shape[1]
         out = torch.empty(B, dp, device=x0.device, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_cross_layer_fwd(
-            _p(x0p), _p(xlp), dp, _p(wp), _p(bp), B, dp, _p(out), dp, _stream(x0)),
-            "recalgo_cross_layer_fwd")
+        _lib_().recalgo_cross_layer_fwd(_p(x0p), _p(xlp), dp, _p(wp), _p(bp), B, dp, _p(out), dp, _stream(x0))
         ctx.vars = (w, b)
         ctx.d = d
         ctx.save_for_backward(x0p, xlp)
@@ -621,9 +605,8 @@ class _CrossLayerFn(Function):
         else:
             wp, bp = _pad4(w.data.reshape(1, d)), _pad4(b.data.reshape(1, d))
             dw, db = torch.empty_like(wp), torch.empty_like(bp)
-        _lib.check(lib.recalgo_cross_layer_bwd(
-            _p(x0p), _p(xlp), dp, _p(wp), _p(bp), _p(g), dp, B, dp, _p(dx0), _p(dxl),
-            _p(dw), _p(db), _p(ws), _stream(x0p)), "recalgo_cross_layer_bwd")
+        lib.recalgo_cross_layer_bwd(_p(x0p), _p(xlp), dp, _p(wp), _p(bp), _p(g), dp, B, dp, _p(dx0), _p(dxl), _p(dw), _p(db),
+                                    _p(ws), _stream(x0p))
         if dp != d:
             w.grad.copy_(dw[:, :d].reshape(w.grad.shape))
             b.grad.copy_(db[:, :d].reshape(b.grad.shape))
@@ -661,9 +644,7 @@ class _CinFn(Function):
         Hk, N = h1 - h0, n1 - n0
         out = torch.empty(B, N, D, device=x0.device, dtype=torch.float32)
         pool = torch.empty(B, N, device=x0.device, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_cin_layer_fwd(
-            _p(x0), _p(xk_c), _p(w), B, m, Hk, N, D, _p(out), _p(pool), N, 0, _stream(x0)),
-            "recalgo_cin_layer_fwd")
+        _lib_().recalgo_cin_layer_fwd(_p(x0), _p(xk_c), _p(w), B, m, Hk, N, D, _p(out), _p(pool), N, 0, _stream(x0))
         ctx.filt, ctx.box, ctx.whole = filt, (h0, h1, n0, n1), whole
         ctx.xk_shape = xk.shape
         ctx.save_for_backward(x0, xk_c, w)
@@ -688,9 +669,8 @@ class _CinFn(Function):
             g_pool = None if g_pool is None else g_pool.contiguous()
             lib = _lib_()
             ws = _workspace(lib.recalgo_cin_layer_bwd_workspace_bytes(B, m, Hk, N, D), x0.device)
-            _lib.check(lib.recalgo_cin_layer_bwd(
-                _p(x0), _p(xk), _p(w), _p(g_out), _p(g_pool), N, 0, B, m, Hk, N, D,
-                _p(dx0), 0, _p(dxk), 0, _p(dw), _p(ws), _stream(x0)), "recalgo_cin_layer_bwd")
+            lib.recalgo_cin_layer_bwd(_p(x0), _p(xk), _p(w), _p(g_out), _p(g_pool), N, 0, B, m, Hk, N, D, _p(dx0), 0, _p(dxk), 0,
+                                      _p(dw), _p(ws), _stream(x0))
         if not ctx.whole:
             Hk_full = filt.data.shape[-2] // m
             filt.grad.reshape(Hk_full, m, filt.data.shape[-1])[h0:h1, :, n0:n1].copy_(dw.reshape(Hk, m, N))
@@ -720,8 +700,8 @@ class _CinStackFn(Function):
         for f, N in zip(filts, Ns):
             Hk = xk.shape[1]
             out = torch.empty(B, N, D, device=x0.device, dtype=torch.float32)
-            _lib.check(lib.recalgo_cin_layer_fwd(_p(x0), _p(xk), _p(f.data), B, m, Hk, N, D, _p(out), _p(p_plus), p_plus.shape[1], col,
-                                                 _stream(x0)), "recalgo_cin_layer_fwd")
+            lib.recalgo_cin_layer_fwd(_p(x0), _p(xk), _p(f.data), B, m, Hk, N, D, _p(out), _p(p_plus), p_plus.shape[1], col,
+                                      _stream(x0))
             xs.append(out)
             xk = out
             col += N
@@ -759,10 +739,9 @@ class _CinStackFn(Function):
                 continue
             dxk = torch.empty_like(xk)
             ws = _workspace(lib.recalgo_cin_layer_bwd_workspace_bytes(B, m, Hk, N, D), x0.device)
-            _lib.check(lib.recalgo_cin_layer_bwd(
+            lib.recalgo_cin_layer_bwd(
                 _p(x0), _p(xk), _p(filts[i].data), _p(g_out), _p(g_pplus), 0 if g_pplus is None else g_pplus.stride(0), cols[i],
-                B, m, Hk, N, D, _p(dx0), 0 if first else 1, _p(dxk), 0, _p(filts[i].grad), _p(ws), _stream(x0)),
-                "recalgo_cin_layer_bwd")
+                B, m, Hk, N, D, _p(dx0), 0 if first else 1, _p(dxk), 0, _p(filts[i].grad), _p(ws), _stream(x0))
             first = False
             g_next = dxk
         if first:
@@ -821,9 +800,8 @@ class _DinAttentionFn(Function):
         # vs = (f1_w, f1_b, f2_w, f2_b, f3_w, f3_b) Variables
         B, T, H = keys.shape
         out = torch.empty(B, H, device=query.device, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_din_attention_fwd(
-            _p(query), _p(keys), _p(keys_length), *[_p(v.data) for v in vs], B, T, H, int(is_softmax),
-            _p(out), _stream(query)), "recalgo_din_attention_fwd")
+        _lib_().recalgo_din_attention_fwd(_p(query), _p(keys), _p(keys_length), *[_p(v.data) for v in vs], B, T, H, int(is_softmax),
+                                          _p(out), _stream(query))
         ctx.vs, ctx.is_softmax, ctx.kl = vs, is_softmax, keys_length
         ctx.query_join = query_join
         ctx.in_step = _loss_seed is not None      # built inside Estimator.train_step: its optimizer runs the deferred sums
@@ -855,10 +833,9 @@ class _DinAttentionFn(Function):
         else:
             ws = _workspace(nbytes, query.device)
             grads = [_p(v.grad) for v in vs]
-        _lib.check(lib.recalgo_din_attention_bwd_joined(
-            _p(query), _p(keys), _p(ctx.kl), *[_p(v.data) for v in vs], _p(g), g.stride(0),
-            _p(extra) if fused_extra else None, extra.stride(0) if fused_extra else 0, B, T, H,
-            int(ctx.is_softmax), _p(dq), _p(dk), *grads, _p(ws), _stream(query)), "recalgo_din_attention_bwd")
+        lib.recalgo_din_attention_bwd_joined(_p(query), _p(keys), _p(ctx.kl), *[_p(v.data) for v in vs], _p(g), g.stride(0),
+                                             _p(extra) if fused_extra else None, extra.stride(0) if fused_extra else 0, B, T, H,
+                                             int(ctx.is_softmax), _p(dq), _p(dk), *grads, _p(ws), _stream(query))
         if ctx.in_step:
             rows, pf = int(lib.recalgo_din_attention_bwd_partial_rows(B)), int(lib.recalgo_din_attention_bwd_partial_floats(H))
             wsf, off = ws.view(torch.float32), 0
@@ -894,7 +871,8 @@ def din_attention(store, query, keys, keys_length, vs, is_softmax=False, query_j
 # =============================================================================================
 # K7/K8: FiBiNET SENET + bilinear interaction
 # =============================================================================================
-BILINEAR_TYPES = {"all": 0, "each": 1, "interaction": 2}
+BILINEAR_TYPES = {"all": _C["RECALGO_BILINEAR_ALL"], "each": _C["RECALGO_BILINEAR_EACH"],
+                  "interaction": _C["RECALGO_BILINEAR_INTERACTION"]}
 
 
 class _SenetFn(Function):
@@ -903,8 +881,7 @@ class _SenetFn(Function):
         B, F, K = emb.shape
         Rd = w1.data.shape[1]
         v = torch.empty_like(emb)
-        _lib.check(_lib_().recalgo_senet_fwd(_p(emb), _p(w1.data), _p(w2.data), B, F, K, Rd, _p(v), None,
-                                             _stream(emb)), "recalgo_senet_fwd")
+        _lib_().recalgo_senet_fwd(_p(emb), _p(w1.data), _p(w2.data), B, F, K, Rd, _p(v), None, _stream(emb))
         ctx.vars = (w1, w2)
         ctx.save_for_backward(emb)
         return v
@@ -919,8 +896,8 @@ class _SenetFn(Function):
         g = g.contiguous()
         ws = _workspace(lib.recalgo_senet_bwd_workspace_bytes(B, F, K, Rd), emb.device)
         d = torch.empty_like(emb)
-        _lib.check(lib.recalgo_senet_bwd(_p(emb), _p(w1.data), _p(w2.data), _p(g), B, F, K, Rd, _p(d), 0,
-                                         _p(w1.grad), _p(w2.grad), _p(ws), _stream(emb)), "recalgo_senet_bwd")
+        lib.recalgo_senet_bwd(_p(emb), _p(w1.data), _p(w2.data), _p(g), B, F, K, Rd, _p(d), 0,
+                              _p(w1.grad), _p(w2.grad), _p(ws), _stream(emb))
         return None, d, None, None
 
 
@@ -939,9 +916,8 @@ class _BilinearFn(Function):
         nv = 1 if x1 is None else 2
         P = (F - 1) * (F - 2) // 2
         out = torch.empty(B, P, nv * K, device=x0.device, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_bilinear_fwd(
-            _p(x0), _p(w0.data), _p(x1), None if w1 is None else _p(w1.data), B, F, K, btype, _p(out), nv * K, 0,
-            _stream(x0)), "recalgo_bilinear_fwd")
+        _lib_().recalgo_bilinear_fwd(_p(x0), _p(w0.data), _p(x1), None if w1 is None else _p(w1.data), B, F, K, btype, _p(out),
+                                     nv * K, 0, _stream(x0))
         ctx.vars, ctx.btype, ctx.nv = (w0, w1), btype, nv
         ctx.save_for_backward(x0, x1)
         return out
@@ -957,10 +933,8 @@ class _BilinearFn(Function):
         ws = _workspace(lib.recalgo_bilinear_bwd_workspace_bytes(B, F, K, nv, ctx.btype), x0.device)
         dx0 = torch.empty_like(x0)
         dx1 = None if x1 is None else torch.empty_like(x1)
-        _lib.check(lib.recalgo_bilinear_bwd(
-            _p(x0), _p(w0.data), _p(x1), None if w1 is None else _p(w1.data), _p(g), nv * K, 0, B, F, K, ctx.btype,
-            _p(dx0), _p(w0.grad), _p(dx1), None if w1 is None else _p(w1.grad), _p(ws), _stream(x0)),
-            "recalgo_bilinear_bwd")
+        lib.recalgo_bilinear_bwd(_p(x0), _p(w0.data), _p(x1), None if w1 is None else _p(w1.data), _p(g), nv * K, 0, B, F, K,
+                                 ctx.btype, _p(dx0), _p(w0.grad), _p(dx1), None if w1 is None else _p(w1.grad), _p(ws), _stream(x0))
         return None, None, dx0, None, dx1, None
 
 
@@ -983,7 +957,7 @@ def bilinear_interaction(store, btype: str, x0: torch.Tensor, w0: Variable,
 # =============================================================================================
 # K6: PNN product layer
 # =============================================================================================
-PNN_METHODS = {"IPNN": 0, "OPNN": 1}
+PNN_METHODS = {"IPNN": _C["RECALGO_PNN_IPNN"], "OPNN": _C["RECALGO_PNN_OPNN"]}
 
 
 class _PnnProductFn(Function):
@@ -1001,9 +975,8 @@ class _PnnProductFn(Function):
         st = _stream(emb_flat)
         phi = torch.empty(B, T4, device=emb_flat.device, dtype=torch.float32)      # padding columns zeroed by the kernel
         omega = _pnn_omega(product_w, T4, D)                                        # padding rows stay zero
-        _lib.check(lib.recalgo_pnn_features_fwd(_p(emb_flat), B, F, K, method, _p(phi), T4, st), "recalgo_pnn_features_fwd")
-        _lib.check(lib.recalgo_pnn_weights_fwd(_p(product_w.data), D, F, K, method, _p(omega), st),
-                   "recalgo_pnn_weights_fwd")
+        lib.recalgo_pnn_features_fwd(_p(emb_flat), B, F, K, method, _p(phi), T4, st)
+        lib.recalgo_pnn_weights_fwd(_p(product_w.data), D, F, K, method, _p(omega), st)
         # lz + lp + bias, ReLU  (pnn.py:139,175,178,181)
         y = dense_fwd(emb_flat, linear_w.data.reshape(-1, D), bias.data.reshape(-1), True, x2=phi, w2=omega)
         ctx.vars = (linear_w, product_w, bias)
@@ -1028,10 +1001,8 @@ class _PnnProductFn(Function):
         dphi = dense_bwd(phi, g, y, omega, domega, None)
         d_emb = dense_bwd(emb_flat, g, y, linear_w.data.reshape(-1, D), linear_w.grad.view(-1, D), bias.grad.view(-1),
                           defer=True)
-        _lib.check(lib.recalgo_pnn_features_bwd(_p(emb_flat), _p(dphi), T4, B, F, K, method, _p(d_emb), 1, st),
-                   "recalgo_pnn_features_bwd")
-        _lib.check(lib.recalgo_pnn_weights_bwd(_p(product_w.data), _p(domega), D, F, K, method, _p(product_w.grad), st),
-                   "recalgo_pnn_weights_bwd")
+        lib.recalgo_pnn_features_bwd(_p(emb_flat), _p(dphi), T4, B, F, K, method, _p(d_emb), 1, st)
+        lib.recalgo_pnn_weights_bwd(_p(product_w.data), _p(domega), D, F, K, method, _p(product_w.grad), st)
         return None, d_emb, None, None, None, None, None, None
 
 
@@ -1070,8 +1041,7 @@ class _IpnnFeaturesFn(Function):
         lib = _lib_()
         T = lib.recalgo_pnn_feature_count(F, K, 0)
         phi = torch.empty(B, T, device=emb_flat.device, dtype=torch.float32)
-        _lib.check(lib.recalgo_pnn_features_fwd(_p(emb_flat), B, F, K, 0, _p(phi), T, _stream(emb_flat)),
-                   "recalgo_pnn_features_fwd")
+        lib.recalgo_pnn_features_fwd(_p(emb_flat), B, F, K, 0, _p(phi), T, _stream(emb_flat))
         ctx.dims = (F, K)
         ctx.save_for_backward(emb_flat)
         return phi
@@ -1082,8 +1052,8 @@ class _IpnnFeaturesFn(Function):
         F, K = ctx.dims
         dphi = dphi.contiguous()
         d_emb = torch.empty_like(emb_flat)
-        _lib.check(_lib_().recalgo_pnn_features_bwd(_p(emb_flat), _p(dphi), dphi.shape[1], emb_flat.shape[0], F, K, 0, _p(d_emb), 0,
-                                                    _stream(emb_flat)), "recalgo_pnn_features_bwd")
+        _lib_().recalgo_pnn_features_bwd(_p(emb_flat), _p(dphi), dphi.shape[1], emb_flat.shape[0], F, K, 0, _p(d_emb), 0,
+                                         _stream(emb_flat))
         return d_emb, None, None
 
 
@@ -1178,7 +1148,7 @@ class _BiInteractionFn(Function):
         emb = emb.contiguous()
         B = emb.shape[0]
         out = torch.empty(B, K, device=emb.device, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_bi_interaction_fwd(_p(emb), B, F, K, _p(out), _stream(emb)), "recalgo_bi_interaction_fwd")
+        _lib_().recalgo_bi_interaction_fwd(_p(emb), B, F, K, _p(out), _stream(emb))
         ctx.dims = (F, K)
         ctx.save_for_backward(emb)
         return out
@@ -1188,8 +1158,7 @@ class _BiInteractionFn(Function):
         (emb,) = ctx.saved_tensors
         F, K = ctx.dims
         d = torch.empty_like(emb)
-        _lib.check(_lib_().recalgo_bi_interaction_bwd(_p(emb), _p(g.contiguous()), emb.shape[0], F, K, _p(d), _stream(emb)),
-                   "recalgo_bi_interaction_bwd")
+        _lib_().recalgo_bi_interaction_bwd(_p(emb), _p(g.contiguous()), emb.shape[0], F, K, _p(d), _stream(emb))
         return d, None, None
 
 
@@ -1206,8 +1175,7 @@ class _AttentionPoolFn(Function):
         B, P, K = pairs.shape
         out = torch.empty(B, K, device=pairs.device, dtype=torch.float32)
         score = torch.empty(B, P, device=pairs.device, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_attention_pool_fwd(_p(pairs), _p(att), B, P, K, _p(out), _p(score), _stream(pairs)),
-                   "recalgo_attention_pool_fwd")
+        _lib_().recalgo_attention_pool_fwd(_p(pairs), _p(att), B, P, K, _p(out), _p(score), _stream(pairs))
         ctx.save_for_backward(pairs, score)
         return out
 
@@ -1216,8 +1184,7 @@ class _AttentionPoolFn(Function):
         pairs, score = ctx.saved_tensors
         B, P, K = pairs.shape
         dp, da = torch.empty_like(pairs), torch.empty_like(score)
-        _lib.check(_lib_().recalgo_attention_pool_bwd(_p(pairs), _p(score), _p(g.contiguous()), B, P, K, _p(dp), _p(da),
-                                                      _stream(pairs)), "recalgo_attention_pool_bwd")
+        _lib_().recalgo_attention_pool_bwd(_p(pairs), _p(score), _p(g.contiguous()), B, P, K, _p(dp), _p(da), _stream(pairs))
         return dp, da
 
 
@@ -1232,7 +1199,7 @@ class _FfmPairsFn(Function):
         x = x.contiguous()
         B = x.shape[0]
         out = torch.empty(B, 1, device=x.device, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_ffm_pairs_fwd(_p(x), B, F, K, _p(out), _stream(x)), "recalgo_ffm_pairs_fwd")
+        _lib_().recalgo_ffm_pairs_fwd(_p(x), B, F, K, _p(out), _stream(x))
         ctx.dims = (F, K)
         ctx.save_for_backward(x)
         return out
@@ -1242,8 +1209,7 @@ class _FfmPairsFn(Function):
         (x,) = ctx.saved_tensors
         F, K = ctx.dims
         dx = torch.empty_like(x)
-        _lib.check(_lib_().recalgo_ffm_pairs_bwd(_p(x), _p(g.contiguous()), x.shape[0], F, K, _p(dx), _stream(x)),
-                   "recalgo_ffm_pairs_bwd")
+        _lib_().recalgo_ffm_pairs_bwd(_p(x), _p(g.contiguous()), x.shape[0], F, K, _p(dx), _stream(x))
         return dx, None, None
 
 
@@ -1288,9 +1254,9 @@ def dense_fwd(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], re
     if drop is not None:
         drop.check_mask((M, N))
     cd, _keep = _cdrop(drop)
-    _lib.check(_lib_().recalgo_dense_fwd(
+    _lib_().recalgo_dense_fwd(
         _p(x), x.stride(0), _p(w), K, _p(x2), 0 if x2 is None else x2.stride(0), _p(w2), 0 if x2 is None else x2.shape[1],
-        _p(bias), M, N, int(relu), _ACT_NONE, None, None, _p(y), N, _p(bn_partials), cd, _stream(x)), "recalgo_dense_fwd")
+        _p(bias), M, N, int(relu), _ACT_NONE, None, None, _p(y), N, _p(bn_partials), cd, _stream(x))
     return y
 
 
@@ -1308,9 +1274,8 @@ def dense_fwd_act(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor]
         raise ValueError("dense_fwd_act: bn_partials must be a contiguous [bn_partial_rows(M), 2 N] tensor")
     z = torch.empty(M, N, device=x.device, dtype=torch.float32)
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    _lib.check(_lib_().recalgo_dense_fwd(
-        _p(x), x.stride(0), _p(w), K, None, 0, None, 0, _p(bias), M, N, 0, int(kind), _p(alpha), _p(z), _p(y), N,
-        _p(bn_partials), None, _stream(x)), "recalgo_dense_fwd")
+    _lib_().recalgo_dense_fwd(_p(x), x.stride(0), _p(w), K, None, 0, None, 0, _p(bias), M, N, 0, int(kind), _p(alpha), _p(z), _p(y),
+                              N, _p(bn_partials), None, _stream(x))
     return z, y
 
 
@@ -1325,23 +1290,12 @@ def dense_bwd_input(g: torch.Tensor, y_mask: Optional[torch.Tensor], w: torch.Te
     if y_mask is not None and (y_mask.shape != g.shape or y_mask.stride() != g.stride()):
         raise ValueError("dense_bwd_input: y_mask must have g's layout")
     dx = out if out is not None else torch.empty(M, K, device=g.device, dtype=torch.float32)
-    _lib.check(_lib_().recalgo_dense_bwd_input(
-        _p(g), g.stride(0), _p(y_mask), _p(w), M, N, K, _p(c_in), 0 if c_in is None else c_in.stride(0), float(beta),
-        _p(dx), dx.stride(0), int(accumulate), _stream(g)), "recalgo_dense_bwd_input")
+    _lib_().recalgo_dense_bwd_input(_p(g), g.stride(0), _p(y_mask), _p(w), M, N, K, _p(c_in), 0 if c_in is None else c_in.stride(0),
+                                    float(beta), _p(dx), dx.stride(0), int(accumulate), _stream(g))
     return dx
 
 
 _dense_ws = {}
-
-
-class _ColSum(ctypes.Structure):              # include/recalgo.h recalgo_colsum_t
-    _fields_ = [("partials", ctypes.c_void_p), ("out", ctypes.c_void_p), ("rows", ctypes.c_int),
-                ("row_stride", ctypes.c_int64), ("n", ctypes.c_int64)]
-
-
-class _DenseSplit(ctypes.Structure):          # include/recalgo.h recalgo_dense_split_t
-    _fields_ = [("M", ctypes.c_int), ("K", ctypes.c_int), ("N", ctypes.c_int), ("workspace", ctypes.c_void_p),
-                ("dw", ctypes.c_void_p), ("dbias", ctypes.c_void_p)]
 
 
 def dense_bwd_weights(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], dw: torch.Tensor,
@@ -1369,8 +1323,8 @@ def dense_bwd_weights(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.T
     if ws is None:
         ws = _dense_ws[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
     defer = bool(defer and nbytes > 0)
-    _lib.check(lib.recalgo_dense_bwd_weights(_p(x), x.stride(0), _p(g), g.stride(0), _p(y_mask), M, K, N, _p(dw), _p(dbias),
-                                             _p(ws), int(defer), _stream(x)), "recalgo_dense_bwd_weights")
+    lib.recalgo_dense_bwd_weights(_p(x), x.stride(0), _p(g), g.stride(0), _p(y_mask), M, K, N, _p(dw), _p(dbias),
+                                  _p(ws), int(defer), _stream(x))
     if defer:
         _dense_pending.append((M, K, N, ws, dw, dbias))
 
@@ -1428,9 +1382,8 @@ def dense_bwd(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], 
             cargs, cdone = (None, 0, None, None, None, 0, 0, 0, None, None), None
             if crider is not None:
                 cargs, cdone = _cross_rider_args(*crider)
-            _lib.check(lib.recalgo_dense_bwd_rider(*main, _p(rx), 0 if rx is None else rx.stride(0), _p(rg),
-                                                   0 if rg is None else rg.stride(0), rK, rN, _p(rdw), _p(rdb), _p(rws), *cargs,
-                                                   _stream(x)), "recalgo_dense_bwd_rider")
+            lib.recalgo_dense_bwd_rider(*main, _p(rx), 0 if rx is None else rx.stride(0), _p(rg), 0 if rg is None else rg.stride(0),
+                                        rK, rN, _p(rdw), _p(rdb), _p(rws), *cargs, _stream(x))
             _dense_pending.append((M, K, N, ws, dw, dbias))
             if rider is not None:
                 rider_stats["wgrad"] += 1
@@ -1444,7 +1397,7 @@ def dense_bwd(x: torch.Tensor, g: torch.Tensor, y_mask: Optional[torch.Tensor], 
             dense_bwd_weights(rx, rg, None, rdw, rdb, defer=True)          # (not on the vectorised tile paths: a launch of its own)
         if crider is not None:
             _cross_rider = crider                                          # (left to the cross node's own backward)
-    _lib.check(lib.recalgo_dense_bwd(*main, _stream(x)), "recalgo_dense_bwd")
+    lib.recalgo_dense_bwd(*main, _stream(x))
     if defer:
         _dense_pending.append((M, K, N, ws, dw, dbias))
     return dx
@@ -1556,8 +1509,7 @@ def flush_dense_splits(step_dev: Optional[torch.Tensor] = None) -> None:
     nj, ns = len(_dense_pending), len(_colsum_pending)
     _dense_pending.clear()
     _colsum_pending.clear()
-    _lib.check(_lib_().recalgo_dense_bwd_weights_reduce(jobs, nj, sums, ns, _p(step_dev), _stream(dev_t)),
-               "recalgo_dense_bwd_weights_reduce")
+    _lib_().recalgo_dense_bwd_weights_reduce(jobs, nj, sums, ns, _p(step_dev), _stream(dev_t))
 
 
 def mlp_width_supported(C: int) -> bool:
@@ -1570,8 +1522,7 @@ def relu_bwd_bias_(g: torch.Tensor, y: Optional[torch.Tensor], dbias: torch.Tens
     lib = _lib_()
     ws = _workspace(lib.recalgo_relu_bwd_bias_workspace_bytes(rows, C), g.device)
     g2 = None if y is None else torch.empty_like(g)
-    _lib.check(lib.recalgo_relu_bwd_bias(_p(g), _p(y), rows, C, _p(g2), _p(dbias), _p(ws), _stream(g)),
-               "recalgo_relu_bwd_bias")
+    lib.recalgo_relu_bwd_bias(_p(g), _p(y), rows, C, _p(g2), _p(dbias), _p(ws), _stream(g))
     return g if y is None else g2
 
 
@@ -1592,8 +1543,7 @@ def dense1_fwd(parts, w: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Te
     B = parts[0].shape[0]
     widths = (ctypes.c_int * len(parts))(*[int(t.shape[1]) for t in parts])
     out = torch.empty(B, 1, dtype=torch.float32, device=parts[0].device)
-    _lib.check(_lib_().recalgo_dense1_fwd(_ptr_array(parts), widths, len(parts), B, _p(w), _p(bias), _p(out), _stream(out)),
-               "recalgo_dense1_fwd")
+    _lib_().recalgo_dense1_fwd(_ptr_array(parts), widths, len(parts), B, _p(w), _p(bias), _p(out), _stream(out))
     return out
 
 
@@ -1603,8 +1553,8 @@ def dense1_bwd(parts, w: torch.Tensor, g: torch.Tensor, dxs, dw: torch.Tensor, d
     lib = _lib_()
     widths = (ctypes.c_int * len(parts))(*[int(t.shape[1]) for t in parts])
     ws = _workspace(lib.recalgo_dense1_bwd_workspace_bytes(B, C), g.device)
-    _lib.check(lib.recalgo_dense1_bwd(_ptr_array(parts), widths, len(parts), B, _p(w), _p(g), _ptr_array(dxs), _p(dw), _p(dbias),
-                                      _p(ws), _stream(g)), "recalgo_dense1_bwd")
+    lib.recalgo_dense1_bwd(_ptr_array(parts), widths, len(parts), B, _p(w), _p(g), _ptr_array(dxs), _p(dw), _p(dbias),
+                           _p(ws), _stream(g))
 
 
 def batchnorm_train_fwd(x, gamma, beta, moving_mean, moving_var, momentum: float, eps: float, partials=None,
@@ -1620,10 +1570,10 @@ def batchnorm_train_fwd(x, gamma, beta, moving_mean, moving_var, momentum: float
         out_drop.check_mask((rows, C))
     if partials is None:
         partials = _workspace(bn_partial_rows(rows) * 2 * C * 4, x.device)
-        _lib.check(lib.recalgo_batchnorm_moments(_p(x), rows, C, _p(partials), _stream(x)), "recalgo_batchnorm_moments")
+        lib.recalgo_batchnorm_moments(_p(x), rows, C, _p(partials), _stream(x))
     cd, _keep = _cdrop(out_drop)
-    _lib.check(lib.recalgo_batchnorm_apply(_p(x), _p(gamma), _p(beta), _p(partials), 1, rows, C, eps, momentum, _p(moving_mean),
-                                           _p(moving_var), _p(y), _p(mean), _p(rstd), cd, _stream(x)), "recalgo_batchnorm_apply")
+    lib.recalgo_batchnorm_apply(_p(x), _p(gamma), _p(beta), _p(partials), 1, rows, C, eps, momentum, _p(moving_mean),
+                                _p(moving_var), _p(y), _p(mean), _p(rstd), cd, _stream(x))
     return y, mean, rstd
 
 
@@ -1644,9 +1594,9 @@ def batchnorm_train_bwd_act(x, gamma, mean, rstd, g, dgamma, dbeta, kind: int, z
     else:
         ws = _workspace(nbytes, x.device)
     cd, _keep = _cdrop(g_drop)
-    _lib.check(lib.recalgo_batchnorm_train_bwd(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), None if g_drop is not None else _p(sums),
-                                               rows, C, int(kind), _p(z), _p(alpha), _p(dz), _p(dgamma), _p(dbeta),
-                                               None if defer else _p(dalpha), _p(ws), 0, 1.0, cd, _stream(x)), "recalgo_batchnorm_train_bwd")
+    lib.recalgo_batchnorm_train_bwd(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), None if g_drop is not None else _p(sums),
+                                    rows, C, int(kind), _p(z), _p(alpha), _p(dz), _p(dgamma), _p(dbeta),
+                                    None if defer else _p(dalpha), _p(ws), 0, 1.0, cd, _stream(x))
     if defer:
         nb = bn_partial_rows(rows)
         _colsum_pending.append((ws.view(torch.float32), nb * 2 * C, nb, C, C, dalpha))
@@ -1681,15 +1631,14 @@ def batchnorm_sync_fwd(x, gamma, beta, moving_mean, moving_var, momentum: float,
     lib = _lib_()
     nb = int(lib.recalgo_batchnorm_partial_rows(rows))
     local = torch.empty(nb * 2 * C, device=x.device, dtype=torch.float32)
-    _lib.check(lib.recalgo_batchnorm_moments(_p(x), rows, C, _p(local), _stream(x)), "recalgo_batchnorm_moments")
+    lib.recalgo_batchnorm_moments(_p(x), rows, C, _p(local), _stream(x))
     parts = torch.empty(world, nb * 2 * C, device=x.device, dtype=torch.float32)
     all_gather(parts, local)
     y = torch.empty_like(x)
     mean = torch.empty(C, device=x.device, dtype=torch.float32)
     rstd = torch.empty(C, device=x.device, dtype=torch.float32)
-    _lib.check(lib.recalgo_batchnorm_apply(_p(x), _p(gamma), _p(beta), _p(parts), world, rows, C, eps, momentum,
-                                           _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(rstd), None, _stream(x)),
-               "recalgo_batchnorm_apply")
+    lib.recalgo_batchnorm_apply(_p(x), _p(gamma), _p(beta), _p(parts), world, rows, C, eps, momentum,
+                                _p(moving_mean), _p(moving_var), _p(y), _p(mean), _p(rstd), None, _stream(x))
     return y, mean, rstd
 
 
@@ -1699,13 +1648,12 @@ def batchnorm_sync_bwd(x, gamma, mean, rstd, g, dgamma, dbeta, sync) -> torch.Te
     lib = _lib_()
     nb = int(lib.recalgo_batchnorm_partial_rows(rows))
     local = torch.empty(nb * 2 * C, device=x.device, dtype=torch.float32)
-    _lib.check(lib.recalgo_batchnorm_bwd_sums(_p(x), _p(mean), _p(rstd), _p(g), rows, C, _p(local), _stream(x)),
-               "recalgo_batchnorm_bwd_sums")
+    lib.recalgo_batchnorm_bwd_sums(_p(x), _p(mean), _p(rstd), _p(g), rows, C, _p(local), _stream(x))
     parts = torch.empty(world, nb * 2 * C, device=x.device, dtype=torch.float32)
     all_gather(parts, local)
     dx = torch.empty_like(x)
-    _lib.check(lib.recalgo_batchnorm_bwd_apply(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), _p(parts), world, rank, rows, C,
-                                               _p(dx), _p(dgamma), _p(dbeta), 0, _stream(x)), "recalgo_batchnorm_bwd_apply")
+    lib.recalgo_batchnorm_bwd_apply(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), _p(parts), world, rank, rows, C,
+                                    _p(dx), _p(dgamma), _p(dbeta), 0, _stream(x))
     return dx
 
 
@@ -1719,14 +1667,14 @@ def batchnorm_train_bwd(x, gamma, mean, rstd, g, dgamma, dbeta, sums=None, relu_
     lib = _lib_()
     dx = torch.empty_like(x)
     if sums is not None and relu_scale == 1.0 and g_drop is None:
-        _lib.check(lib.recalgo_batchnorm_bwd_apply(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), _p(sums), 1, 0, rows, C, _p(dx),
-                                                   _p(dgamma), _p(dbeta), int(relu_x), _stream(x)), "recalgo_batchnorm_bwd_apply")
+        lib.recalgo_batchnorm_bwd_apply(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), _p(sums), 1, 0, rows, C, _p(dx),
+                                        _p(dgamma), _p(dbeta), int(relu_x), _stream(x))
         return dx
     ws = _workspace(lib.recalgo_batchnorm_bwd_workspace_bytes(rows, C), x.device)
     cd, _keep = _cdrop(g_drop)
-    _lib.check(lib.recalgo_batchnorm_train_bwd(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), None if g_drop is not None else _p(sums),
-                                               rows, C, _ACT_NONE, None, None, _p(dx), _p(dgamma), _p(dbeta), None, _p(ws), int(relu_x),
-                                               float(relu_scale), cd, _stream(x)), "recalgo_batchnorm_train_bwd")
+    lib.recalgo_batchnorm_train_bwd(_p(x), _p(gamma), _p(mean), _p(rstd), _p(g), None if g_drop is not None else _p(sums),
+                                    rows, C, _ACT_NONE, None, None, _p(dx), _p(dgamma), _p(dbeta), None, _p(ws), int(relu_x),
+                                    float(relu_scale), cd, _stream(x))
     return dx
 
 
@@ -1766,9 +1714,8 @@ class _SigmoidCEFn(Function):
         prob = torch.empty_like(lg)
         loss = torch.empty(1, device=lg.device, dtype=torch.float32)
         dlogit = torch.empty_like(lg)
-        _lib.check(_lib_().recalgo_sigmoid_ce_fwd_bwd(
-            _p(lg), _p(lb), B, 1.0 if ctx.seed is None else ctx.seed, _p(prob), _p(loss), _p(dlogit), _stream(lg)),
-            "recalgo_sigmoid_ce_fwd_bwd")
+        _lib_().recalgo_sigmoid_ce_fwd_bwd(
+            _p(lg), _p(lb), B, 1.0 if ctx.seed is None else ctx.seed, _p(prob), _p(loss), _p(dlogit), _stream(lg))
         ctx.save_for_backward(dlogit)
         ctx.shape = logits.shape
         ctx.mark_non_differentiable(prob)
@@ -1827,12 +1774,11 @@ class _LogitLossFn(Function):
         relu_flags = (ctypes.c_int * n_parts)(*[int(sr is not None) for sr in srcs])
         lb = labels.contiguous().view(-1).to(torch.float32)
         wi = (ctypes.c_int * n_parts)(*widths)
-        _lib.check(lib.recalgo_logit_loss_fwd_bwd(
-            _ptr_array(parts), _ptr_array(ws_w), wi, n_parts, None if bias is None else _p(bias.data),
-            _p(addends[0].contiguous().view(-1)) if n_addends > 0 else None,
-            _p(addends[1].contiguous().view(-1)) if n_addends > 1 else None,
-            _p(lb), _p(loss_addend), B, float(_loss_seed), _p(logit), _p(prob), _p(dlogit), _ptr_array(dxs), relu_flags, _p(partials),
-            _stream(logit)), "recalgo_logit_loss_fwd_bwd")
+        lib.recalgo_logit_loss_fwd_bwd(_ptr_array(parts), _ptr_array(ws_w), wi, n_parts, None if bias is None else _p(bias.data),
+                                       _p(addends[0].contiguous().view(-1)) if n_addends > 0 else None,
+                                       _p(addends[1].contiguous().view(-1)) if n_addends > 1 else None, _p(lb), _p(loss_addend), B,
+                                       float(_loss_seed), _p(logit), _p(prob), _p(dlogit), _ptr_array(dxs), relu_flags,
+                                       _p(partials), _stream(logit))
         for sr, dxp in zip(srcs, dxs):
             if sr is not None:
                 sr.premasked = dxp
@@ -1889,10 +1835,10 @@ class _TailDenseHeadFn(Function):
         dz3 = torch.empty(B, N3, device=dev, dtype=torch.float32)
         dh2 = torch.empty_like(h2)
         lb = labels.contiguous().view(-1).to(torch.float32)
-        _lib.check(lib.recalgo_tail_dense_head_fwd_bwd(
+        lib.recalgo_tail_dense_head_fwd_bwd(
             _p(h2), K2, _p(w3.data), _p(b3.data), N3, _p(side), Cs, int(bool(side_first)), _p(w_side) if Cs else None, _p(w_h3),
             None if head_bias is None else _p(head_bias.data), _p(lb), _p(loss_addend), B, float(_loss_seed), _p(logit), _p(prob),
-            _p(dlogit), _p(d_side), _p(dz3), _p(dh2), _p(partials), _stream(logit)), "recalgo_tail_dense_head_fwd_bwd")
+            _p(dlogit), _p(d_side), _p(dz3), _p(dh2), _p(partials), _stream(logit))
         src = getattr(h2, "_recalgo_relu_src", None)
         if src is not None:
             src.premasked = dh2                        # masked with h2 > 0 by the kernel: the producing layer skips its own mask
@@ -1966,8 +1912,7 @@ class _ConcatSumsqFn(Function):
         if ws is None:
             ws = _dense_ws[key] = torch.zeros(int(lib.recalgo_concat_sumsq_workspace_bytes(B)), dtype=torch.uint8, device=dev)
         wi = (ctypes.c_int * len(parts))(*widths)
-        _lib.check(lib.recalgo_concat_sumsq(_ptr_array(parts), wi, len(parts), B, _p(out), float(scale), _p(val), _p(ws),
-                                            _stream(out)), "recalgo_concat_sumsq")
+        lib.recalgo_concat_sumsq(_ptr_array(parts), wi, len(parts), B, _p(out), float(scale), _p(val), _p(ws), _stream(out))
         ctx.widths = widths
         ctx.mark_non_differentiable(val)
         ctx.set_materialize_grads(False)      # (else autograd fills a zero "gradient" for val: one launch per step)
@@ -2021,7 +1966,7 @@ def logit_loss(store, labels: torch.Tensor, heads, bias, parts, addends, loss_ad
 # =============================================================================================
 # MMoE (csrc/mmoe.hip): softmax gates + expert mix, the multi-task loss tail
 # =============================================================================================
-GATE_MIX_MAX = 16                            # include/recalgo.h RECALGO_GATE_MIX_MAX
+GATE_MIX_MAX = _C["RECALGO_GATE_MIX_MAX"]
 
 
 def _colsum_now(jobs, device_tensor: torch.Tensor) -> None:
@@ -2029,8 +1974,7 @@ def _colsum_now(jobs, device_tensor: torch.Tensor) -> None:
     sums = (_ColSum * len(jobs))()
     for i, (part, off, rows, stride, n, out) in enumerate(jobs):
         sums[i] = _ColSum(part.data_ptr() + 4 * off, out.data_ptr(), rows, stride, n)
-    _lib.check(_lib_().recalgo_dense_bwd_weights_reduce((_DenseSplit * 1)(), 0, sums, len(jobs), None, _stream(device_tensor)),
-               "recalgo_dense_bwd_weights_reduce")
+    _lib_().recalgo_dense_bwd_weights_reduce((_DenseSplit * 1)(), 0, sums, len(jobs), None, _stream(device_tensor))
 
 
 class GateMixSpec:
@@ -2059,8 +2003,8 @@ class _GateMixFn(Function):
         E, H = len(experts), experts[0].shape[1]
         outs = [torch.empty(B, H, device=x.device, dtype=torch.float32) for _ in range(G)]
         p = torch.empty(B, spec.n_total, device=x.device, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_gate_mix_fwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts),
-                                                B, In, E, G, H, _ptr_array(outs), _p(p), _stream(x)), "recalgo_gate_mix_fwd")
+        _lib_().recalgo_gate_mix_fwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts),
+                                     B, In, E, G, H, _ptr_array(outs), _p(p), _stream(x))
         ctx.spec, ctx.ws, ctx.E = spec, ws, E
         ctx.save_for_backward(x, p, *experts)
         ctx.mark_non_differentiable(p)
@@ -2082,9 +2026,8 @@ class _GateMixFn(Function):
         rows = int(lib.recalgo_gate_mix_partial_rows(B))
         partials = torch.empty(rows, In * spec.n_total, device=x.device, dtype=torch.float32)
         relu = spec.relu_sources is not None
-        _lib.check(lib.recalgo_gate_mix_bwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts), _p(p),
-                                            _ptr_array(gs), B, In, E, G, H, int(relu), _ptr_array(dex), _p(dx), In, _p(partials),
-                                            _stream(x)), "recalgo_gate_mix_bwd")
+        lib.recalgo_gate_mix_bwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts), _p(p),
+                                 _ptr_array(gs), B, In, E, G, H, int(relu), _ptr_array(dex), _p(dx), In, _p(partials), _stream(x))
         if relu:
             for src, d in zip(spec.relu_sources, dex):
                 src.premasked = d            # (nn.ReluSource: the expert layers' backward then runs without mask loads)
@@ -2167,9 +2110,8 @@ class _MultiTaskCEFn(Function):
         losses = torch.empty(T, device=dev, dtype=torch.float32)
         total = torch.empty(1, device=dev, dtype=torch.float32)
         dlogit = torch.empty(T, B, device=dev, dtype=torch.float32)
-        _lib.check(_lib_().recalgo_multitask_sigmoid_ce_fwd_bwd(
-            _ptr_array(lgs), _ptr_array(lbs), T, B, 1.0 if ctx.seed is None else ctx.seed, _p(prob), _p(losses), _p(total),
-            _p(dlogit), _stream(lgs[0])), "recalgo_multitask_sigmoid_ce_fwd_bwd")
+        _lib_().recalgo_multitask_sigmoid_ce_fwd_bwd(_ptr_array(lgs), _ptr_array(lbs), T, B, 1.0 if ctx.seed is None else ctx.seed,
+                                                     _p(prob), _p(losses), _p(total), _p(dlogit), _stream(lgs[0]))
         ctx.save_for_backward(dlogit)
         ctx.shapes = [t.shape for t in logits]
         ctx.mark_non_differentiable(prob)
@@ -2214,8 +2156,7 @@ class _ActFn(Function):
         x = x.contiguous()
         rows, C = x.shape
         y = torch.empty_like(x)
-        _lib.check(_lib_().recalgo_activation_fwd(_p(x), _p(alpha.data), rows, C, kind, _p(y), _stream(x)),
-                   "recalgo_activation_fwd")
+        _lib_().recalgo_activation_fwd(_p(x), _p(alpha.data), rows, C, kind, _p(y), _stream(x))
         ctx.alpha, ctx.kind = alpha, kind
         ctx.in_step = _loss_seed is not None      # built inside Estimator.train_step: its optimizer runs the deferred sums
         ctx.save_for_backward(x)
@@ -2235,15 +2176,13 @@ class _ActFn(Function):
             ws = _dense_ws.get(key)
             if ws is None:
                 ws = _dense_ws[key] = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
-            _lib.check(lib.recalgo_activation_bwd(_p(x), _p(ctx.alpha.data), _p(gy), rows, C, ctx.kind, _p(dx), None, _p(ws),
-                                                  _stream(x)), "recalgo_activation_bwd")
+            lib.recalgo_activation_bwd(_p(x), _p(ctx.alpha.data), _p(gy), rows, C, ctx.kind, _p(dx), None, _p(ws), _stream(x))
             _colsum_pending.append((ws.view(torch.float32), 0, int(lib.recalgo_activation_bwd_partial_rows(rows, C)), C, C,
                                     ctx.alpha.grad))
             return None, dx, None, None
         ws = _workspace(nbytes, x.device)
-        _lib.check(lib.recalgo_activation_bwd(_p(x), _p(ctx.alpha.data), _p(gy), rows, C, ctx.kind, _p(dx),
-                                              _p(ctx.alpha.grad), _p(ws), _stream(x)),
-                   "recalgo_activation_bwd")
+        lib.recalgo_activation_bwd(_p(x), _p(ctx.alpha.data), _p(gy), rows, C, ctx.kind, _p(dx),
+                                   _p(ctx.alpha.grad), _p(ws), _stream(x))
         return None, dx, None, None
 
 
@@ -2274,11 +2213,6 @@ class DropSpec:
             raise ValueError("dropout: the explicit keep mask must be a contiguous fp32 tensor of the dropped tensor's shape")
 
 
-class _CDrop(ctypes.Structure):              # include/recalgo.h recalgo_dropout_t
-    _fields_ = [("rate", ctypes.c_double), ("keep_mask", ctypes.c_void_p), ("seed", ctypes.c_uint), ("call", ctypes.c_uint),
-                ("step", ctypes.c_void_p)]
-
-
 def _cdrop(d: Optional["DropSpec"]):
     """-> (byref argument or None, keep-alive)"""
     if d is None:
@@ -2289,8 +2223,7 @@ def _cdrop(d: Optional["DropSpec"]):
 
 def _dropout_launch(x: torch.Tensor, d: DropSpec) -> torch.Tensor:
     y = torch.empty_like(x)
-    _lib.check(_lib_().recalgo_dropout_fwd(_p(x), x.numel(), d.rate, _p(d.mask), d.seed, d.call, _p(d.step), _p(y), _stream(x)),
-               "recalgo_dropout_fwd")
+    _lib_().recalgo_dropout_fwd(_p(x), x.numel(), d.rate, _p(d.mask), d.seed, d.call, _p(d.step), _p(y), _stream(x))
     return y
 
 
@@ -2317,8 +2250,7 @@ def dropout(x: torch.Tensor, d: DropSpec) -> torch.Tensor:
 def dropout_keep_mask(shape, d: DropSpec, device) -> torch.Tensor:
     """The keep mask (1 / 0) the hash of `d` stands for at the CURRENT value of the step counter."""
     out = torch.empty(*shape, dtype=torch.float32, device=device)
-    _lib.check(_lib_().recalgo_dropout_keep_mask(out.numel(), d.rate, d.seed, d.call, _p(d.step), _p(out), _stream(out)),
-               "recalgo_dropout_keep_mask")
+    _lib_().recalgo_dropout_keep_mask(out.numel(), d.rate, d.seed, d.call, _p(d.step), _p(out), _stream(out))
     return out
 
 
@@ -2338,9 +2270,8 @@ def adam_tf1_(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor
     lr_, b1_, b2_ = f32(lr), f32(beta1), f32(beta2)
     lr_t = 0.0 if lr_t_dev is not None else \
         lr_ * math.sqrt(1.0 - b2_ ** step) / (1.0 - b1_ ** step)
-    _lib.check(_lib_().recalgo_adam_tf1_dense(
-        _p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, _p(lr_t_dev), beta1, beta2, eps,
-        int(zero_grad), _stream(p)), "recalgo_adam_tf1_dense")
+    _lib_().recalgo_adam_tf1_dense(_p(p), _p(g), _p(m), _p(v), p.numel(), lr_t, _p(lr_t_dev), beta1, beta2, eps, int(zero_grad),
+                                   _stream(p))
 
 
 def adam_tf1_rows_(weight: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor,
@@ -2349,9 +2280,8 @@ def adam_tf1_rows_(weight: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v:
     """TF1 dense Adam over an embedding arena [rows, K] that skips rows no batch has touched yet
     (exactly the identity for them); row_live [rows] uint8 is maintained by the kernel."""
     rows, K = weight.shape
-    _lib.check(_lib_().recalgo_adam_tf1_rows(
-        _p(weight), _p(grad), _p(m), _p(v), _p(row_live), rows, K, 0.0, _p(lr_t_dev), beta1, beta2, eps,
-        int(zero_grad), _stream(weight)), "recalgo_adam_tf1_rows")
+    _lib_().recalgo_adam_tf1_rows(_p(weight), _p(grad), _p(m), _p(v), _p(row_live), rows, K, 0.0, _p(lr_t_dev), beta1, beta2, eps,
+                                  int(zero_grad), _stream(weight))
 
 
 def adam_tf1_list_(arena, lr_t_dev: torch.Tensor, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
@@ -2360,22 +2290,14 @@ def adam_tf1_list_(arena, lr_t_dev: torch.Tensor, beta1: float = 0.9, beta2: flo
     the dense pass)."""
     _, lst, cnt = arena.live_state()
     rows, K = arena.weight.shape
-    _lib.check(_lib_().recalgo_adam_tf1_list(
-        _p(arena.weight), _p(arena.grad), _p(arena.m), _p(arena.v), _p(lst), _p(cnt), rows, K, 0.0, _p(lr_t_dev),
-        beta1, beta2, eps, int(zero_grad), _stream(arena.weight)), "recalgo_adam_tf1_list")
+    _lib_().recalgo_adam_tf1_list(_p(arena.weight), _p(arena.grad), _p(arena.m), _p(arena.v), _p(lst), _p(cnt), rows, K, 0.0,
+                                  _p(lr_t_dev), beta1, beta2, eps, int(zero_grad), _stream(arena.weight))
 
 
 def adam_tf1_advance_(step_dev: torch.Tensor, lr_t_dev: torch.Tensor, lr: float,
                       beta1: float = 0.9, beta2: float = 0.999) -> None:
     """step_dev (int64[1]) += 1; lr_t_dev (float[1]) = lr*sqrt(1-b2^t)/(1-b1^t), on device."""
-    _lib.check(_lib_().recalgo_adam_tf1_advance(_p(step_dev), lr, beta1, beta2, _p(lr_t_dev),
-                                                 _stream(step_dev)), "recalgo_adam_tf1_advance")
-
-
-class _AdamArena(ctypes.Structure):          # include/recalgo.h recalgo_adam_arena_t
-    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
-                ("live_list", ctypes.c_void_p), ("live_count", ctypes.c_void_p), ("max_rows", ctypes.c_int64),
-                ("K", ctypes.c_int), ("lazy", ctypes.c_int)]
+    _lib_().recalgo_adam_tf1_advance(_p(step_dev), lr, beta1, beta2, _p(lr_t_dev), _stream(step_dev))
 
 
 def adam_tf1_step_(flat, flat_grad, flat_m, flat_v, arenas, step_dev: torch.Tensor, ticket_dev: Optional[torch.Tensor],
@@ -2401,7 +2323,6 @@ def adam_tf1_step_(flat, flat_grad, flat_m, flat_v, arenas, step_dev: torch.Tens
         scans = None
         if plan_scans:
             scans = (type(plan_scans[0]) * len(plan_scans))(*plan_scans)
-        _lib.check(lib.recalgo_adam_tf1_step_plans(_p(flat) if n else None, _p(flat_grad) if n else None, _p(flat_m) if n else None,
-                                                   _p(flat_v) if n else None, n, arr, len(chunk), _p(step_dev), _p(ticket_dev),
-                                                   int(advance), lr, beta1, beta2, eps, int(zero_grad), scans, len(plan_scans),
-                                                   _stream(step_dev)), "recalgo_adam_tf1_step")
+        lib.recalgo_adam_tf1_step_plans(_p(flat) if n else None, _p(flat_grad) if n else None, _p(flat_m) if n else None,
+                                        _p(flat_v) if n else None, n, arr, len(chunk), _p(step_dev), _p(ticket_dev), int(advance),
+                                        lr, beta1, beta2, eps, int(zero_grad), scans, len(plan_scans), _stream(step_dev))

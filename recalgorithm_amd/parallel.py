@@ -178,8 +178,7 @@ def hip_exchange_plan(rows: torch.Tensor, world: int, cap: int, overflow: torch.
     counters = torch.empty(world, dtype=torch.int32, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     p = lambda t: ctypes.c_void_p(t.data_ptr())
-    _lib.check(lib.recalgo_exchange_plan(p(rows.contiguous()), M, world, cap, p(send_local), None, p(req_slot), p(counters),
-                                         p(overflow), st), "recalgo_exchange_plan")
+    lib.recalgo_exchange_plan(p(rows.contiguous()), M, world, cap, p(send_local), None, p(req_slot), p(counters), p(overflow), st)
     return send_local, req_slot
 
 
@@ -195,7 +194,7 @@ def hip_dedup_rows(rows: torch.Tensor):
         ws = torch.empty(int(lib.recalgo_dedup_rows_workspace_bytes(M)), dtype=torch.uint8, device=dev)
         st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
-        _lib.check(lib.recalgo_dedup_rows(p(rows), M, p(unique_rows), p(rep), p(ws), st), "recalgo_dedup_rows")
+        lib.recalgo_dedup_rows(p(rows), M, p(unique_rows), p(rep), p(ws), st)
     return unique_rows, rep
 
 
@@ -211,8 +210,8 @@ def hip_local_gather(shard_weight: torch.Tensor, local_rows: torch.Tensor, defer
         zero = _zero(shard_weight.device)
         st = ctypes.c_void_p(torch.cuda.current_stream(shard_weight.device).cuda_stream)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
-        _lib.check(lib.recalgo_embedding_gather_fwd_deferred(p(local_rows), p(shard_weight), p(zero), n, 1, K, p(out), K, 0,
-                                                             deferred, step_dev, 0, st), "recalgo_embedding_gather_fwd")
+        lib.recalgo_embedding_gather_fwd_deferred(p(local_rows), p(shard_weight), p(zero), n, 1, K, p(out), K, 0,
+                                                  deferred, step_dev, 0, st)
     return out
 
 
@@ -229,8 +228,7 @@ def hip_local_scatter_add(arena: EmbeddingArena, local_rows: torch.Tensor, g: to
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         g = g.contiguous()
         # the scatter marks the rows it flushes in the shard's live-row list
-        _lib.check(lib.recalgo_embedding_gather_bwd(p(local_rows), p(g), p(zero), n, 1, K, K, 0, p(shard_grad),
-                                                    ops._live(arena), st), "recalgo_embedding_gather_bwd")
+        lib.recalgo_embedding_gather_bwd(p(local_rows), p(g), p(zero), n, 1, K, K, 0, p(shard_grad), ops._live(arena), st)
 
 
 class Sharding:

@@ -29,10 +29,16 @@ import torch
 
 from . import _lib
 
-MODE_GRAD, MODE_ADAM, MODE_LAZY_ADAM = 0, 1, 2
-PREPARE_COUNT, PREPARE_SWEEP, PREPARE_CATCHUP = 1, 2, 4          # include/recalgo.h RECALGO_PREPARE_*
-MAX_SOURCES = 16
-LR_RING = 1024
+_C = _lib.CONSTANTS                          # the RECALGO_* #defines of include/recalgo.h
+MODE_GRAD, MODE_ADAM, MODE_LAZY_ADAM = _C["RECALGO_SCATTER_GRAD"], _C["RECALGO_SCATTER_ADAM"], _C["RECALGO_SCATTER_LAZY_ADAM"]
+MODE_PRESCANNED = _C["RECALGO_SCATTER_PRESCANNED"]
+PREPARE_COUNT, PREPARE_SWEEP, PREPARE_CATCHUP = _C["RECALGO_PREPARE_COUNT"], _C["RECALGO_PREPARE_SWEEP"], _C["RECALGO_PREPARE_CATCHUP"]
+MAX_SOURCES = _C["RECALGO_SCATTER_MAX_SOURCES"]
+LR_RING = _C["RECALGO_LR_RING"]
+# the structs of include/recalgo.h (ctypes classes derived from the header, fields in its order)
+_CSource, _CCompanion = _lib.STRUCTS["recalgo_scatter_source_t"], _lib.STRUCTS["recalgo_scatter_companion_t"]
+_CPlanScan, _CDeferred = _lib.STRUCTS["recalgo_plan_scan_t"], _lib.STRUCTS["recalgo_deferred_adam_t"]
+_CLookupJob = _lib.STRUCTS["recalgo_lookup_job_t"]
 
 
 # Test hooks (module attributes, not environment knobs): tests/test_gpu_sparse.py compares the owner-computes path with the
@@ -56,28 +62,6 @@ def sweep_period() -> int:
     if not 1 <= p <= LR_RING - 8:
         raise ValueError(f"RECALGO_ADAM_SWEEP_PERIOD={p}: expected 1 .. {LR_RING - 8}")
     return p
-
-
-class _CSource(ctypes.Structure):            # include/recalgo.h recalgo_scatter_source_t
-    _fields_ = [("ids", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("row_base", ctypes.c_void_p), ("base", ctypes.c_int64),
-                ("n_ex", ctypes.c_int), ("F", ctypes.c_int), ("g", ctypes.c_void_p), ("g_stride", ctypes.c_int64),
-                ("g_col", ctypes.c_int), ("g_fmul", ctypes.c_int),
-                ("fm_scale", ctypes.c_void_p), ("fm_sum", ctypes.c_void_p), ("fm_emb", ctypes.c_void_p)]
-
-
-class _CCompanion(ctypes.Structure):         # include/recalgo.h recalgo_scatter_companion_t
-    _fields_ = [("sources", ctypes.c_void_p), ("w", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
-                ("grad", ctypes.c_void_p), ("deferred", ctypes.c_void_p), ("rows", ctypes.c_int64)]
-
-
-class _CPlanScan(ctypes.Structure):          # include/recalgo.h recalgo_plan_scan_t
-    _fields_ = [("total", ctypes.c_void_p), ("offs", ctypes.c_void_p), ("sched", ctypes.c_void_p),
-                ("counter_shift", ctypes.c_uint32), ("nb_log2", ctypes.c_uint32)]
-
-
-class _CDeferred(ctypes.Structure):          # include/recalgo.h recalgo_deferred_adam_t
-    _fields_ = [("w", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("last_step", ctypes.c_void_p),
-                ("lr_ring", ctypes.c_void_p), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float)]
 
 
 class Source:
@@ -312,11 +296,10 @@ def begin_lookup(arena, store, ids: torch.Tensor, offsets: Optional[torch.Tensor
         src.deferred = True
         _batch["arenas"].setdefault(id(arena), (arena, plan, []))[2].append((src, cs, first, flags, d, step))
     elif flags:
-        _lib.check(lib.recalgo_scatter_prepare(ctypes.byref(cs), arena.K, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity, plan.nb_log2,
-                                               first, flags, None if d is None else ctypes.byref(d),
-                                               None if d1 is None else ctypes.byref(d1), arena.weight.shape[0], c_rows, sweep_period(),
-                                               None if step is None else ctypes.c_void_p(step.data_ptr()), 0, _stream(arena.weight)),
-                   "recalgo_scatter_prepare")
+        lib.recalgo_scatter_prepare(ctypes.byref(cs), arena.K, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity, plan.nb_log2,
+                                    first, flags, None if d is None else ctypes.byref(d),
+                                    None if d1 is None else ctypes.byref(d1), arena.weight.shape[0], c_rows, sweep_period(),
+                                    None if step is None else ctypes.c_void_p(step.data_ptr()), 0, _stream(arena.weight))
     plan.sources.append(src)
     plan.counted = plan.counted[:2] + (plan.counted[2] + (id(src),),)
     return src
@@ -357,12 +340,6 @@ def batching() -> bool:
     return _batch is not None
 
 
-class _CLookupJob(ctypes.Structure):         # include/recalgo.h recalgo_lookup_job_t
-    _fields_ = [("kind", ctypes.c_int), ("ids", ctypes.c_void_p), ("aux", ctypes.c_void_p), ("table", ctypes.c_void_p),
-                ("B", ctypes.c_int), ("F_or_T", ctypes.c_int), ("K", ctypes.c_int), ("out", ctypes.c_void_p),
-                ("out_stride", ctypes.c_int), ("out_col", ctypes.c_int), ("seq_len", ctypes.c_void_p)]
-
-
 def defer_launch(fn, job=None) -> None:
     """the forward kernel of a lookup whose prepare work is pending: enqueued by flush_batch() / the end of the block.
     job = (kind, ids, aux, table, B, F_or_T, K, out, out_stride, out_col, seq_len | None): a plain lookup that may share ONE launch
@@ -392,16 +369,15 @@ def _flush_batch(b) -> None:
             stp = None if step is None else ctypes.c_void_p(step.data_ptr())
             if len(chunk) == 1:
                 _, cs, first, _, _, _ = chunk[0]
-                _lib.check(lib.recalgo_scatter_prepare(ctypes.byref(cs), arena.K, ws, plan.capacity, plan.nb_log2, first, flags,
-                                                       None if d is None else ctypes.byref(d), None, arena.weight.shape[0], 0,
-                                                       sweep_period(), stp, 0, _stream(arena.weight)), "recalgo_scatter_prepare")
+                lib.recalgo_scatter_prepare(ctypes.byref(cs), arena.K, ws, plan.capacity, plan.nb_log2, first, flags,
+                                            None if d is None else ctypes.byref(d), None, arena.weight.shape[0], 0,
+                                            sweep_period(), stp, 0, _stream(arena.weight))
             else:
                 arr = (_CSource * len(chunk))(*[e[1] for e in chunk])
                 firsts = (ctypes.c_int64 * len(chunk))(*[e[2] for e in chunk])
-                _lib.check(lib.recalgo_scatter_prepare_multi(arr, len(chunk), firsts, arena.K, ws, plan.capacity, plan.nb_log2, flags,
-                                                             None if d is None else ctypes.byref(d), arena.weight.shape[0],
-                                                             sweep_period(), stp, 0, _stream(arena.weight)),
-                           "recalgo_scatter_prepare_multi")
+                lib.recalgo_scatter_prepare_multi(arr, len(chunk), firsts, arena.K, ws, plan.capacity, plan.nb_log2, flags,
+                                                  None if d is None else ctypes.byref(d), arena.weight.shape[0],
+                                                  sweep_period(), stp, 0, _stream(arena.weight))
                 prepare_stats["merged"] += len(chunk) - 1
         # what the workspace holds now: EVERY entry of the block (also one registered before a later lookup re-sized — and
         # cleared — the workspace, whose id the book-keeping dropped then) beside the sources counted by launches of their own
@@ -419,7 +395,7 @@ def _flush_batch(b) -> None:
         ptr = lambda t: None if t is None else t.data_ptr()
         arr = (_CLookupJob * len(chunk))(*[_CLookupJob(j[0], ptr(j[1]), ptr(j[2]), ptr(j[3]), j[4], j[5], j[6], ptr(j[7]), j[8], j[9],
                                                         ptr(j[10])) for _, j in chunk])
-        _lib.check(lib.recalgo_lookup_multi_fwd(arr, len(chunk), _stream(chunk[0][1][7])), "recalgo_lookup_multi_fwd")
+        lib.recalgo_lookup_multi_fwd(arr, len(chunk), _stream(chunk[0][1][7]))
         prepare_stats["merged_lookups"] += len(chunk) - 1
 
 
@@ -530,9 +506,6 @@ def _merge_dense(sources: List[Source], K: int) -> List[Source]:
     return rest + [merged]
 
 
-MODE_PRESCANNED = 0x100        # include/recalgo.h RECALGO_SCATTER_PRESCANNED
-
-
 def plan_scan_record(arena, lazy: bool):
     """The recalgo_plan_scan_t of the arena's plan, for the optimizer launch that runs between the step's last count and this
     arena's `apply` (ops.adam_tf1_step_(plan_scans=)) — or None when `apply` will not find the totals of exactly its sources in
@@ -572,9 +545,8 @@ def _run(plan: ArenaPlan, sources: List[Source], mode: int, step_dev, step_offse
         first = 0
         for s in srcs:
             cs = s.c_struct(a.K)
-            _lib.check(lib.recalgo_scatter_prepare(ctypes.byref(cs), a.K, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity,
-                                                   plan.nb_log2, first, PREPARE_COUNT, None, None, 0, 0, 1, None, 0, _stream(a.weight)),
-                       "recalgo_scatter_prepare")
+            lib.recalgo_scatter_prepare(ctypes.byref(cs), a.K, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity,
+                                        plan.nb_log2, first, PREPARE_COUNT, None, None, 0, 0, 1, None, 0, _stream(a.weight))
             first += s.slots
     if not srcs:                               # (the sweep and the lr ring still need the launch)
         dummy = Source(a.weight, None, None, 0, 0, 1)
@@ -588,11 +560,10 @@ def _run(plan: ArenaPlan, sources: List[Source], mode: int, step_dev, step_offse
         dc0 = None
         if comp_arena is not None and plan_of(comp_arena).last_step is not None and not plan_of(comp_arena).swept:
             dc0 = plan_of(comp_arena)._deferred_struct()
-        _lib.check(lib.recalgo_scatter_prepare(None, a.K, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity, plan.nb_log2, 0,
-                                               PREPARE_SWEEP, ctypes.byref(d), None if dc0 is None else ctypes.byref(dc0),
-                                               a.weight.shape[0], comp_arena.weight.shape[0] if dc0 is not None else 0, sweep_period(),
-                                               ctypes.c_void_p(step_dev.data_ptr()), step_offset - 1, _stream(a.weight)),
-                   "recalgo_scatter_prepare (sweep)")
+        lib.recalgo_scatter_prepare(None, a.K, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity, plan.nb_log2, 0,
+                                    PREPARE_SWEEP, ctypes.byref(d), None if dc0 is None else ctypes.byref(dc0),
+                                    a.weight.shape[0], comp_arena.weight.shape[0] if dc0 is not None else 0, sweep_period(),
+                                    ctypes.c_void_p(step_dev.data_ptr()), step_offset - 1, _stream(a.weight))
         if dc0 is not None:
             plan_of(comp_arena).swept = True
     if mode == MODE_ADAM and comp_arena is not None:
@@ -602,10 +573,9 @@ def _run(plan: ArenaPlan, sources: List[Source], mode: int, step_dev, step_offse
         cpl = plan_of(comp_arena)
         if cpl.last_step is not None and not cpl.swept:
             dc1 = cpl._deferred_struct()
-            _lib.check(lib.recalgo_scatter_prepare(None, 1, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity, plan.nb_log2, 0,
-                                                   PREPARE_SWEEP, ctypes.byref(dc1), None, comp_arena.weight.shape[0], 0,
-                                                   sweep_period(), ctypes.c_void_p(step_dev.data_ptr()), step_offset - 1,
-                                                   _stream(a.weight)), "recalgo_scatter_prepare (companion sweep)")
+            lib.recalgo_scatter_prepare(None, 1, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity, plan.nb_log2, 0, PREPARE_SWEEP,
+                                        ctypes.byref(dc1), None, comp_arena.weight.shape[0], 0, sweep_period(),
+                                        ctypes.c_void_p(step_dev.data_ptr()), step_offset - 1, _stream(a.weight))
             cpl.swept = True
     if mode != MODE_GRAD:
         plan.swept = False                     # (the next step's first lookup sweeps again)
@@ -635,12 +605,10 @@ def _run(plan: ArenaPlan, sources: List[Source], mode: int, step_dev, step_offse
         comp = _CCompanion(ctypes.addressof(carr), ptr(c.weight), ptr(c.m), ptr(c.v), ptr(cgrad),
                            None if dc is None else ctypes.addressof(dc), c.weight.shape[0])
     grad = a._grad if (mode == MODE_GRAD or plan.grad_materialized) else None
-    _lib.check(lib.recalgo_scatter_apply(arr, len(srcs), None if comp is None else ctypes.byref(comp), a.K, p(plan.ws), plan.capacity,
-                                         plan.nb_log2, mode | (MODE_PRESCANNED if prescanned is not None else 0), p(a.weight), p(a.m),
-                                         p(a.v), p(grad),
-                                         None if d is None else ctypes.byref(d), a.weight.shape[0],
-                                         live, p(step_dev), step_offset, lr, b1, b2, eps, _stream(a.weight)),
-               "recalgo_scatter_apply")
+    lib.recalgo_scatter_apply(arr, len(srcs), None if comp is None else ctypes.byref(comp), a.K, p(plan.ws), plan.capacity,
+                              plan.nb_log2, mode | (MODE_PRESCANNED if prescanned is not None else 0), p(a.weight), p(a.m), p(a.v),
+                              p(grad), None if d is None else ctypes.byref(d), a.weight.shape[0], live, p(step_dev), step_offset,
+                              lr, b1, b2, eps, _stream(a.weight))
     if comp_arena is not None and mode != MODE_GRAD:
         cp.companions = []
         cp.grad_materialized = False
@@ -743,9 +711,8 @@ def sync(arena, step_dev: Optional[torch.Tensor], step_offset: int = 0) -> None:
     if plan is None or plan.last_step is None or step_dev is None:
         return
     d = plan._deferred_struct()
-    _lib.check(_lib.load().recalgo_adam_deferred_sweep(ctypes.byref(d), arena.K, 0, arena.weight.shape[0],
-                                                      ctypes.c_void_p(step_dev.data_ptr()), step_offset, _stream(arena.weight)),
-               "recalgo_adam_deferred_sweep")
+    _lib.load().recalgo_adam_deferred_sweep(ctypes.byref(d), arena.K, 0, arena.weight.shape[0],
+                                           ctypes.c_void_p(step_dev.data_ptr()), step_offset, _stream(arena.weight))
 
 
 def sync_arena(arena) -> None:

@@ -461,8 +461,7 @@ class EmbeddingArena:
                                          device=self.weight.device)
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         st = ctypes.c_void_p(torch.cuda.current_stream(self.weight.device).cuda_stream)
-        _lib.check(lib.recalgo_order_live_list(p(self.live), rows, p(self.live_list), p(self.live_count), p(self._order_ws), st),
-                   "recalgo_order_live_list")
+        lib.recalgo_order_live_list(p(self.live), rows, p(self.live_list), p(self.live_count), p(self._order_ws), st)
 
     def force_all_live(self) -> None:
         """Mark every row live: the optimizer then walks the whole arena, i.e. TF1's dense Adam at its full cost (what a

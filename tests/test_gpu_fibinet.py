@@ -127,6 +127,10 @@ def test_bilinear_rejects_bad_arguments(dev):
     x = torch.zeros(2, 5, 8, device=dev)
     w = torch.zeros(8, 8, device=dev)
     out = torch.zeros(2, 6, 8, device=dev)
-    assert lib.recalgo_bilinear_fwd(_p(x), _p(w), None, None, 2, 5, 8, 3, _p(out), 8, 0, _st()) != 0    # bad type
-    assert lib.recalgo_bilinear_fwd(_p(x), _p(w), None, None, 2, 5, 10, 0, _p(out), 8, 0, _st()) != 0   # bad K
-    assert lib.recalgo_senet_fwd(_p(x), _p(w), _p(w), 2, 5, 8, 8, _p(x), None, _st()) != 0              # Rd !< K
+    # a non-zero hipError_t, which the binding raises
+    with pytest.raises(_lib.RecalgoError, match="recalgo_bilinear_fwd failed with hipError_t=[1-9]"):
+        lib.recalgo_bilinear_fwd(_p(x), _p(w), None, None, 2, 5, 8, 3, _p(out), 8, 0, _st())            # bad type
+    with pytest.raises(_lib.RecalgoError, match="recalgo_bilinear_fwd failed with hipError_t=[1-9]"):
+        lib.recalgo_bilinear_fwd(_p(x), _p(w), None, None, 2, 5, 10, 0, _p(out), 8, 0, _st())           # bad K
+    with pytest.raises(_lib.RecalgoError, match="recalgo_senet_fwd failed with hipError_t=[1-9]"):
+        lib.recalgo_senet_fwd(_p(x), _p(w), _p(w), 2, 5, 8, 8, _p(x), None, _st())                      # Rd !< K

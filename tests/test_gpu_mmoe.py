@@ -209,15 +209,15 @@ def test_gate_mix_limits(dev):
     with pytest.raises(NotImplementedError):
         ops.gate_mix(torch.zeros(8, 400, device=dev), [torch.zeros(400, 12, device=dev)],
                      [torch.zeros(8, 8, device=dev) for _ in range(12)])                                           # LDS budget
-    # the entry point checks again: an error code, never a launch
+    # the entry point checks again: an error code (raised by the binding), never a launch
     lib = _lib.load()
     import ctypes
     n_sel, sel = (ctypes.c_int * 1)(3), (ctypes.c_int * 3)(0, 1, 2)
     e = [torch.zeros(8, 6, device=dev) for _ in range(3)]
     w, o, p = torch.zeros(82, 3, device=dev), torch.zeros(8, 6, device=dev), torch.zeros(8, 3, device=dev)
-    rc = lib.recalgo_gate_mix_fwd(ops._p(x), 82, ops._ptr_array([w]), n_sel, sel, ops._ptr_array(e), 8, 82, 3, 1, 6,
-                                  ops._ptr_array([o]), ops._p(p), ops._stream(x))
-    assert rc != 0
+    with pytest.raises(_lib.RecalgoError, match="recalgo_gate_mix_fwd failed with hipError_t=[1-9]"):
+        lib.recalgo_gate_mix_fwd(ops._p(x), 82, ops._ptr_array([w]), n_sel, sel, ops._ptr_array(e), 8, 82, 3, 1, 6,
+                                 ops._ptr_array([o]), ops._p(p), ops._stream(x))
 
 
 @pytest.mark.parametrize("T,B", [(3, 4096), (1, 1000), (5, 37)])
