@@ -1,4 +1,4 @@
-"""ctypes binding of librecalgo_hip.so (the C-ABI declared in include/recalgo.h).
+"""ctypes binding of librecalgo_hip.so (the C-ABI declared in include/recalgo.h and include/recalgo_cgc.h).
 
 The product path has NO CPU fallback: if the shared library is missing or a symbol
 declared in the header is absent, loading raises immediately.
@@ -23,6 +23,9 @@ SIGNATURES = ABI.functions  # name -> (restype, argtypes) of every function of t
 STRUCTS = ABI.structs  # recalgo_*_t -> ctypes.Structure subclass
 CONSTANTS = ABI.constants  # RECALGO_* -> int
 ABI_VERSION = CONSTANTS["RECALGO_ABI_VERSION"]  # (bumped on any signature change)
+# include/recalgo_cgc.h: the second header of the same library (PLE's CGC block), with a version of its own
+ABI_CGC = _abi.read("recalgo_cgc.h")
+ABI_CGC_VERSION = ABI_CGC.constants["RECALGO_CGC_ABI_VERSION"]
 
 _lib = None
 
@@ -47,18 +50,21 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "(there is no CPU fallback for the hot path)")
     import torch  # noqa: F401  (maps torch's libamdhip64 before ours resolves its NEEDED)
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise RecalgoError(f"{path} does not export {name}") from e
-        fn.restype = res
-        fn.argtypes = args
-        if name in ABI.launches:
-            fn.errcheck = launch_errcheck(name)
-    if lib.recalgo_abi_version() != ABI_VERSION:
-        raise RecalgoError(f"{path}: ABI version {lib.recalgo_abi_version()}, this binding expects {ABI_VERSION} "
-                           "(a stale build: python -m recalgorithm_amd.build)")
+    for abi in (ABI, ABI_CGC):
+        for name, (res, args) in abi.functions.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise RecalgoError(f"{path} does not export {name}") from e
+            fn.restype = res
+            fn.argtypes = args
+            if name in abi.launches:
+                fn.errcheck = launch_errcheck(name)
+    for what, got, want in (("ABI", lib.recalgo_abi_version(), ABI_VERSION),
+                            ("CGC ABI", lib.recalgo_cgc_abi_version(), ABI_CGC_VERSION)):
+        if got != want:
+            raise RecalgoError(f"{path}: {what} version {got}, this binding expects {want} "
+                               "(a stale build: python -m recalgorithm_amd.build)")
     _lib = lib
     return lib
 

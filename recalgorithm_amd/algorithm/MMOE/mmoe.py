@@ -12,8 +12,6 @@ dropout / BatchNorm epilogues, the T losses and their sum are one launch (ops.mu
 """
 from __future__ import annotations
 
-import csv
-import os
 from typing import Tuple
 
 import torch
@@ -23,7 +21,7 @@ from ... import flags, nn
 from ...model_tail import finish_multitask_model_fn
 from ...variables import variable_scope
 from .. import _common as common
-from ..utils import eval_input_fn, parse_example
+from ..utils import parse_example
 from .tower_layer import tower_layer
 
 # flags: /root/reference algorithm/MMOE/mmoe.py:16-44
@@ -110,25 +108,8 @@ def main(unused_argv):
     print("after evaluate")
 
 
-def write_predictions(estimator, example_parser, out_csv="predictions.csv"):
-    """mmoe.py:341-351: one `<task>_probabilities` column per task; the label join with dataframe/test.csv is applied only
-    when that file exists (quirk B-13)."""
-    task_names = FLAGS.task_names.split(",")
-    results = estimator.predict(input_fn=lambda: eval_input_fn(
-        filepath=FLAGS.eval_data, example_parser=example_parser, batch_size=FLAGS.batch_size))
-    labels = None
-    test_csv = "../../dataset/wechat_algo_data1/dataframe/test.csv"
-    if os.path.exists(test_csv):
-        with open(test_csv) as f:
-            labels = list(csv.DictReader(f))
-    with open(out_csv, "w", newline="") as f:
-        w = csv.writer(f)
-        w.writerow([""] + [f"{t}_probabilities" for t in task_names] + (task_names if labels else []))
-        for i, r in enumerate(results):
-            row = [i] + [float(r[f"{t}_probabilities"].reshape(-1)[0]) for t in task_names]
-            if labels and i < len(labels):
-                row += [labels[i].get(t) for t in task_names]
-            w.writerow(row)
+# mmoe.py:341-351, shared with the other multi-task scripts
+write_predictions = common.write_multitask_predictions
 
 
 if __name__ == "__main__":

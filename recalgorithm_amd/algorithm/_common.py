@@ -189,3 +189,24 @@ def fused_fm_sparse_part(features, params, first_scope: str, dense_name: str, wh
         raise NotImplementedError(f"{who}: multi-valued fields are not supported by the fused sparse kernel")
     rb = store.row_base_tensor(arena, [t for _, t in tables])
     return ops.deepfm_sparse(store, fc._as_matrix(ids), arena, w1, bias, rb)
+
+
+def write_multitask_predictions(estimator, example_parser, out_csv="predictions.csv"):
+    """The predictions writer of the multi-task scripts (mmoe.py:341-351, ple.py:373-382): one `<task>_probabilities` column
+    per task; the label join with dataframe/test.csv is applied only when that file exists (quirk B-13)."""
+    task_names = FLAGS.task_names.split(",")
+    results = estimator.predict(input_fn=lambda: eval_input_fn(
+        filepath=FLAGS.eval_data, example_parser=example_parser, batch_size=FLAGS.batch_size))
+    labels = None
+    test_csv = "../../dataset/wechat_algo_data1/dataframe/test.csv"
+    if os.path.exists(test_csv):
+        with open(test_csv) as f:
+            labels = list(csv.DictReader(f))
+    with open(out_csv, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow([""] + [f"{t}_probabilities" for t in task_names] + (task_names if labels else []))
+        for i, r in enumerate(results):
+            row = [i] + [float(r[f"{t}_probabilities"].reshape(-1)[0]) for t in task_names]
+            if labels and i < len(labels):
+                row += [labels[i].get(t) for t in task_names]
+            w.writerow(row)

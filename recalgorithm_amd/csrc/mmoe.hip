@@ -1,6 +1,7 @@
-// Multi-gate mixture of experts (MMoE, algorithm/MMOE/mmoe.py:208-232; the same block as PLE's CGC,
-// algorithm/PLE/extraction_network.py): the bias-free softmax gates and the mix of the expert outputs in ONE streaming
-// kernel each way, and the T-task sigmoid cross-entropy tail in one launch.
+// Multi-gate mixture of experts (MMoE, algorithm/MMOE/mmoe.py:208-232; PLE's CGC block, algorithm/PLE/extraction_network.py,
+// is the same block only within this kernel's limits — E, n_g <= 16, 16 KiB of gate kernels; PLE's default sizes are served
+// by csrc/cgc.hip): the bias-free softmax gates and the mix of the expert outputs in ONE streaming kernel each way, and the
+// T-task sigmoid cross-entropy tail in one launch.
 //
 //   z_g = x Wg                     x [B, In], Wg [In, n_g]: the gate kernels sit in LDS
 //   p_g = softmax(z_g)             max-subtracted

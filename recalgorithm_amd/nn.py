@@ -522,14 +522,19 @@ class _ExpertsFn(Function):
         return (None, dx if need_x else None, None, None) + (None,) * (2 * len(ks))
 
 
-def expert_layers(x: torch.Tensor, units, num_experts: int, chain: Optional[InputGradChain] = None):
+def expert_layers(x: torch.Tensor, units, num_experts: int, chain: Optional[InputGradChain] = None, names=None):
     """[tf.layers.dense(x, units, activation=tf.nn.relu, name=f"expert_{i}") for i in range(num_experts)] (mmoe.py:199-202):
-    variables <scope>/expert_<i>/{kernel,bias}.  -> the list of expert outputs [B, units]."""
+    variables <scope>/expert_<i>/{kernel,bias}, or <scope>/<names[i]>/{kernel,bias} when `names` lists the num_experts layer
+    names (PLE's shared_expert_<j> / task_specific_expert_<task>_<j>: ONE call — one autograd node, one input-gradient chain —
+    over all the experts of a block).  -> the list of expert outputs [B, units]."""
     store = current_store()
     units = int(units)
+    names = [f"expert_{i}" for i in range(int(num_experts))] if names is None else [str(n) for n in names]
+    if len(names) != int(num_experts) or len(set(names)) != len(names):
+        raise ValueError("expert_layers: `names` must list num_experts distinct layer names")
     kb = []
-    for i in range(int(num_experts)):
-        with store.variable_scope(f"expert_{i}"):
+    for name in names:
+        with store.variable_scope(name):
             kb.append(store.get_variable("kernel", (x.shape[-1], units), glorot_uniform))
             kb.append(store.get_variable("bias", (units,), zeros))
     if store.building:
@@ -561,6 +566,28 @@ def gate_mix(x: torch.Tensor, experts, num_gates: int, selection=None, chain: Op
         return [torch.zeros_like(experts[0]) for _ in selection], x.new_zeros(x.shape[0], sum(len(s) for s in selection))
     return ops.gate_mix(x if x.stride(-1) == 1 else x.contiguous(), kernels, experts, selection, x_grad_sink=chain,
                         anchor=store.anchor, return_gates=True)
+
+
+def cgc_layer(x: torch.Tensor, experts, gate_names, selection, sum_outputs: bool = False,
+              chain: Optional[InputGradChain] = None):
+    """The gates and the mix of a PLE "customized gate control" block (extraction_network.py:55-85, ple.py:215-226): per
+    named gate tf.layers.dense(x, n_g, activation=tf.nn.softmax, use_bias=False, name=<gate_name>) over the experts
+    selection[g], mixed by tf.matmul(experts, gate[..., None], transpose_a=True) — one kernel each way (ops.cgc_mix).
+    Variables: <scope>/<gate_name>/kernel (a gate name may carry a scope of its own: "task_gate_final/gate_final_like").
+    -> the per-gate mixed tensors [B, H]; with sum_outputs their tf.add_n as ONE tensor."""
+    from . import ops
+    store = current_store()
+    experts, selection = list(experts), [list(s) for s in selection]
+    if len(gate_names) != len(selection):
+        raise ValueError("cgc_layer: one gate name per selection row")
+    kernels = []
+    for name, sel in zip(gate_names, selection):
+        with store.variable_scope(name):
+            kernels.append(store.get_variable("kernel", (x.shape[-1], len(sel)), glorot_uniform))
+    if store.building:
+        return torch.zeros_like(experts[0]) if sum_outputs else [torch.zeros_like(experts[0]) for _ in selection]
+    return ops.cgc_mix(x if x.stride(-1) == 1 else x.contiguous(), kernels, experts, selection, sum_outputs=sum_outputs,
+                       x_grad_sink=chain, anchor=store.anchor)
 
 
 def dense_with(x: torch.Tensor, kernel: Variable, bias: Optional[Variable] = None, relu: bool = False) -> torch.Tensor:

@@ -1978,16 +1978,46 @@ def _colsum_now(jobs, device_tensor: torch.Tensor) -> None:
 
 
 class GateMixSpec:
-    """What `_GateMixFn` needs besides its tensors: the gate kernels (Variables: the gradient goes to Variable.grad through the
-    step's deferred column sums; tensors: returned by backward), the selection table, whether the experts are ReLU outputs
-    whose gradient this op masks, and where the gates' share of d x goes (x_grad_sink.first instead of autograd)."""
+    """What `_GateMixFn` / `_CgcMixFn` need besides their tensors: the gate kernels (Variables: the gradient goes to Variable.grad
+    through the step's deferred column sums; tensors: returned by backward), the selection table, whether the experts are ReLU
+    outputs whose gradient the op masks, where the gates' share of d x goes (x_grad_sink.first instead of autograd), and
+    (`_CgcMixFn` only) whether the G outputs are summed into one."""
 
-    def __init__(self, kernels, selection, relu_sources, x_grad_sink):
+    def __init__(self, kernels, selection, relu_sources, x_grad_sink, sum_outputs: bool = False):
         self.kernels, self.selection, self.relu_sources, self.x_grad_sink = kernels, selection, relu_sources, x_grad_sink
+        self.sum_outputs = bool(sum_outputs)
         self.n_sel = (ctypes.c_int * len(selection))(*[len(s) for s in selection])
         flat = [int(e) for s in selection for e in s]
         self.sel = (ctypes.c_int * len(flat))(*flat)
         self.n_total = len(flat)
+
+
+def _mix_backward_tail(spec: GateMixSpec, ws, need_w, partials, rows, x, dx, dex):
+    """What the backward of both gate-mix ops does once its kernel has run (-> the Function's return tuple): hands the masked
+    expert gradients to the experts' ReluSources, turns the [rows, In * n_total] partial rows into the gate kernels' gradients
+    (Variables: jobs of the step's deferred column sums; tensors: a fixed-order sum launched now) and offers d x to the sink."""
+    if spec.relu_sources is not None:
+        for src, d in zip(spec.relu_sources, dex):
+            src.premasked = d                # (nn.ReluSource: the expert layers' backward then runs without mask loads)
+    In, stride = x.shape[1], x.shape[1] * spec.n_total
+    dws, now, off = [], [], 0
+    for k, w, nd in zip(spec.kernels, ws, need_w):
+        n = In * w.shape[1]
+        if isinstance(k, Variable):
+            _colsum_pending.append((partials, off, rows, stride, n, k.grad))
+            dws.append(None)
+        elif nd:
+            dw = torch.empty_like(w)
+            now.append((partials, off, rows, stride, n, dw))
+            dws.append(dw)
+        else:
+            dws.append(None)
+        off += n
+    if now:
+        _colsum_now(now, x)
+    if dx is not None and spec.x_grad_sink is not None and spec.x_grad_sink.offer(dx):
+        dx = None                            # (the other consumers of x add it in their input-gradient epilogue)
+    return (None, None, dx, *dex, *dws)
 
 
 class _GateMixFn(Function):
@@ -2028,28 +2058,7 @@ class _GateMixFn(Function):
         relu = spec.relu_sources is not None
         lib.recalgo_gate_mix_bwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts), _p(p),
                                  _ptr_array(gs), B, In, E, G, H, int(relu), _ptr_array(dex), _p(dx), In, _p(partials), _stream(x))
-        if relu:
-            for src, d in zip(spec.relu_sources, dex):
-                src.premasked = d            # (nn.ReluSource: the expert layers' backward then runs without mask loads)
-        # gate kernel gradients: fixed-order column sums of the per-workgroup partial rows
-        dws, now, off = [], [], 0
-        for k, w, nd in zip(spec.kernels, ws, ctx.needs_input_grad[3 + E:]):
-            n = In * w.shape[1]
-            if isinstance(k, Variable):
-                _colsum_pending.append((partials, off, rows, In * spec.n_total, n, k.grad))
-                dws.append(None)
-            elif nd:
-                dw = torch.empty_like(w)
-                now.append((partials, off, rows, In * spec.n_total, n, dw))
-                dws.append(dw)
-            else:
-                dws.append(None)
-            off += n
-        if now:
-            _colsum_now(now, x)
-        if need_x and spec.x_grad_sink is not None and spec.x_grad_sink.offer(dx):
-            dx = None                        # (the other consumers of x add it in their input-gradient epilogue)
-        return (None, None, dx, *dex, *dws)
+        return _mix_backward_tail(spec, ws, ctx.needs_input_grad[3 + E:], partials, rows, x, dx, dex)
 
 
 def gate_mix_supported(In: int, E: int, G: int, H: int, n_total: int) -> bool:
@@ -2092,6 +2101,106 @@ def gate_mix(x: torch.Tensor, gate_kernels, experts, selection=None, x_grad_sink
     spec = GateMixSpec(gate_kernels, selection, srcs, x_grad_sink)
     gate_ts = [None if isinstance(k, Variable) else k for k in gate_kernels]
     *outs, p = _GateMixFn.apply(anchor, spec, x, *experts, *gate_ts)
+    return (outs, p) if return_gates else outs
+
+
+# =============================================================================================
+# PLE (csrc/cgc.hip, include/recalgo_cgc.h): the CGC block — wide softmax gates + expert mix, optionally summed
+# =============================================================================================
+_CC = _lib.ABI_CGC.constants                 # the RECALGO_CGC_* #defines of include/recalgo_cgc.h
+CGC_MAX_EXPERTS = _CC["RECALGO_CGC_MAX_EXPERTS"]
+CGC_MAX_GATES = _CC["RECALGO_CGC_MAX_GATES"]
+
+
+class _CgcMixFn(Function):
+    """include/recalgo_cgc.h recalgo_cgc_fwd / recalgo_cgc_bwd: G outputs [B, H], or their sum as ONE (spec.sum_outputs)."""
+
+    @staticmethod
+    def forward(ctx, anchor, spec: GateMixSpec, x, *tensors):
+        ctx.set_materialize_grads(False)     # a gate nobody differentiates: NULL upstream gradient, no zero tensor
+        G = len(spec.kernels)
+        experts, gate_ts = tensors[:len(tensors) - G], tensors[len(tensors) - G:]
+        ws = [k.data if isinstance(k, Variable) else t for k, t in zip(spec.kernels, gate_ts)]
+        B, In = x.shape
+        E, H = len(experts), experts[0].shape[1]
+        outs = [torch.empty(B, H, device=x.device, dtype=torch.float32) for _ in range(1 if spec.sum_outputs else G)]
+        p = torch.empty(B, spec.n_total, device=x.device, dtype=torch.float32)
+        _lib_().recalgo_cgc_fwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts),
+                                B, In, E, G, H, int(spec.sum_outputs), _ptr_array(outs), _p(p), _stream(x))
+        ctx.spec, ctx.ws, ctx.E = spec, ws, E
+        ctx.save_for_backward(x, p, *experts)
+        ctx.mark_non_differentiable(p)
+        return (*outs, p)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        spec, ws, E = ctx.spec, ctx.ws, ctx.E
+        x, p, *experts = ctx.saved_tensors
+        G = len(ws)
+        M = 1 if spec.sum_outputs else G
+        gs = [None if g is None else (g if g.is_contiguous() else g.contiguous()) for g in grads[:M]]
+        n_in = 3 + E + G
+        if all(g is None for g in gs):
+            return (None,) * n_in
+        B, In = x.shape
+        H = experts[0].shape[1]
+        lib = _lib_()
+        need_x = ctx.needs_input_grad[2]
+        need_e = ctx.needs_input_grad[3:3 + E]
+        dx = torch.empty(B, In, device=x.device, dtype=torch.float32) if need_x else None
+        dex = [torch.empty_like(t) if nd else None for t, nd in zip(experts, need_e)]
+        rows = int(lib.recalgo_cgc_partial_rows(B, In, spec.n_total))
+        partials = torch.empty(rows, In * spec.n_total, device=x.device, dtype=torch.float32)
+        relu = spec.relu_sources is not None
+        lib.recalgo_cgc_bwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts), _p(p),
+                            _ptr_array(gs), B, In, E, G, H, int(spec.sum_outputs), int(relu), _ptr_array(dex), _p(dx), In,
+                            _p(partials), _stream(x))
+        return _mix_backward_tail(spec, ws, ctx.needs_input_grad[3 + E:], partials, rows, x, dx, dex)
+
+
+def cgc_supported(In: int, E: int, G: int, H: int, n_total: int, n_max: int) -> bool:
+    return bool(_lib_().recalgo_cgc_supported(int(In), int(E), int(G), int(H), int(n_total), int(n_max)))
+
+
+def cgc_mix(x: torch.Tensor, gate_kernels, experts, selection, sum_outputs: bool = False, x_grad_sink=None, anchor=None,
+            return_gates: bool = False):
+    """PLE's CGC block (extraction_network.py:25-85, ple.py:185-226) at sizes beyond `gate_mix`: for every gate g,
+        out_g = sum_j softmax(x @ gate_kernels[g])[:, j, None] * experts[selection[g][j]]
+    x [B, In]; gate_kernels: G bias-free [In, n_g] kernels (Variables or tensors); experts: E [B, H] tensors;
+    selection[g]: the n_g expert indices gate g mixes (duplicates allowed).
+    -> the G outputs [B, H]; with sum_outputs ONE tensor, their sum (the tf.add_n an extraction network returns) — and the
+    gate probabilities [B, sum n_g] with return_gates.
+    Experts that carry an nn.ReluSource get their gradient already masked; x_grad_sink as in `gate_mix`.
+    Malformed tables: ValueError.  Outside the kernel's limits (recalgo_cgc_supported) or an empty batch: NotImplementedError."""
+    gate_kernels, experts = list(gate_kernels), list(experts)
+    E, G = len(experts), len(gate_kernels)
+    selection = [list(s) for s in selection]
+    ws = [k.data if isinstance(k, Variable) else k for k in gate_kernels]
+    if x.dim() != 2 or G < 1 or len(selection) != G or \
+            any(w.dim() != 2 or tuple(w.shape) != (x.shape[1], len(s)) for w, s in zip(ws, selection)):
+        raise ValueError("cgc_mix: one [In, n_g] gate kernel per selection row")
+    if any(len(s) < 1 for s in selection) or any(e < 0 or e >= E for s in selection for e in s):
+        raise ValueError("cgc_mix: every gate selects at least one expert, indices in [0, E)")
+    if E < 1 or any(t.dim() != 2 or t.shape != experts[0].shape or t.shape[0] != x.shape[0] for t in experts):
+        raise ValueError("cgc_mix: experts must be E same-shaped [B, H] tensors")
+    H = experts[0].shape[1]
+    n_total, n_max = sum(len(s) for s in selection), max(len(s) for s in selection)
+    if not cgc_supported(x.shape[1], E, G, H, n_total, n_max):
+        raise NotImplementedError(
+            f"cgc_mix serves H % 4 == 0, E <= {CGC_MAX_EXPERTS}, G <= {CGC_MAX_GATES}, n_g <= {CGC_MAX_EXPERTS}, In <= 512 and "
+            f"In * (sum n_g | 1) <= 20480; got In={x.shape[1]} E={E} G={G} H={H} sum n_g={n_total} max n_g={n_max}")
+    if x.shape[0] == 0:
+        raise NotImplementedError("cgc_mix: empty batch")
+    x = _mat(x, "x")
+    for w in ws:
+        _chk(w, torch.float32, "gate kernel")
+    srcs = [getattr(t, "_recalgo_relu_src", None) if getattr(t, "_recalgo_relu_scale", 1.0) == 1.0 else None for t in experts]
+    srcs = srcs if all(s is not None for s in srcs) else None
+    experts = [_mat(t if t.is_contiguous() else t.contiguous(), "expert") for t in experts]
+    spec = GateMixSpec(gate_kernels, selection, srcs, x_grad_sink, sum_outputs=sum_outputs)
+    gate_ts = [None if isinstance(k, Variable) else k for k in gate_kernels]
+    *outs, p = _CgcMixFn.apply(anchor, spec, x, *experts, *gate_ts)
+    outs = outs[0] if sum_outputs else outs
     return (outs, p) if return_gates else outs
 
 

@@ -1,0 +1,320 @@
+"""CPU (no kernels launched): the PLE feature's host side.
+  * tests/ple_ref.py (the float64 restatement the GPU tests compare against) reproduces both goldens that
+    scripts/gen_golden_ple.py obtained by executing the reference's own algorithm/PLE/ple.py on oracle/tf1_shim;
+  * the generator's --check round trip (where the reference folder exists);
+  * the CGC backward formulas as written in include/recalgo_cgc.h (summed mode: ONE upstream gradient shared by every
+    gate, E dot products per row), against float64 autograd;
+  * the mirror's variables, and the multi-task tail's PREDICT / EVAL keys, on the launch-free registration pass;
+  * the limits of ops.cgc_mix / ops.cgc_supported;
+  * include/recalgo_cgc.h, the second ABI header: declared = bound, exported by the same library, errcheck on its launches,
+    constants re-exported, include/recalgo_cgc.abi at the header's version with the header's hash."""
+import ctypes
+import hashlib
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import ref_ops as R
+from tests import golden_util as GU
+from tests import ple_ref
+from tests.test_mmoe_host import close, encode, task_labels
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "recalgo_cgc.h")
+GOLDENS = {"model_ple": 76, "model_ple_two_levels_dropout": 96}        # name -> gradient arrays
+TOL = 1e-10         # the bound of every comparison with a golden below
+
+
+def mirror_setup(name, vocab_dir):
+    """(model_fn, params) of the mirror for golden `name`, from the mirror's own create_feature_columns()."""
+    from recalgorithm_amd import flags
+    from recalgorithm_amd.algorithm.PLE import ple as m
+    d = GU.load(name)
+    fl = {k: (v.item() if v.shape == () else v) for k, v in GU.section(d, "flag/").items()}
+    flags.FLAGS.vocabulary_dir = vocab_dir
+    for k, v in fl.items():
+        setattr(flags.FLAGS, k, v)
+    dense, cat, label = m.create_feature_columns()
+    assert [c.key for c in label] == str(fl["task_names"]).split(",")
+    return m.ple_model_fn, {
+        "dense_feature_columns": dense, "category_feature_columns": cat, "hidden_units": str(fl["hidden_units"]).split(","),
+        "dropout_rate": float(fl["dropout_rate"]), "batch_norm": bool(fl["batch_norm"]), "learning_rate": float(fl["learning_rate"]),
+        "num_tasks": int(fl["num_tasks"]), "expert_hidden_units": int(fl["expert_hidden_units"]),
+        "task_names": str(fl["task_names"]).split(","), "num_extract_network": int(fl["num_extract_network"]),
+        "num_experts_per_task": [int(x) for x in str(fl["num_experts_per_task"]).split(",")],
+        "num_experts_in_shared": int(fl["num_experts_in_shared"])}
+
+
+@pytest.mark.parametrize("name", list(GOLDENS))
+def test_restatement_reproduces_the_golden(name, tmp_path):
+    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
+    _, params = mirror_setup(name, vocab_dir)
+    assert params["num_experts_per_task"] == [2, 1, 3] and params["num_experts_in_shared"] == 2
+    d = GU.load(name)
+    tasks = params["task_names"]
+    sfeats, labels = GU.string_batch()
+    feats = encode(params, sfeats)
+    lab = task_labels(d, labels, tasks)
+    P = {k: torch.from_numpy(v.copy()).requires_grad_(True) for k, v in GU.section(d, "var/").items()}
+    out = ple_ref.ple(P, feats, None, params, training=False)
+    for t in tasks:
+        close(out["probs"][t], d[f"predict/{t}_probabilities"], f"{name} {t}_probabilities", tol=TOL)
+    masks = GU.dropout_masks(d)
+    assert len(masks) == (6 if float(params["dropout_rate"]) > 0 else 0)
+    out = ple_ref.ple(P, feats, lab, params, training=True, dropout_masks=masks)
+    close(out["loss"], d["train/loss"], f"{name} loss", tol=TOL)
+    out["loss"].backward()
+    gg, ga = GU.section(d, "grad/"), GU.section(d, "var_after/")
+    assert len(gg) == GOLDENS[name] and not [k for k in gg if k not in P]
+    assert not [k for k, g in gg.items() if not np.any(g)], "an all-zero gradient in the golden"
+    for k, g in gg.items():
+        got = P[k].grad if P[k].grad is not None else torch.zeros_like(P[k])
+        close(got, g, f"{name} d({k})", tol=TOL)
+        p = P[k].detach().clone()            # one TF1-Adam step (A-10) on the golden's gradient
+        R.adam_tf1_step(p, torch.from_numpy(g.copy()), torch.zeros_like(p), torch.zeros_like(p), 1, float(d["meta/learning_rate"]))
+        close(p, ga[k], f"{name} adam({k})", tol=TOL)
+    # EVAL after the step: the updated variables, the moving statistics the TRAIN run left
+    Pa = {k: torch.from_numpy(v.copy()) for k, v in ga.items()}
+    ev = ple_ref.ple(Pa, feats, lab, params, training=False)
+    close(ev["loss"], d["eval/loss"], f"{name} eval loss", tol=TOL)
+    for t in tasks:
+        acc = ((ev["probs"][t] >= 0.5).double() == lab[t]).double().mean()
+        close(acc, d[f"eval/{t}_accuracy"], f"{name} eval {t} accuracy", tol=TOL)
+        close(R.tf_metrics_auc(lab[t], ev["probs"][t]), d[f"eval/{t}_auc"], f"{name} eval {t} auc", tol=TOL)
+
+
+def test_generator_check_round_trip():
+    from oracle import gen_golden
+    if not os.path.isdir(os.path.join(gen_golden.REF, "PLE")):
+        pytest.skip("the reference folder is not on this machine")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "gen_golden_ple.py"), "--check"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "model_ple.npz  checked" in r.stdout and "model_ple_two_levels_dropout.npz  checked" in r.stdout
+
+
+def cgc_summed_backward_formulas(x, ws, experts, selection, p_rows, d, relu_experts=False):
+    """The summed-mode backward of include/recalgo_cgc.h, written out (float64): every gate shares the ONE upstream d, so
+        dot[e] = <d, expert_e>                       E dot products per row, not sum n_g
+        d_expert_e = (sum_g c[g][e]) * d             c[g][e] = sum_{j: sel[g][j] = e} p_g[j]  (zeroed where expert_e <= 0 if relu)
+        dp_g[j] = dot[sel[g][j]];  dz_g = p_g * (dp_g - sum_j p_g[j] dp_g[j]);  dx = sum_g dz_g Wg^T;  dWg = x^T dz_g"""
+    E = len(experts)
+    dot = torch.stack([(d * e).sum(dim=1) for e in experts], dim=1)              # [B, E]
+    ctot = torch.zeros(x.shape[0], E, dtype=x.dtype)
+    dx, dws = torch.zeros_like(x), []
+    for w, sel, p in zip(ws, selection, p_rows):
+        for j, e in enumerate(sel):
+            ctot[:, e] += p[:, j]
+        dp = dot[:, sel]
+        dz = p * (dp - (p * dp).sum(dim=1, keepdim=True))
+        dx += dz @ w.t()
+        dws.append(x.t() @ dz)
+    dex = [ctot[:, e:e + 1] * d for e in range(E)]
+    if relu_experts:
+        dex = [g * (e > 0) for g, e in zip(dex, experts)]
+    return dx, dws, dex
+
+
+@pytest.mark.parametrize("shape", [(29, 7, 6, 4, 8, ple_ref.ple_selection([2, 1, 1], 2, all_gate=True)),
+                                   (11, 4, 2, 2, 4, [[1, 1, 0], [0]])])
+def test_cgc_summed_backward_formulas_against_autograd(shape):
+    B, In, E, G, H, selection = shape
+    assert len(selection) == G and max(e for s in selection for e in s) == E - 1
+    gen = torch.Generator().manual_seed(B * 131 + H)
+    x = torch.randn(B, In, generator=gen, dtype=torch.float64, requires_grad=True)
+    ws = [torch.randn(In, len(s), generator=gen, dtype=torch.float64, requires_grad=True) for s in selection]
+    experts = [torch.randn(B, H, generator=gen, dtype=torch.float64, requires_grad=True) for _ in range(E)]
+    d = torch.randn(B, H, generator=gen, dtype=torch.float64)
+    out, ps = ple_ref.cgc(x, ws, experts, selection, sum_outputs=True)
+    per_gate, _ = ple_ref.cgc(x, ws, experts, selection)
+    close(out, sum(per_gate).detach(), "the summed output is the sum of the per-gate outputs", tol=1e-14)
+    grads = torch.autograd.grad((out * d).sum(), [x, *ws, *experts])
+    with torch.no_grad():
+        dx, dws, dex = cgc_summed_backward_formulas(x, ws, experts, selection, ps, d)
+    close(dx, grads[0], "dx", tol=1e-12)
+    for g, (a, b) in enumerate(zip(dws, grads[1:1 + G])):
+        close(a, b, f"dW{g}", tol=1e-12)
+    for e, (a, b) in enumerate(zip(dex, grads[1 + G:])):
+        close(a, b, f"d_expert{e}", tol=1e-12)
+    # experts that are ReLU outputs: the masked form is the gradient at the pre-activation
+    pre = [torch.randn(B, H, generator=gen, dtype=torch.float64, requires_grad=True) for _ in range(E)]
+    relu = [torch.relu(t) for t in pre]
+    out, ps = ple_ref.cgc(x, ws, relu, selection, sum_outputs=True)
+    gpre = torch.autograd.grad((out * d).sum(), pre)
+    with torch.no_grad():
+        _, _, dex = cgc_summed_backward_formulas(x, ws, [t.detach() for t in relu], selection, ps, d, relu_experts=True)
+    for e, (a, b) in enumerate(zip(dex, gpre)):
+        close(a, b, f"d_expert{e} (relu)", tol=1e-12)
+
+
+@pytest.mark.parametrize("name", list(GOLDENS))
+def test_mirror_variables_and_tail_keys_on_the_registration_pass(name, tmp_path):
+    from recalgorithm_amd.estimator import Estimator, ModeKeys, RunConfig
+    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
+    model_fn, params = mirror_setup(name, vocab_dir)
+    d = GU.load(name)
+    tasks = params["task_names"]
+    sfeats, labels = GU.string_batch()
+    feats = {k: (v.float() if isinstance(v, torch.Tensor) else v) for k, v in sfeats.items()}
+    lab = {t: v.float() for t, v in task_labels(d, labels, tasks).items()}
+    est = Estimator(model_fn, params, RunConfig(device="cpu", seed=3, use_hip_graph=False))
+    est.build(feats, lab)                    # registration pass only: no HIP call
+    arrays = est.store.named_arrays()
+    gv = GU.section(d, "var/")
+    assert not [k for k in gv if k not in arrays], "reference variables absent from the mirror"
+    assert not [k for k in arrays if k not in gv], "mirror variables the reference does not have"
+    for k, v in gv.items():
+        assert tuple(arrays[k].shape) == tuple(v.shape), (k, arrays[k].shape, v.shape)
+    est.store.building = True
+    try:
+        with torch.no_grad():
+            pred = est._call_model_fn(feats, None, ModeKeys.PREDICT)
+            ev = est._call_model_fn(feats, lab, ModeKeys.EVAL)
+    finally:
+        est.store.building = False
+    assert sorted(pred.predictions) == sorted(f"{t}_probabilities" for t in tasks)
+    assert pred.export_outputs == {"prediction": pred.predictions}
+    assert all(tuple(v.shape) == (48, 1) for v in pred.predictions.values())
+    assert sorted(ev.eval_metric_ops) == sorted([f"eval_{t}_accuracy" for t in tasks] + [f"eval_{t}_auc" for t in tasks])
+    assert ev.loss is not None and ev.loss.dim() == 0
+
+
+def test_reference_flag_defaults_and_call_surface():
+    """ple.py:21-50 (checked in a child process: a model script imported earlier in this one defines flags of the same names)"""
+    code = ("from recalgorithm_amd.algorithm.PLE import ple as m; from recalgorithm_amd.algorithm.PLE.extraction_network import "
+            "extraction_network; F = m.FLAGS; print(F.batch_size, F.learning_rate, F.hidden_units, F.batch_norm, F.dropout_rate, "
+            "F.num_extract_network, F.num_experts_per_task, F.num_experts_in_shared, F.expert_hidden_units, F.num_tasks, "
+            "F.task_names); print(all(callable(getattr(m, n)) for n in ('create_feature_columns', 'example_parser', "
+            "'ple_model_fn', 'main')), callable(m.example_parser.columns_getter), "
+            "extraction_network.__code__.co_varnames[:6])")
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = r.stdout.strip().splitlines()
+    assert lines[-2] == "1024 0.005 512,256,128 True 0.1 1 5,5,5 10 256 3 read_comment,like,click_avatar"
+    assert lines[-1] == ("True True ('input', 'task_names', 'num_experts_per_task', 'num_experts_in_shared', "
+                         "'expert_hidden_units', 'name')")
+
+
+def test_limits():
+    """the limits include/recalgo_cgc.h states (the entry points check them again; this needs the built library, not a GPU:
+    built here if stale, as tests/test_abi.py does)"""
+    from recalgorithm_amd import build, ops
+    build.build(verbose=False)
+    assert ops.cgc_supported(82, 25, 4, 256, 70, 25)             # the default extraction network
+    assert ops.cgc_supported(256, 25, 3, 256, 45, 15)            # the default final CGC
+    assert ops.cgc_supported(82, 7, 4, 12, 22, 8) and ops.cgc_supported(12, 7, 3, 12, 14, 5)     # the golden shapes
+    assert ops.cgc_supported(512, 32, 8, 1028, 39, 32)           # 512 * 39 floats: under the 80 KiB
+    assert not ops.cgc_supported(82, 25, 4, 254, 70, 25)         # H % 4
+    assert not ops.cgc_supported(82, 33, 4, 256, 70, 25)         # E = 33
+    assert not ops.cgc_supported(82, 25, 9, 256, 70, 25)         # G = 9
+    assert not ops.cgc_supported(513, 25, 4, 256, 30, 25)        # In = 513
+    assert not ops.cgc_supported(82, 25, 4, 256, 70, 33)         # a gate over 33 experts
+    assert not ops.cgc_supported(512, 25, 4, 256, 41, 25)        # 512 * 41 floats > 20 480
+    assert ops.CGC_MAX_EXPERTS == 32 and ops.CGC_MAX_GATES == 8
+    x, e = torch.zeros(4, 82), [torch.zeros(4, 8) for _ in range(3)]
+    w = [torch.zeros(82, 3)]
+    with pytest.raises(NotImplementedError, match="H % 4 == 0, E <= 32, G <= 8, n_g <= 32, In <= 512"):
+        ops.cgc_mix(x, w, [torch.zeros(4, 6) for _ in range(3)], [[0, 1, 2]])
+    with pytest.raises(NotImplementedError):
+        ops.cgc_mix(x, [torch.zeros(82, 1)] * 9, e, [[0]] * 9)                                   # G = 9
+    with pytest.raises(NotImplementedError):
+        ops.cgc_mix(x, [torch.zeros(82, 33)], [torch.zeros(4, 8) for _ in range(33)], [list(range(33))])       # E = 33
+    with pytest.raises(NotImplementedError, match="empty batch"):
+        ops.cgc_mix(torch.zeros(0, 82), w, [torch.zeros(0, 8) for _ in range(3)], [[0, 1, 2]])
+    with pytest.raises(ValueError):
+        ops.cgc_mix(x, [torch.zeros(82, 0)], e, [[]])                                            # a gate over no expert
+    with pytest.raises(ValueError):
+        ops.cgc_mix(x, w, e, [[0, 1, 3]])                                                        # an index past E
+    with pytest.raises(ValueError):
+        ops.cgc_mix(x, w, e, [[0, 1]])                                                           # kernel width != n_g
+    with pytest.raises(ValueError):
+        ops.cgc_mix(x, w, e, [[0, 1, 2], [0]])                                                   # a row without a kernel
+    with pytest.raises(ValueError):
+        ops.cgc_mix(x, w, e[:2] + [torch.zeros(4, 12)], [[0, 1, 2]])                             # experts of two widths
+
+
+# ---- include/recalgo_cgc.h: the checks tests/test_abi.py and tests/test_abi_reader.py make on recalgo.h ---------------------
+def declared_functions():
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(recalgo_[a-z0-9_]+)\s*\(", src)))
+
+
+def declaration_hash():
+    """sha256 over the header's declarations: comments, the version number and white space removed."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"#define RECALGO_CGC_ABI_VERSION \d+", "", src)
+    return hashlib.sha256(re.sub(r"\s+", " ", src).strip().encode()).hexdigest()
+
+
+def test_second_header_is_bound_and_exported():
+    from recalgorithm_amd import _abi, _lib, build
+    lib_path = build.build(verbose=False)
+    declared = declared_functions()
+    assert declared == sorted(["recalgo_cgc_abi_version", "recalgo_cgc_supported", "recalgo_cgc_partial_rows",
+                               "recalgo_cgc_fwd", "recalgo_cgc_bwd"])
+    assert set(_lib.ABI_CGC.functions) == set(declared)
+    assert not set(_lib.ABI_CGC.functions) & set(_lib.SIGNATURES), "the first header's table stays what it is"
+    assert _lib.ABI_CGC.launches == ["recalgo_cgc_fwd", "recalgo_cgc_bwd"]
+    assert not _lib.ABI_CGC.structs
+    raw = ctypes.CDLL(lib_path)
+    assert not [f for f in declared if not hasattr(raw, f)], "declared in recalgo_cgc.h but not exported"
+    lib = _lib.load()
+    assert lib.recalgo_cgc_abi_version() == _lib.ABI_CGC_VERSION == 1
+    for name, (res, args) in _lib.ABI_CGC.functions.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+        assert (fn.errcheck is not None) == (name in _lib.ABI_CGC.launches), name
+    c_int, ptr = ctypes.c_int, ctypes.c_void_p
+    assert _lib.ABI_CGC.functions["recalgo_cgc_supported"] == (c_int, [c_int] * 6)
+    assert _lib.ABI_CGC.functions["recalgo_cgc_partial_rows"] == (c_int, [c_int] * 3)
+    assert _lib.ABI_CGC.functions["recalgo_cgc_fwd"] == (c_int, [ptr, c_int, ptr, ptr, ptr, ptr] + [c_int] * 6 + [ptr, ptr, ptr])
+    assert _lib.ABI_CGC.functions["recalgo_cgc_bwd"] == (
+        c_int, [ptr, c_int, ptr, ptr, ptr, ptr, ptr, ptr] + [c_int] * 7 + [ptr, ptr, c_int, ptr, ptr])
+    # a launch that returns an error raises through the errcheck (NULL tables: refused before any launch)
+    with pytest.raises(_lib.RecalgoError, match="recalgo_cgc_fwd failed with hipError_t=[1-9]"):
+        lib.recalgo_cgc_fwd(None, 0, None, None, None, None, 1, 1, 1, 1, 4, 0, None, None, None)
+    with pytest.raises(_lib.RecalgoError, match="recalgo_cgc_bwd failed with hipError_t=[1-9]"):
+        lib.recalgo_cgc_bwd(None, 0, None, None, None, None, None, None, 1, 1, 1, 1, 4, 0, 0, None, None, 0, None, None)
+    # self-contained: the reader takes it as it is, and it repeats the stream typedef instead of including recalgo.h
+    text = open(HEADER).read()
+    assert "typedef void* recalgo_stream_t;" in text and '#include "recalgo.h"' not in text
+    assert _abi.read("recalgo_cgc.h").constants == _lib.ABI_CGC.constants
+
+
+def test_second_header_constants_are_re_exported():
+    from recalgorithm_amd import _lib, ops
+    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (RECALGO_CGC_\w+) (\d+)", open(HEADER).read())
+               if not m.group(1).endswith("_H_")}
+    assert defines == {"RECALGO_CGC_ABI_VERSION": 1, "RECALGO_CGC_MAX_EXPERTS": 32, "RECALGO_CGC_MAX_GATES": 8}
+    assert _lib.ABI_CGC.constants == defines
+    assert ops.CGC_MAX_EXPERTS == defines["RECALGO_CGC_MAX_EXPERTS"] and ops.CGC_MAX_GATES == defines["RECALGO_CGC_MAX_GATES"]
+    # the first header's tables are untouched by the second
+    assert _lib.CONSTANTS is _lib.ABI.constants and not [k for k in _lib.CONSTANTS if k.startswith("RECALGO_CGC_")]
+
+
+def test_second_header_declarations_do_not_change_without_a_version_bump():
+    """include/recalgo_cgc.abi: one `version sha256` line per version, the convention of include/recalgo.abi"""
+    version = int(re.search(r"#define RECALGO_CGC_ABI_VERSION (\d+)", open(HEADER).read()).group(1))
+    recorded = dict((int(v), h) for v, h in (ln.split() for ln in open(os.path.join(ROOT, "include", "recalgo_cgc.abi"))
+                                             if ln.strip() and not ln.startswith("#")))
+    h = declaration_hash()
+    assert version == max(recorded), f"recalgo_cgc.h is at version {version}, include/recalgo_cgc.abi ends at {max(recorded)}"
+    assert recorded[version] == h, (
+        f"the declarations of include/recalgo_cgc.h changed (sha256 {h}) but RECALGO_CGC_ABI_VERSION is still {version}: bump "
+        f"it and append `<version> {h}` to include/recalgo_cgc.abi")
+    assert len(set(recorded.values())) == len(recorded), "two versions with identical declarations"
+
+
+def test_stale_second_header_version_fails_loudly(monkeypatch):
+    from recalgorithm_amd import _lib, build
+    build.build(verbose=False)
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "ABI_CGC_VERSION", _lib.ABI_CGC_VERSION + 1)
+    with pytest.raises(_lib.RecalgoError, match="CGC ABI version 1, this binding expects 2"):
+        _lib.load()
