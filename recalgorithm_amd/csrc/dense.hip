@@ -690,12 +690,15 @@ __global__ __launch_bounds__(kThreads) void dense_wgrad_kernel(WgradArgs P) {
 // layer's backward waits for them), the rest weight-gradient tiles.  The two GEMMs share nothing but their inputs;
 // what the merge buys is one launch ramp / drain / boundary instead of two (each ~6 us per layer at these sizes,
 // scripts/bench_dense_k.py) and a fuller chip for the small layers (256 + 256 workgroups for [4096 x 256 x 128]).
-template <bool FAST, bool MASK>
+// FAST_D / FAST_W: each GEMM takes the main loop its own operands allow, as in its separate launch — the two main loops add in
+// different orders, and "same results" as recalgo_dense_bwd_input + recalgo_dense_bwd_weights means bit for bit (K % 4 != 0 with
+// N % 4 == 0: float4-addressable G and W, element-wise X)
+template <bool FAST_D, bool FAST_W, bool MASK>
 __global__ __launch_bounds__(kThreads) void dense_bwd_kernel(DgradArgs D, WgradArgs W, int dgrad_blocks) {
     __shared__ __attribute__((aligned(16))) float As[kStages * kBufFloats];
     __shared__ __attribute__((aligned(16))) float Bs[kStages * kBufFloats];
-    if ((int)blockIdx.x < dgrad_blocks) dgrad_tile<FAST, MASK>(D, blockIdx.x, dgrad_blocks, As, Bs);
-    else wgrad_tile<FAST, MASK>(W, blockIdx.x - dgrad_blocks, As, Bs);
+    if ((int)blockIdx.x < dgrad_blocks) dgrad_tile<FAST_D, MASK>(D, blockIdx.x, dgrad_blocks, As, Bs);
+    else wgrad_tile<FAST_W, MASK>(W, blockIdx.x - dgrad_blocks, As, Bs);
 }
 
 // The same launch carrying RIDERS: work of OTHER layers over the same batch whose operands are ready and which nothing in this
@@ -1031,11 +1034,17 @@ RECALGO_EXPORT int recalgo_dense_bwd(const float* x, int ldx, const float* g, in
     RECALGO_REQUIRE(S >= 1);
     hipStream_t st = as_stream(stream);
     const int gd = cdiv(cdiv(M, BM) * cdiv(K, BN), D.tiles_per_block), gw = cdiv(K, BM) * cdiv(N, BN) * S;
-    const bool fast = dgrad_fast(D) && wgrad_fast(W);
-    if (fast && y_mask) hipLaunchKernelGGL((dense_bwd_kernel<true, true>), dim3(gd + gw), dim3(kThreads), 0, st, D, W, gd);
-    else if (fast) hipLaunchKernelGGL((dense_bwd_kernel<true, false>), dim3(gd + gw), dim3(kThreads), 0, st, D, W, gd);
-    else if (y_mask) hipLaunchKernelGGL((dense_bwd_kernel<false, true>), dim3(gd + gw), dim3(kThreads), 0, st, D, W, gd);
-    else hipLaunchKernelGGL((dense_bwd_kernel<false, false>), dim3(gd + gw), dim3(kThreads), 0, st, D, W, gd);
+    const bool fd = dgrad_fast(D), fw = wgrad_fast(W);
+#define BWD_LAUNCH(FD, FW)                                                                                                     \
+    do {                                                                                                                       \
+        if (y_mask) hipLaunchKernelGGL((dense_bwd_kernel<FD, FW, true>), dim3(gd + gw), dim3(kThreads), 0, st, D, W, gd);      \
+        else hipLaunchKernelGGL((dense_bwd_kernel<FD, FW, false>), dim3(gd + gw), dim3(kThreads), 0, st, D, W, gd);            \
+    } while (0)
+    if (fd && fw) BWD_LAUNCH(true, true);
+    else if (fd) BWD_LAUNCH(true, false);
+    else if (fw) BWD_LAUNCH(false, true);
+    else BWD_LAUNCH(false, false);
+#undef BWD_LAUNCH
     return finish_wgrad(S, defer_reduce, K, N, dw, dbias, workspace, st);
 }
 
