@@ -1,4 +1,5 @@
-"""ctypes binding of librecalgo_hip.so (the C-ABI declared in include/recalgo.h and include/recalgo_cgc.h).
+"""ctypes binding of librecalgo_hip.so (the C-ABI declared in include/recalgo.h, include/recalgo_cgc.h and
+include/recalgo_wide.h).
 
 The product path has NO CPU fallback: if the shared library is missing or a symbol
 declared in the header is absent, loading raises immediately.
@@ -26,6 +27,9 @@ ABI_VERSION = CONSTANTS["RECALGO_ABI_VERSION"]  # (bumped on any signature chang
 # include/recalgo_cgc.h: the second header of the same library (PLE's CGC block), with a version of its own
 ABI_CGC = _abi.read("recalgo_cgc.h")
 ABI_CGC_VERSION = ABI_CGC.constants["RECALGO_CGC_ABI_VERSION"]
+# include/recalgo_wide.h: the third header (Wide&Deep's crossed wide column + FTRL), with a version of its own
+ABI_WIDE = _abi.read("recalgo_wide.h")
+ABI_WIDE_VERSION = ABI_WIDE.constants["RECALGO_WIDE_ABI_VERSION"]
 
 _lib = None
 
@@ -50,7 +54,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "(there is no CPU fallback for the hot path)")
     import torch  # noqa: F401  (maps torch's libamdhip64 before ours resolves its NEEDED)
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for abi in (ABI, ABI_CGC):
+    for abi in (ABI, ABI_CGC, ABI_WIDE):
         for name, (res, args) in abi.functions.items():
             try:
                 fn = getattr(lib, name)
@@ -61,7 +65,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             if name in abi.launches:
                 fn.errcheck = launch_errcheck(name)
     for what, got, want in (("ABI", lib.recalgo_abi_version(), ABI_VERSION),
-                            ("CGC ABI", lib.recalgo_cgc_abi_version(), ABI_CGC_VERSION)):
+                            ("CGC ABI", lib.recalgo_cgc_abi_version(), ABI_CGC_VERSION),
+                            ("WIDE ABI", lib.recalgo_wide_abi_version(), ABI_WIDE_VERSION)):
         if got != want:
             raise RecalgoError(f"{path}: {what} version {got}, this binding expects {want} "
                                "(a stale build: python -m recalgorithm_amd.build)")

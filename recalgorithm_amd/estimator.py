@@ -56,8 +56,12 @@ class EvalSpec:
 # tf.train.AdamOptimizer (a15)
 # --------------------------------------------------------------------------------------------
 class TrainOp:
-    def __init__(self, optimizer: "AdamOptimizer", loss: torch.Tensor, store: VariableStore):
+    """optimizer.minimize(loss, var_list=...).  var_list None: every trainable variable (what every model but Wide&Deep asks
+    for); else the variables `get_collection(GraphKeys.TRAINABLE_VARIABLES, scope=...)` returned."""
+
+    def __init__(self, optimizer: "AdamOptimizer", loss: torch.Tensor, store: VariableStore, var_list=None):
         self.optimizer, self.loss, self.store = optimizer, loss, store
+        self.var_list = None if var_list is None else list(var_list)
 
     def run(self):
         self.loss.backward()
@@ -73,11 +77,17 @@ class AdamOptimizer:
     def __init__(self, learning_rate=0.001, beta1=0.9, beta2=0.999, epsilon=1e-8):
         self.lr, self.beta1, self.beta2, self.eps = float(learning_rate), beta1, beta2, epsilon
 
-    def minimize(self, loss, global_step=None) -> TrainOp:
+    def minimize(self, loss, global_step=None, var_list=None) -> TrainOp:
+        """global_step is accepted and ignored: the Estimator counts its steps itself, once per step.  An Adam op over a
+        var_list that leaves trainable variables out is only valid inside group() with the op that claims the rest (the
+        fused launch sweeps the whole flat buffer: it is the identity exactly where g = m = v = 0)."""
         from .variables import current_store
-        return TrainOp(self, loss, current_store())
+        return TrainOp(self, loss, current_store(), var_list)
 
-    def apply_gradients(self, store: VariableStore, grad_hook: Optional[Callable] = None):
+    def apply_gradients(self, store: VariableStore, grad_hook: Optional[Callable] = None,
+                        before_update: Optional[Callable] = None):
+        """before_update (group()): called once the step's gradients are complete (parked sums, all-reduce) and before the
+        first Adam launch — another optimizer consumes and zeroes the gradients of ITS variables there."""
         st = store.ensure_opt_state()
         from . import nn, sparse
         arenas = [ar for ar in store.arenas.values() if ar.weight is not None and ar.trainable]
@@ -92,6 +102,8 @@ class AdamOptimizer:
         nn.apply_parked_grads(step_dev=st["step"] if fused else None)
         if grad_hook is not None:           # data-parallel all-reduce of the flat dense grads
             grad_hook(store)
+        if before_update is not None:
+            before_update()
         if fused:
             # one launch: dense TF1 Adam over the flat buffer + dense-semantics TF1 Adam over the rows a gradient has ever
             # reached (the update is the identity for all others); lr_t derived on the device from the step counter
@@ -129,6 +141,147 @@ class LazyAdamOptimizer(AdamOptimizer):
 
 def get_global_step():
     return None
+
+
+# --------------------------------------------------------------------------------------------
+# tf.train.FtrlOptimizer, tf.get_collection(TRAINABLE_VARIABLES, scope), tf.group (Wide&Deep, wide_and_deep.py:251-276)
+# --------------------------------------------------------------------------------------------
+class FtrlOptimizer:
+    """tf.train.FtrlOptimizer(learning_rate) with TF's defaults (initial_accumulator_value 0.1, l1 = l2 = 0, lr_power -0.5):
+    ApplyFtrl, restated in include/recalgo_wide.h (not checked against TensorFlow).  Slots: `<var>/Ftrl` (accum) and
+    `<var>/Ftrl_1` (linear), TF's names.
+
+    The reference's wide gradient is dense, so TF updates EVERY bucket of the wide kernel in every step.  Reproduced exactly
+    by a sparse update: buckets the batch touched get the update (fused with the gradient sum, csrc/wide.hip); a bucket it
+    did not touch has g = 0, for which the update (1) on the first step sets var = 0 (linear == 0): the glorot initial values
+    survive only until the first training step — one hash_bucket_size-wide zeroing launch, once; (2) on every later step
+    recomputes the same accum, linear and var: nothing to do.
+    Serves the variables of nn.crossed_indicator_dense layers (kernel and bias); anything else raises."""
+
+    def __init__(self, learning_rate, learning_rate_power=-0.5, initial_accumulator_value=0.1,
+                 l1_regularization_strength=0.0, l2_regularization_strength=0.0):
+        if float(learning_rate_power) != -0.5:
+            raise NotImplementedError("FtrlOptimizer: learning_rate_power = -0.5 (TF's default) only")
+        self.lr, self.init = float(learning_rate), float(initial_accumulator_value)
+        self.l1, self.l2 = float(l1_regularization_strength), float(l2_regularization_strength)
+
+    def minimize(self, loss, global_step=None, var_list=None) -> TrainOp:
+        from . import wide
+        from .variables import current_store
+        store = current_store()
+        if var_list is None:
+            var_list = get_collection(GraphKeys.TRAINABLE_VARIABLES)
+        op = TrainOp(self, loss, store, var_list)
+        if not store.building:
+            for st in self._states(store, op.var_list):
+                st.ensure_slots(self.init)          # (before any capture: a slot is never allocated by a captured step)
+        return op
+
+    @staticmethod
+    def _states(store, var_list):
+        from . import wide
+        found, names = [], {getattr(v, "name", None) for v in var_list}
+        for v in var_list:
+            st = wide.state_of(store, v)
+            if st is None:
+                raise NotImplementedError(f"FtrlOptimizer: {getattr(v, 'name', v)} is not a variable of a crossed wide layer "
+                                          "(nn.crossed_indicator_dense)")
+            if st not in found:
+                found.append(st)
+        for st in found:
+            missing = [v.name for v in (st.kernel, st.bias) if v is not None and v.name not in names]
+            if missing:
+                raise NotImplementedError(f"FtrlOptimizer: var_list must hold both variables of a wide layer ({missing} left out)")
+        return found
+
+    def apply_var_list(self, store: VariableStore, var_list) -> None:
+        """the gradients are complete (bias.grad in the flat gradient buffer): update, and leave g = 0 behind"""
+        import struct
+        f32 = lambda x: struct.unpack("f", struct.pack("f", x))[0]      # TF keeps the hyper-parameters as float32
+        for st in self._states(store, var_list):
+            st.apply_ftrl(f32(self.lr), f32(self.l1), f32(self.l2), f32(self.init))
+
+    def apply_gradients(self, store: VariableStore, grad_hook: Optional[Callable] = None, var_list=None):
+        from . import nn
+        nn.apply_parked_grads()
+        if grad_hook is not None:
+            raise NotImplementedError("FtrlOptimizer: data parallelism is not supported")
+        self.apply_var_list(store, get_collection(GraphKeys.TRAINABLE_VARIABLES, store=store) if var_list is None else var_list)
+
+
+class GraphKeys:
+    TRAINABLE_VARIABLES = "trainable_variables"
+
+
+class TableRef:
+    """An embedding table in a var_list (the tables live in arenas, not in Variables)."""
+
+    def __init__(self, name: str):
+        self.name = name
+
+    def __repr__(self):
+        return f"TableRef({self.name})"
+
+
+def _trainable_names(store: VariableStore):
+    names = [n for n in store.order if store.vars[n].trainable and n not in {b for b, _ in store._alias.values()}]
+    names += [n for n, v in store.vars.items() if n in store._alias and v.trainable]
+    for ar in store.arenas.values():
+        if ar.trainable:
+            names += list(ar.tables)
+    return names
+
+
+def get_collection(key, scope: Optional[str] = None, store: Optional[VariableStore] = None):
+    """tf.get_collection(tf.GraphKeys.TRAINABLE_VARIABLES, scope=...): the trainable variables (and embedding tables, as
+    TableRefs) whose name starts with `scope` (TF matches the scope as a prefix), in creation order."""
+    from .variables import current_store
+    if key != GraphKeys.TRAINABLE_VARIABLES:
+        raise NotImplementedError(f"get_collection: only GraphKeys.TRAINABLE_VARIABLES (got {key!r})")
+    store = store or current_store()
+    names = [n for n in _trainable_names(store) if scope is None or n.startswith(scope)]
+    return [store.vars[n] if n in store.vars else TableRef(n) for n in names]
+
+
+class _Group:
+    """The optimizers of group(op, op, ...): ONE backward pass has filled the gradients; each optimizer then updates its
+    var_list.  FTRL ops run first, inside the Adam op's `before_update` (they consume and zero the gradients of their
+    variables), then the one Adam launch sweeps everything — the identity on the variables it does not own."""
+
+    def __init__(self, ops):
+        self.ops = list(ops)
+        store = self.ops[0].store
+        self.adam = [op for op in self.ops if isinstance(op.optimizer, AdamOptimizer)]
+        self.ftrl = [op for op in self.ops if isinstance(op.optimizer, FtrlOptimizer)]
+        if len(self.adam) > 1 or len(self.adam) + len(self.ftrl) != len(self.ops):
+            raise NotImplementedError("group: at most one Adam op, any number of FTRL ops")
+        if any(op.loss is not self.ops[0].loss or op.store is not store for op in self.ops):
+            raise NotImplementedError("group: every op must minimize the same loss (one backward pass)")
+        if not store.building:
+            claimed = [v.name for op in self.ops for v in (op.var_list if op.var_list is not None else get_collection(
+                GraphKeys.TRAINABLE_VARIABLES, store=store))]
+            if sorted(claimed) != sorted(_trainable_names(store)):
+                raise NotImplementedError("group: the ops' var_lists must partition the trainable variables "
+                                          f"({len(claimed)} claimed, {len(_trainable_names(store))} trainable)")
+
+    def apply_gradients(self, store: VariableStore, grad_hook: Optional[Callable] = None):
+        def ftrl_updates():
+            for op in self.ftrl:
+                op.optimizer.apply_var_list(store, op.var_list)
+        if self.adam:
+            self.adam[0].optimizer.apply_gradients(store, grad_hook, before_update=ftrl_updates)
+        else:
+            from . import nn
+            nn.apply_parked_grads()
+            ftrl_updates()
+
+
+def group(*train_ops) -> TrainOp:
+    """tf.group(wide_part_op, deep_part_op): one train op — one backward pass, every optimizer on its own var_list, the
+    global step advanced once."""
+    if not train_ops:
+        raise ValueError("group: no ops")
+    return TrainOp(_Group(train_ops), train_ops[0].loss, train_ops[0].store)
 
 
 # --------------------------------------------------------------------------------------------
@@ -813,6 +966,15 @@ class Estimator:
             for name, val in values.items():
                 if name.endswith("/Adam") or name.endswith("/Adam_1") or name in ("global_step", "beta1_power", "beta2_power"):
                     continue
+                if name.endswith("/Ftrl") or name.endswith("/Ftrl_1"):
+                    # FTRL slots (TF's names): restored where the model has an FTRL-trained wide layer for them
+                    from . import wide
+                    for st in wide.states(self.store).values():
+                        if name.rsplit("/", 1)[0] in [v.name for v in (st.kernel, st.bias) if v is not None]:
+                            st.ensure_slots(0.1)
+                            st.slots[name].copy_(torch.as_tensor(val).to(torch.float32).reshape(st.slots[name].shape))
+                            st.ftrl_steps = max(st.ftrl_steps, 1)      # (slots of a trained model: the first-step zeroing is behind it)
+                    continue
                 t = torch.as_tensor(val).to(torch.float32)
                 if name in arrays:
                     if tuple(arrays[name].shape) != tuple(t.shape):
@@ -869,6 +1031,10 @@ class Estimator:
         import numpy as np
         from .io import tf_checkpoint
         arrays = dict(self.export_variables())
+        from . import wide
+        for st in wide.states(self.store).values():              # FTRL slots under TF's names: <var>/Ftrl, <var>/Ftrl_1
+            for n, t in st.slots.items():
+                arrays[n] = t.detach().cpu().numpy().copy()
         arrays["global_step"] = np.array(int(self.global_step), dtype=np.int64)
         tf_checkpoint.write_checkpoint(prefix, arrays)
         return prefix
@@ -927,6 +1093,11 @@ def collect_checkpoint_state(store: VariableStore, global_step: int):
         "arena_m": arena_m, "arena_v": arena_v,
         "opt_step": None if store.opt_state is None else int(store.opt_state["step"]),
     }
+    from . import wide
+    ftrl = {n: t.cpu() for st in wide.states(store).values() for n, t in st.slots.items()}
+    if ftrl:                                 # FTRL slots under TF's names (<var>/Ftrl accum, <var>/Ftrl_1 linear)
+        state["ftrl_slots"] = ftrl
+        state["ftrl_steps"] = {k: st.ftrl_steps for k, st in wide.states(store).items()}
     return state, True
 
 
@@ -998,6 +1169,16 @@ def restore_checkpoint_state(store: VariableStore, state: dict, device, where: s
             a.live = None            # rebuilt from the restored moments on next use
             from . import sparse
             sparse.reset(a)          # (deferred-Adam bookkeeping likewise)
+    from . import wide
+    for k, st in wide.states(store).items():
+        saved_slots = state.get("ftrl_slots") or {}
+        mine = [v.name + sfx for v in (st.kernel, st.bias) if v is not None for sfx in ("/Ftrl", "/Ftrl_1")]
+        if all(n in saved_slots for n in mine):
+            st.slots = {}
+            st.ensure_slots(0.0)
+            for n in mine:
+                st.slots[n].copy_(saved_slots[n].reshape(st.slots[n].shape))
+            st.ftrl_steps = int((state.get("ftrl_steps") or {}).get(k, 1))
     if state.get("opt_step") is not None:
         if store.opt_state is not None and _same_device(store.opt_state["step"].device, device):
             # in place: the captured step, and the arenas' deferred-Adam plans (sparse.sync_arena), hold THIS tensor

@@ -147,6 +147,49 @@ class EmbeddingColumn:
         return self.categorical_column.parse_spec()
 
 
+class CrossedColumn:
+    """tf.feature_column.crossed_column(keys, hash_bucket_size, hash_key): the cross of two CategoricalColumns over their int64
+    ids (TF 1.14 sparse_cross_op.cc HashCrosser with FingerprintCat64, restated in include/recalgo_wide.h; not checked against
+    TensorFlow).  One cross per (id of keys[0], id of keys[1]) pair of an example; the first key is single-valued, the second
+    may be a bag.  Ids are crossed as their int64 value: an OOV id of -1 is crossed as 0xFFFF...FFFF, as TF crosses the
+    vocabulary column's default_value.  A dense [B] id column cannot tell an absent value from an OOV one: both are -1 and
+    both are crossed (TF would make no cross for an absent value)."""
+
+    def __init__(self, keys, hash_bucket_size, hash_key=None):
+        keys = list(keys)
+        if len(keys) != 2 or not all(isinstance(k, CategoricalColumn) for k in keys):
+            raise NotImplementedError("crossed_column: exactly two CategoricalColumn keys (the reference's only use)")
+        if not 1 <= int(hash_bucket_size) <= 2147483647:
+            raise ValueError("crossed_column: hash_bucket_size must be in [1, 2^31 - 1]")
+        self.keys, self.hash_bucket_size = keys, int(hash_bucket_size)
+        self.hash_key = 0xDECAFCAFFE if hash_key is None else int(hash_key)
+        self.name = "_X_".join(sorted(k.name for k in keys))
+
+    @property
+    def key(self):
+        return self.name
+
+    @property
+    def num_buckets(self) -> int:
+        return self.hash_bucket_size
+
+    def parse_spec(self):
+        spec = {}
+        for k in self.keys:
+            spec.update(k.parse_spec())
+        return spec
+
+    def requests(self, features, device):
+        """-> (ids of keys[0] int64 [B], bag values of keys[1] int64, bag offsets int64 [B + 1] | None: one value per
+        example), on `device`"""
+        a, b = (k.ids(features, device) for k in self.keys)
+        if isinstance(a, Ragged):
+            raise NotImplementedError(f"crossed_column: the first key ({self.keys[0].key}) must be single-valued")
+        if isinstance(b, Ragged):
+            return a, b.values.contiguous(), b.offsets.contiguous()
+        return a, b, None
+
+
 class IndicatorColumn:
     def __init__(self, categorical_column):
         self.categorical_column = categorical_column
@@ -194,6 +237,14 @@ def shared_embedding_columns(categorical_columns, dimension, combiner="mean"):
 
 def indicator_column(categorical_column):
     return IndicatorColumn(categorical_column)
+
+
+def crossed_column(keys, hash_bucket_size, hash_key=None):
+    return CrossedColumn(keys, hash_bucket_size, hash_key)
+
+
+def is_crossed_indicator(column) -> bool:
+    return isinstance(column, IndicatorColumn) and isinstance(column.categorical_column, CrossedColumn)
 
 
 def make_parse_example_spec(feature_columns) -> dict:
@@ -258,6 +309,11 @@ def input_layer(features, feature_columns, _layer_name: Optional[str] = None) ->
     dev = store.device
     widths = []
     for c in cols:
+        if is_crossed_indicator(c):
+            # [B, hash_bucket_size] multi-hot: 1.6 GB at B = 4096 x 100000 buckets.  It is never materialised.
+            raise NotImplementedError(
+                f"input_layer: {c.name} is an indicator over a crossed column; its multi-hot is never materialised.  Feed it, "
+                "alone, to nn.crossed_indicator_dense (the fused wide op: cross hash + indicator + one-unit dense layer)")
         if isinstance(c, NumericColumn):
             widths.append(int(np.prod(c.shape)))
         elif isinstance(c, EmbeddingColumn):

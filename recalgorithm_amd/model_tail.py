@@ -19,7 +19,10 @@ def sigmoid(logit: torch.Tensor) -> torch.Tensor:
 def finish_model_fn(mode, logit: torch.Tensor, labels, params,
                     predictions: Optional[Callable[[torch.Tensor], Dict[str, torch.Tensor]]] = None,
                     extra_loss: Optional[Callable[[], torch.Tensor]] = None,
-                    label_key: str = "read_comment") -> EstimatorSpec:
+                    label_key: str = "read_comment",
+                    train_op: Optional[Callable[[torch.Tensor], object]] = None) -> EstimatorSpec:
+    """`train_op` (a model that trains with its own optimizers, wide_and_deep.py:251-276): loss -> the train op; default:
+    Adam(params["learning_rate"]) on every variable."""
     from .nn import LazyLogit
     lazy = logit if isinstance(logit, LazyLogit) else None
     extra = None
@@ -72,6 +75,8 @@ def finish_model_fn(mode, logit: torch.Tensor, labels, params,
     # TRAIN: the reference also builds the two metric ops here, but only to feed tf.summary /
     # LoggingTensorHook (deepfm.py:237-238,256-271); they are not part of the training step
     assert mode == ModeKeys.TRAIN
+    if train_op is not None:
+        return EstimatorSpec(mode, loss=loss, train_op=train_op(loss), predictions={"probabilities": prob})
     opt_cls = LazyAdamOptimizer if params.get("lazy_adam") else AdamOptimizer      # lazy_adam: labelled deviation (§8f-1)
     optimizer = opt_cls(learning_rate=params["learning_rate"], beta1=0.9, beta2=0.999, epsilon=1e-8)
     train_op = optimizer.minimize(loss=loss)

@@ -430,6 +430,37 @@ def dense(x, units, activation: Optional[str] = None,
     return out
 
 
+def crossed_indicator_dense(features, feature_columns, units=1, name: Optional[str] = None, training: bool = False) -> torch.Tensor:
+    """tf.layers.dense(fc.input_layer(features, [fc.indicator_column(fc.crossed_column([a, b], H))]), 1, name=name)
+    (the reference's algorithm/WideAndDeep/wide_and_deep.py:208-210) as ONE launch that never builds the [B, H] multi-hot
+    (wide.py, csrc/wide.hip).  Same scopes and variables as the two calls: the input layer takes its auto name (it owns no
+    variable), the layer owns <scope>/<name>/kernel (H, 1) glorot-uniform and <scope>/<name>/bias (1,) zeros.  `training`:
+    a TRAIN step — the requests are counted for the backward's plan; the kernel's gradient never becomes a dense tensor
+    unless somebody reads it, and estimator.FtrlOptimizer updates the touched buckets in place."""
+    from . import feature_column as fc
+    from . import wide
+    store = current_store()
+    cols = list(feature_columns)
+    if len(cols) != 1 or not fc.is_crossed_indicator(cols[0]) or int(units) != 1:
+        raise NotImplementedError("crossed_indicator_dense: ONE indicator column over a crossed column, one unit")
+    crossed = cols[0].categorical_column
+    if getattr(store, "shard_at_build", None) is not None or getattr(store, "sync_bn", None) is not None:
+        raise NotImplementedError(wide.NO_DATA_PARALLEL)
+    store.auto_name("input_layer")
+    name = name or store.auto_name("dense")
+    with store.variable_scope(name):
+        kernel = store.get_variable("kernel", (crossed.hash_bucket_size, 1), glorot_uniform)
+        bias = store.get_variable("bias", (1,), zeros)
+    B = fc._batch_size(features, crossed.keys[0])
+    st = wide.states(store).get(kernel.name)
+    if st is None:           # (made on the registration pass: a checkpoint restored right after it finds the layer)
+        st = wide.states(store)[kernel.name] = wide.WideState(kernel, bias, crossed.hash_bucket_size, crossed.hash_key)
+    if store.building:
+        return torch.zeros(B, 1, device=store.device)
+    users, tags, offsets = crossed.requests(features, store.device)
+    return wide.cross_logit(store, st, users, tags, offsets, training=training)
+
+
 def dense_relu_dropout_bn(x, units, dropout_rate, batch_norm: bool, training: bool) -> torch.Tensor:
     """One hidden layer of the DeepFM / PNN / FiBiNET / NFM MLPs (/root/reference algorithm/DeepFM/deepfm.py:207-211):
         net = tf.layers.dense(net, unit, activation=tf.nn.relu)

@@ -301,8 +301,9 @@ class _BagMeanFn(Function):
         rb, vocab = arena.tables[table_name]
         g = g.contiguous()
         if ctx.src is not None:
-            lens = offsets[1:] - offsets[:-1]
-            bag = torch.repeat_interleave(torch.arange(B, device=values.device), lens)
+            # bag of every entry = the number of bag ends at or before it (what repeat_interleave(arange(B), lens) lists, without
+            # its host synchronisation: a step with a bag lookup captures into a hipGraph)
+            bag = torch.searchsorted(offsets[1:], torch.arange(values.numel(), device=values.device), right=True).clamp_(max=B - 1)
             cnt = torch.zeros(B, device=values.device).index_add_(0, bag, (values >= 0).float()).clamp_(min=1.0)
             ctx.src.set_grad(g[bag] / cnt[bag].unsqueeze(1))
             return None, None, None, None, None, None
@@ -2110,6 +2111,9 @@ def gate_mix(x: torch.Tensor, gate_kernels, experts, selection=None, x_grad_sink
 _CC = _lib.ABI_CGC.constants                 # the RECALGO_CGC_* #defines of include/recalgo_cgc.h
 CGC_MAX_EXPERTS = _CC["RECALGO_CGC_MAX_EXPERTS"]
 CGC_MAX_GATES = _CC["RECALGO_CGC_MAX_GATES"]
+# include/recalgo_wide.h (the op itself lives in wide.py)
+WIDE_HASH_KEY = _lib.ABI_WIDE.constants["RECALGO_WIDE_HASH_KEY"]
+WIDE_MAX_BUCKETS = _lib.ABI_WIDE.constants["RECALGO_WIDE_MAX_BUCKETS"]
 
 
 class _CgcMixFn(Function):

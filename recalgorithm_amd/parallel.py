@@ -451,6 +451,9 @@ def attach_data_parallel(est, dist=None, group=None, local_gather=hip_local_gath
     the reference's single-device BatchNorm on the concatenated batch; the default keeps per-replica statistics."""
     if dist is None:
         import torch.distributed as dist
+    from . import wide
+    if wide.states(est.store):
+        raise NotImplementedError(wide.NO_DATA_PARALLEL)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     sh = ShardSpec(rank, world, group, dist)
     if sync_batch_norm and world > 1:

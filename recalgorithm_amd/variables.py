@@ -270,10 +270,11 @@ class VariableStore:
 
 def named_grads(store: VariableStore) -> Dict[str, torch.Tensor]:
     """name -> gradient tensor, same keys as VariableStore.named_arrays()."""
-    from . import nn, parallel, sparse
+    from . import nn, parallel, sparse, wide
     nn.apply_parked_grads()
     parallel.join_push_streams()
     sparse.materialize_grads(store)
+    wide.materialize_grads(store)            # (a crossed wide layer's kernel gradient is a dense tensor only on request)
     out = {n: v.grad for n, v in store.vars.items() if v.grad is not None}
     for ar in store.arenas.values():
         for tn, (rb, vocab) in ar.tables.items():

@@ -1,6 +1,8 @@
 """Record the declaration hash of include/recalgo.h for its CURRENT RECALGO_ABI_VERSION in include/recalgo.abi — with
---cgc: of include/recalgo_cgc.h for its RECALGO_CGC_ABI_VERSION in include/recalgo_cgc.abi.
-Run after bumping the version for a signature change (tests/test_abi.py / tests/test_ple_host.py compare).  Re-recording an
+--cgc: of include/recalgo_cgc.h for its RECALGO_CGC_ABI_VERSION in include/recalgo_cgc.abi; with --wide: of
+include/recalgo_wide.h for its RECALGO_WIDE_ABI_VERSION in include/recalgo_wide.abi.
+Run after bumping the version for a signature change (tests/test_abi.py / tests/test_ple_host.py / tests/test_wdl_host.py
+compare).  Re-recording an
 existing version is only legitimate while that version has not left the development tree (no library of it exists anywhere
 else)."""
 import os
@@ -12,6 +14,9 @@ sys.path.insert(0, ROOT)
 if "--cgc" in sys.argv[1:]:
     from tests.test_ple_host import HEADER, declaration_hash  # noqa: E402
     define, record = "RECALGO_CGC_ABI_VERSION", "recalgo_cgc.abi"
+elif "--wide" in sys.argv[1:]:
+    from tests.test_wdl_host import HEADER, declaration_hash  # noqa: E402
+    define, record = "RECALGO_WIDE_ABI_VERSION", "recalgo_wide.abi"
 else:
     from tests.test_abi import HEADER, declaration_hash  # noqa: E402
     define, record = "RECALGO_ABI_VERSION", "recalgo.abi"
