@@ -35,7 +35,6 @@ constexpr int kThreads = 64 * kRows;
 constexpr int kDw = kWFloats / kThreads;               // dWg entries a thread owns, at the most
 constexpr int kFwdGrid = 512, kBwdGrid = 256;          // persistent grids: two / one workgroup per CU
 constexpr int kTab = 2 * kG + 2 * kNT;                 // ints: n[G] | off[G] | gate of column c | expert of column c
-constexpr int kLdsLimit = 160 * 1024;
 
 struct CgcTables {
     const float* wg[kG];
@@ -51,29 +50,6 @@ struct CgcBwdPtrs {
     const float* dout[kG];
     float* dex[kE];
 };
-
-__host__ __device__ __forceinline__ int round4(int v) { return (v + 3) & ~3; }
-
-template <bool VEC>
-__device__ __forceinline__ float4 ld4(const float* p) {
-    if (VEC) return *reinterpret_cast<const float4*>(p);
-    return make_float4(p[0], p[1], p[2], p[3]);
-}
-template <bool VEC>
-__device__ __forceinline__ void st4(float* p, float4 v) {
-    if (VEC) {
-        *reinterpret_cast<float4*>(p) = v;
-    } else {
-        p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
-    }
-}
-
-// LDS written by some lanes of a wave, read by others of the same wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // gate kernels -> Ws[k * ldw + off_g + j]; tab = [n | off | gate of column | expert of column]
 __device__ __forceinline__ void stage_gates(const CgcTables& T, int In, int G, int ldw, float* Ws, int* tab) {
@@ -328,7 +304,7 @@ size_t bwd_lds(int In, int NT, int mmax) {
 bool limits_ok(int In, int E, int G, int H, int64_t NT, int n_max) {
     return In >= 1 && In <= kMaxIn && E >= 1 && E <= kE && G >= 1 && G <= kG && H >= 4 && (H & 3) == 0 && n_max >= 1 &&
            n_max <= kE && NT >= G && NT <= (int64_t)G * n_max && (int64_t)In * (NT | 1) <= kWFloats &&
-           fwd_lds(In, (int)NT, kG) <= (size_t)kLdsLimit && bwd_lds(In, (int)NT, kG) <= (size_t)kLdsLimit;
+           fwd_lds(In, (int)NT, kG) <= kLdsMax && bwd_lds(In, (int)NT, kG) <= kLdsMax;
 }
 
 // validates the tables and fills T; -> false outside the served limits
@@ -358,49 +334,21 @@ bool cgc_tables(const float* const* gate_kernels, const int* n_sel, const int* s
     for (int e = 0; e < E; ++e) {
         if (experts[e] == nullptr) return false;
         T->ex[e] = experts[e];
-        vec = vec && (reinterpret_cast<uintptr_t>(experts[e]) & 15) == 0;
+        vec = vec && aligned16(experts[e]);
     }
     S->NT = NT, S->M = M, S->mmax = M <= 1 ? 1 : (M <= 4 ? 4 : 8), S->vec = vec;
     return true;
 }
 
-// A workgroup of these kernels may claim more than the 64 KiB of dynamic LDS a kernel gets by default.  The attribute belongs
-// to (kernel, device): it is raised once per arm and per device the arm is launched on (a benign race: the call is idempotent).
-constexpr int kMaxDevices = 64;
+// launch_lds raises the dynamic-LDS allowance of the arm it launches (these workgroups may claim more than kLdsDefault)
+#define CGC_LAUNCH(KERNEL, MM, ...)                                                             \
+    (S.vec ? launch_lds<KERNEL<MM, true>>(grid, dim3(kThreads), smem, st, __VA_ARGS__)          \
+           : launch_lds<KERNEL<MM, false>>(grid, dim3(kThreads), smem, st, __VA_ARGS__))
 
-template <typename K>
-hipError_t allow_lds(K kernel, bool* done) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= kMaxDevices) return hipErrorInvalidDevice;
-    if (done[dev]) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsLimit);
-    done[dev] = e == hipSuccess;
-    return e;
-}
-
-#define CGC_ARM(KERNEL, MM, VV, ...)                                                          \
-    do {                                                                                      \
-        static bool allowed[kMaxDevices] = {};                                                \
-        const hipError_t e = allow_lds(KERNEL<MM, VV>, allowed);                              \
-        if (e != hipSuccess) return (int)e;                                                   \
-        hipLaunchKernelGGL((KERNEL<MM, VV>), grid, dim3(kThreads), smem, st, __VA_ARGS__);    \
-    } while (0)
-
-#define CGC_DISPATCH(KERNEL, ...)                              \
-    do {                                                       \
-        if (S.mmax == 1) {                                     \
-            if (S.vec) CGC_ARM(KERNEL, 1, true, __VA_ARGS__);  \
-            else CGC_ARM(KERNEL, 1, false, __VA_ARGS__);       \
-        } else if (S.mmax == 4) {                              \
-            if (S.vec) CGC_ARM(KERNEL, 4, true, __VA_ARGS__);  \
-            else CGC_ARM(KERNEL, 4, false, __VA_ARGS__);       \
-        } else {                                               \
-            if (S.vec) CGC_ARM(KERNEL, 8, true, __VA_ARGS__);  \
-            else CGC_ARM(KERNEL, 8, false, __VA_ARGS__);       \
-        }                                                      \
-    } while (0)
+#define CGC_DISPATCH(KERNEL, ...)                                        \
+    RECALGO_CHECK(S.mmax == 1   ? CGC_LAUNCH(KERNEL, 1, __VA_ARGS__)     \
+                  : S.mmax == 4 ? CGC_LAUNCH(KERNEL, 4, __VA_ARGS__)     \
+                                : CGC_LAUNCH(KERNEL, 8, __VA_ARGS__))
 
 }  // namespace
 
@@ -427,7 +375,7 @@ RECALGO_EXPORT int recalgo_cgc_fwd(const float* x, int ldx, const float* const* 
     for (int m = 0; m < S.M; ++m) {
         RECALGO_REQUIRE(outs[m] != nullptr);
         O.out[m] = outs[m];
-        S.vec = S.vec && (reinterpret_cast<uintptr_t>(outs[m]) & 15) == 0;
+        S.vec = S.vec && aligned16(outs[m]);
     }
     const int want = cdiv(B, kRows);
     const dim3 grid(want > kFwdGrid ? kFwdGrid : want);
@@ -450,11 +398,11 @@ RECALGO_EXPORT int recalgo_cgc_bwd(const float* x, int ldx, const float* const* 
     CgcBwdPtrs P = {};
     for (int m = 0; m < S.M; ++m) {
         P.dout[m] = d_outs[m];
-        S.vec = S.vec && (reinterpret_cast<uintptr_t>(d_outs[m]) & 15) == 0;
+        S.vec = S.vec && aligned16(d_outs[m]);
     }
     for (int e = 0; e < E; ++e) {
         P.dex[e] = d_experts ? d_experts[e] : nullptr;
-        S.vec = S.vec && (reinterpret_cast<uintptr_t>(P.dex[e]) & 15) == 0;
+        S.vec = S.vec && aligned16(P.dex[e]);
     }
     const dim3 grid(recalgo_cgc_partial_rows(B, In, S.NT));
     const size_t smem = bwd_lds(In, S.NT, S.mmax);

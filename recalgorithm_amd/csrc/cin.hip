@@ -1041,16 +1041,9 @@ template <int D, int NT>
 int launch_contract_DN(const float* P, const float* Q, const float* F, int B, int HP, int HQ, int C, float* out,
                        int accumulate, float* pool, int pool_stride, int pool_col, hipStream_t st) {
     size_t smem = contract_smem(D, NT, HQ);
-    if (smem > 160 * 1024) return (int)hipErrorInvalidValue;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cin_contract_kernel<D, NT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
     dim3 grid(cdiv((int64_t)B * D, kTM), cdiv(C, NT * 32));
-    hipLaunchKernelGGL((cin_contract_kernel<D, NT>), grid, dim3(kThreads), smem, st, P, Q, F, (unsigned)B,
-                       (unsigned)HP, (unsigned)HQ, (unsigned)C, out, accumulate, pool, (unsigned)pool_stride,
-                       (unsigned)pool_col);
+    RECALGO_CHECK(launch_lds<cin_contract_kernel<D, NT>>(grid, dim3(kThreads), smem, st, P, Q, F, (unsigned)B, (unsigned)HP,
+            (unsigned)HQ, (unsigned)C, out, accumulate, pool, (unsigned)pool_stride, (unsigned)pool_col));
     return (int)hipGetLastError();
 }
 
@@ -1079,7 +1072,7 @@ int launch_contract(const float* P, const float* Q, const float* F, int B, int H
     if (C <= 0 || C > 128) return (int)hipErrorInvalidValue;
     // the register-resident-Q kernel: emb width 16, 17 .. 32 fields (13 .. 16 steps per slab: at most 3 of 16 padded), filter
     // columns in whole float4s and in (32, 64] or (96, 128] (2 or 4 full column tiles); everything else takes the general kernel
-    if (D == 16 && HQ > 16 && HQ <= 32 && C % 4 == 0 && (reinterpret_cast<uintptr_t>(F) & 15) == 0 && HP >= 1 &&
+    if (D == 16 && HQ > 16 && HQ <= 32 && C % 4 == 0 && aligned16(F) && HP >= 1 &&
         ((C > 32 && C <= 64) || (C > 96 && C <= 128))) {
         const bool wide = C > 64;
 #define RECALGO_CIN2(NSTEP)                                                                                                          \
@@ -1103,13 +1096,8 @@ template <int D, int KS>
 int launch_input_grad_DK(const float* x0, const float* xk, const float* W, const float* G, int B, int m, int Hk, int N,
                          float* dx0, int dx0_acc, float* dxk, int dxk_acc, hipStream_t st) {
     const size_t smem = (size_t)2 * 32 * (2 * KS + 1) * sizeof(float);
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cin_input_grad_kernel<D, KS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL((cin_input_grad_kernel<D, KS>), dim3(cdiv((int64_t)B * D, kTM)), dim3(kThreads), smem, st, x0, xk,
-                       W, G, (unsigned)B, (unsigned)m, (unsigned)Hk, (unsigned)N, dx0, dx0_acc, dxk, dxk_acc);
+    RECALGO_CHECK(launch_lds<cin_input_grad_kernel<D, KS>>(dim3(cdiv((int64_t)B * D, kTM)), dim3(kThreads), smem, st, x0, xk, W,
+            G, (unsigned)B, (unsigned)m, (unsigned)Hk, (unsigned)N, dx0, dx0_acc, dxk, dxk_acc));
     return (int)hipGetLastError();
 }
 template <int D>
@@ -1157,17 +1145,11 @@ template <int D, int NT, int QI, int RC>
 int launch_filter_grad_DNQ(const float* P, const float* Q, const float* G, int B, int HP, int HQ, int C, int S,
                            float* partials, hipStream_t st) {
     size_t smem = ((size_t)RC * (NT * 32 + 4) + (size_t)RC * kPW + (size_t)RC * HQ) * sizeof(float);
-    if (smem > 160 * 1024) return (int)hipErrorInvalidValue;
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&cin_filter_grad_kernel<D, NT, QI, RC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
     const int exc = RC / D;
     int ex_per_split = cdiv(cdiv(B, S), exc) * exc;
     dim3 grid(cdiv(HP * HQ, 128), S, cdiv(C, NT * 32));
-    hipLaunchKernelGGL((cin_filter_grad_kernel<D, NT, QI, RC>), grid, dim3(kThreads), smem, st, P, Q, G, (unsigned)B,
-                       (unsigned)HP, (unsigned)HQ, (unsigned)C, (unsigned)ex_per_split, partials);
+    RECALGO_CHECK(launch_lds<cin_filter_grad_kernel<D, NT, QI, RC>>(grid, dim3(kThreads), smem, st, P, Q, G, (unsigned)B,
+            (unsigned)HP, (unsigned)HQ, (unsigned)C, (unsigned)ex_per_split, partials));
     return (int)hipGetLastError();
 }
 template <int D, int NT>
@@ -1248,7 +1230,7 @@ RECALGO_EXPORT int recalgo_cin_layer_bwd(const float* x0, const float* xk, const
     }
     const unsigned wn = (unsigned)Hk * m * N;
     int rc;
-    if (m <= 32 && dxk != nullptr && D == 16 && N == 128 && (reinterpret_cast<uintptr_t>(filters) & 15) == 0) {
+    if (m <= 32 && dxk != nullptr && D == 16 && N == 128 && aligned16(filters)) {
         // fused, round-5 form: row blocks of 32 i (cin_input_grad2_kernel)
         const dim3 grid(cdiv((int64_t)B * D, kTM));
         if (Hk > 32) hipLaunchKernelGGL((cin_input_grad2_kernel<2>), grid, dim3(kThreads), 0, st, x0, xk, filters, G, (unsigned)B,
@@ -1280,8 +1262,7 @@ RECALGO_EXPORT int recalgo_cin_layer_bwd(const float* x0, const float* xk, const
     // dW
     const int S = filter_grad_splits(B, D, Hk * m, N, m);
     const int NT = cdiv(N, 32);
-    if (filter_grad2_ok(D, m, N) && (reinterpret_cast<uintptr_t>(G) & 15) == 0 && (reinterpret_cast<uintptr_t>(x0) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(xk) & 15) == 0) {
+    if (filter_grad2_ok(D, m, N) && aligned16(G, x0, xk)) {
         const int ex_per_split = cdiv(cdiv(B, S), 2) * 2;
         const dim3 grid(cdiv(Hk * m, 128), S);
         if (N == 128) hipLaunchKernelGGL((cin_filter_grad2_kernel<4>), grid, dim3(kThreads), 0, st, xk, x0, G, (unsigned)B, (unsigned)Hk,

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <mutex>
+
 #include "../../include/recalgo.h"
 
 #define RECALGO_EXPORT extern "C" __attribute__((visibility("default")))
@@ -19,9 +22,60 @@
         if (!(cond)) return (int)hipErrorInvalidValue; \
     } while (0)
 
+// Returns a failed hipError_t from the entry point (variadic: the expression may hold template argument lists).
+#define RECALGO_CHECK(...)                          \
+    do {                                            \
+        hipError_t e__ = (__VA_ARGS__);             \
+        if (e__ != hipSuccess) return (int)e__;     \
+    } while (0)
+
 static inline hipStream_t as_stream(recalgo_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+
+__host__ __device__ __forceinline__ int round4(int v) { return (v + 3) & ~3; }
+
+// True when every pointer is 16-byte aligned (a null pointer counts as aligned).
+template <typename... P>
+static inline bool aligned16(const P*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & 15) == 0;
+}
+
+// ---- dynamic LDS ----------------------------------------------------------
+constexpr size_t kLdsDefault = 64 * 1024;   // dynamic LDS a kernel may claim without opting in
+constexpr size_t kLdsMax = 160 * 1024;      // LDS of a gfx950 workgroup
+
+// Launches Kernel with `lds` bytes of dynamic LDS: refuses more than kLdsMax, and above kLdsDefault raises the kernel's
+// hipFuncAttributeMaxDynamicSharedMemorySize first.  The attribute belongs to (kernel, device), so each instantiation keeps
+// the bytes it has been granted per device and calls the runtime only when a launch needs more (the lock keeps a smaller
+// request of another host thread from lowering the attribute below that mark).  A failed launch is left for
+// RECALGO_RETURN_LAST().
+template <auto Kernel>
+hipError_t grant_lds(size_t lds) {
+    constexpr int kDevices = 64;
+    static std::atomic<size_t> granted[kDevices] = {};
+    static std::mutex grow;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= kDevices) return hipErrorInvalidDevice;
+    if (lds <= granted[dev].load(std::memory_order_acquire)) return hipSuccess;
+    std::lock_guard<std::mutex> lock(grow);
+    if (lds <= granted[dev].load(std::memory_order_relaxed)) return hipSuccess;
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) granted[dev].store(lds, std::memory_order_release);
+    return e;
+}
+template <auto Kernel, typename... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    if (lds > kLdsMax) return hipErrorInvalidValue;
+    if (lds > kLdsDefault) {
+        const hipError_t e = grant_lds<Kernel>(lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return hipSuccess;
+}
 
 // ---- wave64 helpers -------------------------------------------------------
 // Sum over all 64 lanes, result in every lane.
@@ -41,6 +95,28 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// LDS written by some lanes of a wave, read by others of the same wave
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Four consecutive floats: one 16-byte access when VEC (p 16-byte aligned), four scalar ones otherwise.
+template <bool VEC>
+__device__ __forceinline__ float4 ld4(const float* p) {
+    if (VEC) return *reinterpret_cast<const float4*>(p);
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+template <bool VEC>
+__device__ __forceinline__ void st4(float* p, float4 v) {
+    if (VEC) {
+        *reinterpret_cast<float4*>(p) = v;
+    } else {
+        p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
+    }
 }
 
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }

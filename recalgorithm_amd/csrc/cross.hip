@@ -334,7 +334,7 @@ RECALGO_EXPORT int recalgo_gather_cross_fwd(const int64_t* ids, const float* are
     RECALGO_REQUIRE(B >= 0 && F >= 1 && K >= 4 && K % 4 == 0 && d <= 1024 && L >= 1 && L <= 6);
     RECALGO_REQUIRE(ids != nullptr && arena != nullptr && row_base != nullptr && x0 != nullptr && out != nullptr);
     RECALGO_REQUIRE(x_stride % 4 == 0 && out_stride % 4 == 0 && x_stride >= d && out_stride >= d);
-    RECALGO_REQUIRE((reinterpret_cast<uintptr_t>(arena) & 15) == 0 && (reinterpret_cast<uintptr_t>(x0) & 15) == 0);
+    RECALGO_REQUIRE(aligned16(arena, x0));
     if (B == 0) return 0;
     const GatherSrc gs{ids, reinterpret_cast<const float4*>(arena), row_base, (unsigned)F, (unsigned)(K / 4)};
     return dispatch_stack(L, true, x0, x_stride, w, b, nullptr, 0, nullptr, B, d, out, out_stride, nullptr, nullptr, nullptr,

@@ -821,7 +821,6 @@ __global__ __launch_bounds__(256) void dense_sum_slabs_kernel(SplitJobs J) {
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int vec_ok(const float* p, int ld) { return (aligned16(p) && ld % 4 == 0) ? 1 : 0; }
 // rows x cols: the extent of the matrix in memory (row-major, leading dimension ld)
 inline Operand operand(const float* p, const float* mask, int ld, int64_t rows, int64_t cols) {
@@ -1083,7 +1082,7 @@ RECALGO_EXPORT int recalgo_dense_bwd_rider(const float* x, int ldx, const float*
     if (c_x0 != nullptr) {
         RECALGO_REQUIRE(recalgo_dense_bwd_cross_rider_supported(c_d, c_L) && c_w && c_b && c_g && c_dx0 && c_workspace);
         RECALGO_REQUIRE(c_x_stride % 4 == 0 && c_g_stride % 4 == 0 && c_x_stride >= c_d && c_g_stride >= c_d);
-        RECALGO_REQUIRE(aligned16(c_x0) && aligned16(c_w) && aligned16(c_b) && aligned16(c_g) && aligned16(c_dx0));
+        RECALGO_REQUIRE(aligned16(c_x0, c_w, c_b, c_g, c_dx0));
         C = CrossRider{c_x0, reinterpret_cast<const float4*>(c_w), reinterpret_cast<const float4*>(c_b), c_g, c_dx0,
                        static_cast<float*>(c_workspace), (unsigned)c_x_stride, (unsigned)c_g_stride, (unsigned)M, (unsigned)(c_d / 4),
                        (unsigned)cross_rider_blocks(M)};

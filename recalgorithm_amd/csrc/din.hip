@@ -1182,25 +1182,15 @@ RECALGO_EXPORT int recalgo_din_attention_fwd(const float* query, const float* ke
     RECALGO_REQUIRE(B >= 0 && T >= 1 && T <= 64 && (H == 4 || H == 8 || H == 16));
     if (B == 0) return 0;
     hipStream_t st = as_stream(stream);
-    if (H == 16 && (reinterpret_cast<uintptr_t>(query) & 15) == 0 && (reinterpret_cast<uintptr_t>(keys) & 15) == 0 &&
-        (reinterpret_cast<uintptr_t>(out) & 15) == 0) {
-        const size_t smem = din16::fwd_smem_bytes();
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&din16::fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(din16::fwd_kernel, dim3(din16::fwd_grid(B)), dim3(kThreads), smem, st, query, keys, keys_length, f1_w, f1_b, f2_w, f2_b,
-                           f3_w, f3_b, (unsigned)B, (unsigned)T, is_softmax, out);
+    if (H == 16 && aligned16(query, keys, out)) {
+        RECALGO_CHECK(launch_lds<din16::fwd_kernel>(dim3(din16::fwd_grid(B)), dim3(kThreads), din16::fwd_smem_bytes(), st,
+                query, keys, keys_length, f1_w, f1_b, f2_w, f2_b, f3_w, f3_b, (unsigned)B, (unsigned)T, is_softmax, out));
         RECALGO_RETURN_LAST();
     }
-#define LAUNCH(HH)                                                                                          \
-    do {                                                                                                    \
-        size_t smem = din_smem<HH>();                                                                       \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&din_attention_fwd_kernel<HH>),    \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);          \
-        if (e != hipSuccess) return (int)e;                                                                 \
-        hipLaunchKernelGGL(din_attention_fwd_kernel<HH>, dim3(din_grid(B)), dim3(kThreads), smem, st, query, keys, \
-                           keys_length, f1_w, f1_b, f2_w, f2_b, f3_w, f3_b, (unsigned)B, (unsigned)T, is_softmax,  \
-                           out);                                                                            \
-    } while (0)
+#define LAUNCH(HH)                                                                                                       \
+    RECALGO_CHECK(launch_lds<din_attention_fwd_kernel<HH>>(dim3(din_grid(B)), dim3(kThreads), din_smem<HH>(), st, query, keys, \
+                                                           keys_length, f1_w, f1_b, f2_w, f2_b, f3_w, f3_b, (unsigned)B,       \
+                                                           (unsigned)T, is_softmax, out))
     if (H == 4) LAUNCH(4); else if (H == 8) LAUNCH(8); else LAUNCH(16);
 #undef LAUNCH
     RECALGO_RETURN_LAST();
@@ -1238,33 +1228,29 @@ RECALGO_EXPORT int recalgo_din_attention_bwd_joined(const float* query, const fl
                                                     float* d_f1_b, float* d_f2_w, float* d_f2_b, float* d_f3_w, float* d_f3_b,
                                                     void* workspace, recalgo_stream_t stream) {
     RECALGO_REQUIRE(B > 0 && T >= 1 && T <= 64 && (H == 4 || H == 8 || H == 16) && workspace != nullptr);
-    RECALGO_REQUIRE(g_out != nullptr && ldg >= H && ldg % 4 == 0 && (reinterpret_cast<uintptr_t>(g_out) & 15) == 0);
+    RECALGO_REQUIRE(g_out != nullptr && ldg >= H && ldg % 4 == 0 && aligned16(g_out));
     RECALGO_REQUIRE(dq_extra == nullptr || ld_extra >= H);
     hipStream_t st = as_stream(stream);
     float* partials = static_cast<float*>(workspace);
     const int grid = din_grid(B);
     int pf;
-#define LAUNCH(HH)                                                                                            \
-    do {                                                                                                      \
-        pf = din_partial_floats<HH>();                                                                        \
-        size_t smem = din_smem<HH>();                                                                     \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&din_attention_bwd_kernel<HH>),      \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);            \
-        if (e != hipSuccess) return (int)e;                                                                   \
-        hipLaunchKernelGGL(din_attention_bwd_kernel<HH>, dim3(grid), dim3(kThreads), smem, st, query, keys,   \
-                           keys_length, f1_w, f1_b, f2_w, f2_b, f3_w, f3_b, g_out, (unsigned)ldg, dq_extra,       \
-                           (unsigned)ld_extra, (unsigned)B, (unsigned)T, is_softmax, dquery, dkeys, partials);    \
+#define LAUNCH(HH)                                                                                                    \
+    do {                                                                                                              \
+        pf = din_partial_floats<HH>();                                                                                \
+        RECALGO_CHECK(launch_lds<din_attention_bwd_kernel<HH>>(                                                       \
+            dim3(grid), dim3(kThreads), din_smem<HH>(), st, query, keys, keys_length, f1_w, f1_b, f2_w, f2_b, f3_w,   \
+            f3_b, g_out, (unsigned)ldg, dq_extra, (unsigned)ld_extra, (unsigned)B, (unsigned)T, is_softmax, dquery,   \
+            dkeys, partials));                                                                                        \
     } while (0)
-    const bool v16 = H == 16 && (reinterpret_cast<uintptr_t>(query) & 15) == 0 && (reinterpret_cast<uintptr_t>(keys) & 15) == 0 &&
-                     (reinterpret_cast<uintptr_t>(dquery) & 15) == 0 && (reinterpret_cast<uintptr_t>(dkeys) & 15) == 0;
+    const bool v16 = H == 16 && aligned16(query, keys, dquery, dkeys);
     if (v16) {
         pf = din_partial_floats<16>();
-        const size_t smem = din16::smem_bytes();
-        auto kern = is_softmax ? &din16::bwd_kernel<true> : &din16::bwd_kernel<false>;
-        hipError_t e16 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e16 != hipSuccess) return (int)e16;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), smem, st, query, keys, keys_length, f1_w, f1_b, f2_w, f2_b, f3_w,
-                           f3_b, g_out, (unsigned)ldg, dq_extra, (unsigned)ld_extra, (unsigned)B, (unsigned)T, dquery, dkeys, partials);
+#define LAUNCH16(SOFTMAX)                                                                                                \
+    launch_lds<din16::bwd_kernel<SOFTMAX>>(dim3(grid), dim3(kThreads), din16::smem_bytes(), st, query, keys, keys_length,    \
+                                           f1_w, f1_b, f2_w, f2_b, f3_w, f3_b, g_out, (unsigned)ldg, dq_extra,               \
+                                           (unsigned)ld_extra, (unsigned)B, (unsigned)T, dquery, dkeys, partials)
+        RECALGO_CHECK(is_softmax ? LAUNCH16(true) : LAUNCH16(false));
+#undef LAUNCH16
     } else if (H == 4) LAUNCH(4); else if (H == 8) LAUNCH(8); else LAUNCH(16);
 #undef LAUNCH
     hipError_t e = hipGetLastError();

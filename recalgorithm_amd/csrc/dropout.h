@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "common.h"
+
 namespace recalgo_drop {
 
 struct Spec {
@@ -40,7 +42,7 @@ inline Spec from_abi(const T* d) {
 }
 template <class T>
 inline bool abi_ok(const T* d) {
-    return d == nullptr || (d->rate > 0.0 && d->rate < 1.0 && (reinterpret_cast<uintptr_t>(d->keep_mask) & 15) == 0);
+    return d == nullptr || (d->rate > 0.0 && d->rate < 1.0 && aligned16(d->keep_mask));
 }
 
 struct Key {

@@ -29,8 +29,7 @@ __global__ __launch_bounds__(256) void dropout_mask_kernel(int64_t n, recalgo_dr
 
 inline bool spec_ok(double rate, const float* x, const float* mask, int64_t n) {
     // float4 paths: base pointers 16-byte aligned (every tensor of the library is); 32-bit element index
-    return rate > 0.0 && rate < 1.0 && n >= 0 && n < (int64_t)1 << 32 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(mask) & 15) == 0;
+    return rate > 0.0 && rate < 1.0 && n >= 0 && n < (int64_t)1 << 32 && aligned16(x, mask);
 }
 inline recalgo_drop::Spec make_spec(double rate, const float* mask, unsigned seed, unsigned call, const int64_t* step) {
     recalgo_drop::Spec s;
@@ -48,7 +47,7 @@ inline unsigned blocks_for(int64_t n) {
 
 RECALGO_EXPORT int recalgo_dropout_fwd(const float* x, int64_t n, double rate, const float* keep_mask, unsigned seed, unsigned call,
                                        const int64_t* step, float* y, recalgo_stream_t stream) {
-    RECALGO_REQUIRE(spec_ok(rate, x, keep_mask, n) && (reinterpret_cast<uintptr_t>(y) & 15) == 0);
+    RECALGO_REQUIRE(spec_ok(rate, x, keep_mask, n) && aligned16(y));
     if (n == 0) return 0;
     hipLaunchKernelGGL(dropout_kernel, dim3(blocks_for(n)), dim3(256), 0, as_stream(stream), x, n,
                        make_spec(rate, keep_mask, seed, call, step), y);

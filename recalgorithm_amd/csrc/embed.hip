@@ -559,16 +559,8 @@ inline size_t agg_smem(int W, unsigned ex) {
 // examples per workgroup of a scatter kernel
 inline unsigned scatter_tile(unsigned dflt) { return dflt; }
 
-// dynamic LDS above 64 KiB must be opted into per kernel
-#define ENSURE_SMEM(kern, bytes)                                                                       \
-    do {                                                                                               \
-        if ((bytes) > 64 * 1024) {                                                                     \
-            hipError_t e__ = hipFuncSetAttribute(reinterpret_cast<const void*>(&kern),                 \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
-            if (e__ != hipSuccess) return (int)e__;                                                    \
-        }                                                                                              \
-    } while (0)
-
+// launch_lds's kLdsMax refusal is unreachable in this file: the entries require K <= 64, so the most one asks for is
+// agg_smem(65, 256) = 139,280 B.
 inline Live to_live(const recalgo_live_t* l) {
     if (l == nullptr || l->row_live == nullptr) return Live{nullptr, nullptr, nullptr, 0};
     return Live{reinterpret_cast<unsigned*>(l->row_live), l->live_list, l->live_count, (long long)l->row_offset};
@@ -635,15 +627,12 @@ RECALGO_EXPORT int recalgo_embedding_gather_bwd(const int64_t* ids, const float*
     dim3 grid(cdiv(F, kFieldsPerWG), cdiv(B, ex));
     const size_t smem = agg_smem(K, ex * kFieldsPerWG);
     if (vec == 4) {
-        ENSURE_SMEM(gather_bwd_kernel<4>, smem);
-        hipLaunchKernelGGL(gather_bwd_kernel<4>, grid, dim3(kThreads), smem, as_stream(stream), ids, g,
-                           row_base, (unsigned)B, (unsigned)F, (unsigned)(K / 4), (unsigned)g_stride,
-                           (unsigned)g_col, grad_arena, ex, to_live(live));
+        RECALGO_CHECK(launch_lds<gather_bwd_kernel<4>>(grid, dim3(kThreads), smem, as_stream(stream), ids, g, row_base,
+                (unsigned)B, (unsigned)F, (unsigned)(K / 4), (unsigned)g_stride, (unsigned)g_col, grad_arena, ex,
+                to_live(live)));
     } else {
-        ENSURE_SMEM(gather_bwd_kernel<1>, smem);
-        hipLaunchKernelGGL(gather_bwd_kernel<1>, grid, dim3(kThreads), smem, as_stream(stream), ids, g,
-                           row_base, (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)g_stride,
-                           (unsigned)g_col, grad_arena, ex, to_live(live));
+        RECALGO_CHECK(launch_lds<gather_bwd_kernel<1>>(grid, dim3(kThreads), smem, as_stream(stream), ids, g, row_base,
+                (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)g_stride, (unsigned)g_col, grad_arena, ex, to_live(live)));
     }
     RECALGO_RETURN_LAST();
 }
@@ -678,15 +667,13 @@ RECALGO_EXPORT int recalgo_embedding_bag_mean_bwd(const int64_t* values, const i
     const int vec = vec_of(K, g_stride, g_col);
     const unsigned ex = scatter_tile(256);
     if (vec == 4) {
-        ENSURE_SMEM(bag_mean_bwd_kernel<4>, agg_smem(K, ex));
-        hipLaunchKernelGGL(bag_mean_bwd_kernel<4>, dim3(cdiv(B, ex)), dim3(kThreads), agg_smem(K, ex),
-                           as_stream(stream), values, offsets, g, (unsigned)B, (unsigned)(K / 4),
-                           (unsigned)g_stride, (unsigned)g_col, grad_table, ex, to_live(live));
+        RECALGO_CHECK(launch_lds<bag_mean_bwd_kernel<4>>(dim3(cdiv(B, ex)), dim3(kThreads), agg_smem(K, ex), as_stream(stream),
+                values, offsets, g, (unsigned)B, (unsigned)(K / 4), (unsigned)g_stride, (unsigned)g_col, grad_table, ex,
+                to_live(live)));
     } else {
-        ENSURE_SMEM(bag_mean_bwd_kernel<1>, agg_smem(K, ex));
-        hipLaunchKernelGGL(bag_mean_bwd_kernel<1>, dim3(cdiv(B, ex)), dim3(kThreads), agg_smem(K, ex),
-                           as_stream(stream), values, offsets, g, (unsigned)B, (unsigned)K,
-                           (unsigned)g_stride, (unsigned)g_col, grad_table, ex, to_live(live));
+        RECALGO_CHECK(launch_lds<bag_mean_bwd_kernel<1>>(dim3(cdiv(B, ex)), dim3(kThreads), agg_smem(K, ex), as_stream(stream),
+                values, offsets, g, (unsigned)B, (unsigned)K, (unsigned)g_stride, (unsigned)g_col, grad_table, ex,
+                to_live(live)));
     }
     RECALGO_RETURN_LAST();
 }
@@ -760,15 +747,12 @@ RECALGO_EXPORT int recalgo_sequence_gather_bwd(const int64_t* values, const int6
     if (BT == 0) return 0;
     const unsigned ex = scatter_tile(256);     // history ids repeat across the batch: big tiles combine more
     if (K % 4 == 0) {
-        ENSURE_SMEM(seq_gather_bwd_kernel<4>, agg_smem(K, ex));
-        hipLaunchKernelGGL(seq_gather_bwd_kernel<4>, dim3(cdiv(BT, ex)), dim3(kThreads), agg_smem(K, ex),
-                           as_stream(stream), values, offsets, g, (unsigned)BT, (unsigned)T, (unsigned)(K / 4),
-                           grad_table, ex, to_live(live));
+        RECALGO_CHECK(launch_lds<seq_gather_bwd_kernel<4>>(dim3(cdiv(BT, ex)), dim3(kThreads), agg_smem(K, ex),
+                as_stream(stream), values, offsets, g, (unsigned)BT, (unsigned)T, (unsigned)(K / 4), grad_table, ex,
+                to_live(live)));
     } else {
-        ENSURE_SMEM(seq_gather_bwd_kernel<1>, agg_smem(K, ex));
-        hipLaunchKernelGGL(seq_gather_bwd_kernel<1>, dim3(cdiv(BT, ex)), dim3(kThreads), agg_smem(K, ex),
-                           as_stream(stream), values, offsets, g, (unsigned)BT, (unsigned)T, (unsigned)K,
-                           grad_table, ex, to_live(live));
+        RECALGO_CHECK(launch_lds<seq_gather_bwd_kernel<1>>(dim3(cdiv(BT, ex)), dim3(kThreads), agg_smem(K, ex),
+                as_stream(stream), values, offsets, g, (unsigned)BT, (unsigned)T, (unsigned)K, grad_table, ex, to_live(live)));
     }
     RECALGO_RETURN_LAST();
 }
@@ -796,7 +780,7 @@ RECALGO_EXPORT int recalgo_deepfm_sparse_fwd_deferred(const int64_t* ids, const 
     RECALGO_REQUIRE(B >= 0 && F > 0 && K > 0 && K % 4 == 0 && K <= 64 && field_sum != nullptr);
     if (B == 0) return 0;
     size_t smem = (size_t)kDeepfmEB * (F * K + 16 + F) * sizeof(float);
-    RECALGO_REQUIRE(smem <= 64 * 1024);
+    RECALGO_REQUIRE(smem <= kLdsDefault);
     hipLaunchKernelGGL(deepfm_sparse_fwd_kernel<kDeepfmEB>, dim3(cdiv(B, kDeepfmEB)),
                        dim3(kThreads), smem, as_stream(stream), ids,
                        reinterpret_cast<const float4*>(arena), w1, bias, row_base, (unsigned)B,
@@ -813,12 +797,10 @@ RECALGO_EXPORT int recalgo_deepfm_sparse_bwd(const int64_t* ids, const float* em
     RECALGO_REQUIRE(B >= 0 && F > 0 && K > 0 && K % 4 == 0 && K <= 64 && live_ok(live) && live_ok(live_w1));
     if (B == 0) return 0;
     const unsigned ex = scatter_tile(256);
-    ENSURE_SMEM(deepfm_sparse_bwd_kernel, agg_smem(K + 1, ex));
-    hipLaunchKernelGGL(deepfm_sparse_bwd_kernel, dim3(F, cdiv(B, ex)), dim3(kThreads), agg_smem(K + 1, ex),
-                       as_stream(stream), ids, reinterpret_cast<const float4*>(emb),
-                       reinterpret_cast<const float4*>(field_sum), reinterpret_cast<const float4*>(g_emb),
-                       g_fm1, g_fm2, row_base, (unsigned)B, (unsigned)F, (unsigned)(K / 4), grad_arena, grad_w1, ex, to_live(live),
-                       to_live(live_w1));
+    RECALGO_CHECK(launch_lds<deepfm_sparse_bwd_kernel>(dim3(F, cdiv(B, ex)), dim3(kThreads), agg_smem(K + 1, ex),
+            as_stream(stream), ids, reinterpret_cast<const float4*>(emb), reinterpret_cast<const float4*>(field_sum),
+            reinterpret_cast<const float4*>(g_emb), g_fm1, g_fm2, row_base, (unsigned)B, (unsigned)F, (unsigned)(K / 4),
+            grad_arena, grad_w1, ex, to_live(live), to_live(live_w1)));
     RECALGO_RETURN_LAST();
 }
 

@@ -738,22 +738,11 @@ inline BiWs bi_ws(int B, int F, int K, int nv, int type) {
     return w;
 }
 
-#define ENSURE_SMEM(kern, bytes)                                                                       \
-    do {                                                                                               \
-        if ((bytes) > 160 * 1024) return (int)hipErrorInvalidValue;                                    \
-        if ((bytes) > 64 * 1024) {                                                                     \
-            hipError_t e__ = hipFuncSetAttribute(reinterpret_cast<const void*>(&kern),                 \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
-            if (e__ != hipSuccess) return (int)e__;                                                    \
-        }                                                                                              \
-    } while (0)
-
 template <int K, int NV>
 int launch_bi_fwd(const BiSets& a, int B, int F, int type, float* out, int out_stride, int out_col, hipStream_t st) {
     const size_t smem = bi_smem(F, K, NV, type, false);
-    ENSURE_SMEM((bilinear_fwd_kernel<K, NV>), smem);
-    hipLaunchKernelGGL((bilinear_fwd_kernel<K, NV>), dim3(grid_for(B)), dim3(kThreads), smem, st, a, (unsigned)B,
-                       (unsigned)F, type, out, (unsigned)out_stride, (unsigned)out_col);
+    RECALGO_CHECK(launch_lds<bilinear_fwd_kernel<K, NV>>(dim3(grid_for(B)), dim3(kThreads), smem, st, a, (unsigned)B,
+            (unsigned)F, type, out, (unsigned)out_stride, (unsigned)out_col));
     return (int)hipGetLastError();
 }
 template <int K, int NV>
@@ -764,7 +753,7 @@ int launch_bi_bwd(const BiSets& a, int B, int F, int type, const float* g, int g
     const size_t shared = ((size_t)ptab_floats(P) + (type == kAll ? (size_t)NV * K * kWS(K) : 0)) * sizeof(float);
     const size_t base = (size_t)NV * 2 * ((size_t)F * K + (size_t)n * K) * sizeof(float);
     const size_t tile = (size_t)P * NV * K * sizeof(float);
-    const size_t budget = 160 * 1024;
+    const size_t budget = kLdsMax;
     int stage = 0, wpb = 0, wpb_budget_all = 1;
     if (type != kInteraction && shared + base + tile <= budget) {
         stage = 1;
@@ -780,18 +769,16 @@ int launch_bi_bwd(const BiSets& a, int B, int F, int type, const float* g, int g
     if (stage && K <= 32 && P <= (kCoopThreads / C4) * 10 && (unsigned)F * K / 4 <= (unsigned)kCoopThreads) {
         // a workgroup per example (COOP): as many workgroups per CU as the LDS holds, persistent over the batch
         const size_t smem1 = shared + base + tile;
-        ENSURE_SMEM((bilinear_bwd_kernel<K, NV, true>), smem1);
         int grid = 256 * wpb_budget_all;
         if (grid > B) grid = B;
-        hipLaunchKernelGGL((bilinear_bwd_kernel<K, NV, true>), dim3(grid), dim3(kCoopThreads), smem1, st, a, (unsigned)B,
-                           (unsigned)F, type, g, (unsigned)g_stride, (unsigned)g_col, dvw, 1);
+        RECALGO_CHECK(launch_lds<bilinear_bwd_kernel<K, NV, true>>(dim3(grid), dim3(kCoopThreads), smem1, st, a, (unsigned)B,
+                (unsigned)F, type, g, (unsigned)g_stride, (unsigned)g_col, dvw, 1));
         return (int)hipGetLastError();
     }
-    ENSURE_SMEM((bilinear_bwd_kernel<K, NV, false>), smem);
     int grid = cdiv(B, wpb);
     if (grid > kMaxBlocks) grid = kMaxBlocks;
-    hipLaunchKernelGGL((bilinear_bwd_kernel<K, NV, false>), dim3(grid), dim3(64 * wpb), smem, st, a, (unsigned)B,
-                       (unsigned)F, type, g, (unsigned)g_stride, (unsigned)g_col, dvw, stage);
+    RECALGO_CHECK(launch_lds<bilinear_bwd_kernel<K, NV, false>>(dim3(grid), dim3(64 * wpb), smem, st, a, (unsigned)B,
+            (unsigned)F, type, g, (unsigned)g_stride, (unsigned)g_col, dvw, stage));
     return (int)hipGetLastError();
 }
 template <int K>
@@ -823,9 +810,8 @@ RECALGO_EXPORT int recalgo_senet_fwd(const float* emb, const float* w1, const fl
     if (B == 0) return 0;
     const size_t smem = ((size_t)kWaves * ((2 * (size_t)F * K + 3 * F + 2 * reduction_dim + 3) & ~(size_t)3) +
                          2 * (size_t)F * reduction_dim) * sizeof(float);
-    ENSURE_SMEM(senet_fwd_kernel, smem);
-    hipLaunchKernelGGL(senet_fwd_kernel, dim3(grid_for(B)), dim3(kThreads), smem, as_stream(stream), emb, w1, w2,
-                       (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)reduction_dim, v_out, a_out);
+    RECALGO_CHECK(launch_lds<senet_fwd_kernel>(dim3(grid_for(B)), dim3(kThreads), smem, as_stream(stream), emb, w1, w2,
+            (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)reduction_dim, v_out, a_out));
     RECALGO_RETURN_LAST();
 }
 
@@ -841,13 +827,12 @@ RECALGO_EXPORT int recalgo_senet_bwd(const float* emb, const float* w1, const fl
     const unsigned WR = (unsigned)F * reduction_dim;
     const size_t smem = ((size_t)kWaves * ((2 * (size_t)F * K + 3 * F + 2 * reduction_dim + 3) & ~(size_t)3) +
                          (size_t)kWaves * 2 * WR + 2 * (size_t)WR) * sizeof(float);
-    ENSURE_SMEM(senet_bwd_kernel, smem);
     const int grid = grid_for(B);        // one partial row per workgroup; up to 1024 workgroups = 16 waves per CU in flight (256 left
                                          // one wave per SIMD walking its four examples' latency chains alone: 44 us)
     float* partials = static_cast<float*>(workspace);
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(senet_bwd_kernel, dim3(grid), dim3(kThreads), smem, st, emb, w1, w2, g_v, (unsigned)B,
-                       (unsigned)F, (unsigned)K, (unsigned)reduction_dim, d_emb, accumulate, partials);
+    RECALGO_CHECK(launch_lds<senet_bwd_kernel>(dim3(grid), dim3(kThreads), smem, st, emb, w1, w2, g_v, (unsigned)B, (unsigned)F,
+            (unsigned)K, (unsigned)reduction_dim, d_emb, accumulate, partials));
     launch_colsum16(partials, (unsigned)grid, 2 * WR, dw1, WR, dw2, st);
     RECALGO_RETURN_LAST();
 }

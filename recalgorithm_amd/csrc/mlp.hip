@@ -847,12 +847,7 @@ RECALGO_EXPORT int recalgo_logit_loss_fwd_bwd(const float* const* x_parts, const
     P.bias = bias; P.addend[0] = addend0; P.addend[1] = addend1; P.labels = labels; P.loss_addend = loss_addend; P.grad_scale = grad_scale;
     P.logit = logit; P.prob = prob; P.dlogit = dlogit; P.partials = partials; P.B = B;
     const size_t smem = (size_t)(kTailRows + 1) * P.C * sizeof(float);
-    RECALGO_REQUIRE(smem <= 150 * 1024);
-    if (smem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&logit_loss_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(logit_loss_kernel, dim3(cdiv(B, kTailRows)), dim3(256), smem, as_stream(stream), P);
+    RECALGO_REQUIRE(smem <= kLdsMax - 10 * 1024);        // (room for the kernel's static arrays)
+    RECALGO_CHECK(launch_lds<logit_loss_kernel>(dim3(cdiv(B, kTailRows)), dim3(256), smem, as_stream(stream), P));
     RECALGO_RETURN_LAST();
 }

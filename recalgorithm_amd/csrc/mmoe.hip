@@ -47,29 +47,6 @@ struct MixBwdPtrs {
     float* dex[kMixMax];
 };
 
-__host__ __device__ __forceinline__ int round4(int v) { return (v + 3) & ~3; }
-
-template <bool VEC>
-__device__ __forceinline__ float4 ld4(const float* p) {
-    if (VEC) return *reinterpret_cast<const float4*>(p);
-    return make_float4(p[0], p[1], p[2], p[3]);
-}
-template <bool VEC>
-__device__ __forceinline__ void st4(float* p, float4 v) {
-    if (VEC) {
-        *reinterpret_cast<float4*>(p) = v;
-    } else {
-        p[0] = v.x, p[1] = v.y, p[2] = v.z, p[3] = v.w;
-    }
-}
-
-// LDS written by some lanes of a wave, read by others of the same wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // gate kernels -> Ws[k * ldw + off_g + j], the tables -> tab = [n[16] | off[16] | sel[16 * 16]]
 __device__ __forceinline__ void stage_gates(const MixTables& T, int In, int G, int ldw, float* Ws, int* tab) {
     for (int g = 0; g < G; ++g) {
@@ -351,7 +328,7 @@ bool mix_tables(const float* const* gate_kernels, const int* n_sel, const int* s
     for (int e = 0; e < E; ++e) {
         if (experts[e] == nullptr) return false;
         T->ex[e] = experts[e];
-        vec = vec && (reinterpret_cast<uintptr_t>(experts[e]) & 15) == 0;
+        vec = vec && aligned16(experts[e]);
     }
     const int m = E > G ? E : G;
     S->NT = NT, S->emax = m <= 4 ? 4 : (m <= 8 ? 8 : 16), S->vec = vec;
@@ -396,7 +373,7 @@ RECALGO_EXPORT int recalgo_gate_mix_fwd(const float* x, int ldx, const float* co
         O.out[g] = g < G ? outs[g] : nullptr;
         if (g < G) {
             RECALGO_REQUIRE(outs[g] != nullptr);
-            S.vec = S.vec && (reinterpret_cast<uintptr_t>(outs[g]) & 15) == 0;
+            S.vec = S.vec && aligned16(outs[g]);
         }
     }
     const int want = cdiv(B, kMixRows);
@@ -422,7 +399,7 @@ RECALGO_EXPORT int recalgo_gate_mix_bwd(const float* x, int ldx, const float* co
     for (int i = 0; i < kMixMax; ++i) {
         P.dout[i] = i < G ? d_outs[i] : nullptr;
         P.dex[i] = (i < E && d_experts) ? d_experts[i] : nullptr;
-        S.vec = S.vec && (reinterpret_cast<uintptr_t>(P.dout[i]) & 15) == 0 && (reinterpret_cast<uintptr_t>(P.dex[i]) & 15) == 0;
+        S.vec = S.vec && aligned16(P.dout[i], P.dex[i]);
     }
     const dim3 grid(recalgo_gate_mix_partial_rows(B));
     const size_t smem = sizeof(float) * (2 * round4(In * (S.NT | 1)) + 2 * kMixMax + kMixMax * kMixMax +

@@ -315,16 +315,6 @@ inline int grid_for(int B) {
     return gblocks > kMaxBlocks ? kMaxBlocks : gblocks;
 }
 
-#define ENSURE_SMEM(kern, bytes)                                                                       \
-    do {                                                                                               \
-        if ((bytes) > 160 * 1024) return (int)hipErrorInvalidValue;                                    \
-        if ((bytes) > 64 * 1024) {                                                                     \
-            hipError_t e__ = hipFuncSetAttribute(reinterpret_cast<const void*>(&kern),                 \
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)); \
-            if (e__ != hipSuccess) return (int)e__;                                                    \
-        }                                                                                              \
-    } while (0)
-
 }  // namespace
 
 RECALGO_EXPORT int recalgo_pnn_feature_count(int F, int K, int method) {
@@ -343,15 +333,13 @@ RECALGO_EXPORT int recalgo_pnn_features_fwd(const float* emb, int B, int F, int 
     if (method == kIPNN) {
         const unsigned T = (unsigned)F * (F + 1) / 2;
         const size_t smem = ((size_t)tab_floats(T) + (size_t)kWaves * F * (K + 1)) * sizeof(float);
-        ENSURE_SMEM(ipnn_features_fwd_kernel, smem);
-        hipLaunchKernelGGL(ipnn_features_fwd_kernel, dim3(grid_for(B)), dim3(kThreads), smem, st, emb, (unsigned)B,
-                           (unsigned)F, (unsigned)K, phi, (unsigned)ld_phi);
+        RECALGO_CHECK(launch_lds<ipnn_features_fwd_kernel>(dim3(grid_for(B)), dim3(kThreads), smem, st, emb, (unsigned)B,
+                (unsigned)F, (unsigned)K, phi, (unsigned)ld_phi));
     } else {
         const unsigned T = (unsigned)K * (K + 1) / 2;
         const size_t smem = ((size_t)tab_floats(T) + (size_t)kWaves * K) * sizeof(float);
-        ENSURE_SMEM(opnn_features_fwd_kernel, smem);
-        hipLaunchKernelGGL(opnn_features_fwd_kernel, dim3(grid_for(B)), dim3(kThreads), smem, st, emb, (unsigned)B,
-                           (unsigned)F, (unsigned)K, phi, (unsigned)ld_phi, static_cast<float*>(nullptr));
+        RECALGO_CHECK(launch_lds<opnn_features_fwd_kernel>(dim3(grid_for(B)), dim3(kThreads), smem, st, emb, (unsigned)B,
+                (unsigned)F, (unsigned)K, phi, (unsigned)ld_phi, static_cast<float*>(nullptr)));
     }
     RECALGO_RETURN_LAST();
 }
@@ -366,23 +354,19 @@ RECALGO_EXPORT int recalgo_pnn_features_bwd(const float* emb, const float* dphi,
     if (method == kIPNN) {
         const unsigned T = (unsigned)F * (F + 1) / 2;
         const size_t smem4 = ((size_t)tab_floats(T) + (size_t)kWaves * ((size_t)F * K + (((size_t)F * F + 3) & ~(size_t)3))) * sizeof(float);
-        if (K % 4 == 0 && smem4 <= 160 * 1024 && (reinterpret_cast<uintptr_t>(emb) & 15) == 0 &&
-            (reinterpret_cast<uintptr_t>(d_emb) & 15) == 0) {
-            ENSURE_SMEM(ipnn_features_bwd4_kernel, smem4);
-            hipLaunchKernelGGL(ipnn_features_bwd4_kernel, dim3(grid_for(B)), dim3(kThreads), smem4, st, emb, dphi,
-                               (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate);
+        if (K % 4 == 0 && smem4 <= kLdsMax && aligned16(emb, d_emb)) {
+            RECALGO_CHECK(launch_lds<ipnn_features_bwd4_kernel>(dim3(grid_for(B)), dim3(kThreads), smem4, st, emb, dphi,
+                    (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate));
             RECALGO_RETURN_LAST();
         }
         const size_t smem = (size_t)kWaves * ((size_t)F * K + T) * sizeof(float);
-        ENSURE_SMEM(ipnn_features_bwd_kernel, smem);
-        hipLaunchKernelGGL(ipnn_features_bwd_kernel, dim3(grid_for(B)), dim3(kThreads), smem, st, emb, dphi,
-                           (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate);
+        RECALGO_CHECK(launch_lds<ipnn_features_bwd_kernel>(dim3(grid_for(B)), dim3(kThreads), smem, st, emb, dphi, (unsigned)B,
+                (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate));
     } else {
         const unsigned T = (unsigned)K * (K + 1) / 2;
         const size_t smem = (size_t)kWaves * (2 * (size_t)K + T) * sizeof(float);
-        ENSURE_SMEM(opnn_features_bwd_kernel, smem);
-        hipLaunchKernelGGL(opnn_features_bwd_kernel, dim3(grid_for(B)), dim3(kThreads), smem, st, emb, dphi,
-                           (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate);
+        RECALGO_CHECK(launch_lds<opnn_features_bwd_kernel>(dim3(grid_for(B)), dim3(kThreads), smem, st, emb, dphi, (unsigned)B,
+                (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate));
     }
     RECALGO_RETURN_LAST();
 }

@@ -178,7 +178,7 @@ RECALGO_EXPORT int recalgo_attention_pool_bwd(const float* pairs, const float* s
     unsigned KL = 1;
     while ((int)KL < K) KL <<= 1;
     const size_t smem = (size_t)4 * P * sizeof(float);
-    RECALGO_REQUIRE(smem <= 64 * 1024);
+    RECALGO_REQUIRE(smem <= kLdsDefault);
     hipLaunchKernelGGL(attn_pool_bwd_kernel, dim3(cdiv(B, 4)), dim3(256), smem, as_stream(stream), pairs, score, g, (unsigned)B,
                        (unsigned)P, (unsigned)K, KL, d_pairs, d_att);
     RECALGO_RETURN_LAST();

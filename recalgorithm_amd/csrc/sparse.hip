@@ -1313,7 +1313,6 @@ __global__ __launch_bounds__(kThreads) void sparse_sweep_kernel(SweepArgs A) {
 
 // ---- host helpers -----------------------------------------------------------------------------
 struct Geometry { int vec; unsigned KV, L, G; };
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool geometry(int K, const recalgo_scatter_source_t* src, int n_src, Geometry* G) {
     if (K < 1 || K > 256) return false;
     bool v4 = (K & 3) == 0 && K / 4 <= 64;
@@ -1595,18 +1594,9 @@ RECALGO_EXPORT int recalgo_scatter_apply(const recalgo_scatter_source_t* sources
     P.stage_ok = (size_t)K * kThreads * sizeof(float) <= 32 * 1024;      // (K <= 32: every model of the reference)
     const size_t smem = ((prescanned ? 0 : (size_t)nb) + 8 * kThreads + 8 + 16 + kSlots * 10) * sizeof(unsigned) + kThreads * 4 * sizeof(float) +
                         kMaxSources * sizeof(SrcDev) + (P.stage_ok ? (size_t)(K + 1) * kThreads * sizeof(float) : 0);
-    if (smem > 64 * 1024) {
-        hipError_t e = G.vec == 4 ? hipFuncSetAttribute(reinterpret_cast<const void*>(&sparse_place_kernel<4>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)
-                                  : hipFuncSetAttribute(reinterpret_cast<const void*>(&sparse_place_kernel<1>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return (int)e;
-    }
     const unsigned place_blocks = W ? W : 1;                  // (the scan of all-zero totals still publishes offs[])
-    if (G.vec == 4)
-        hipLaunchKernelGGL(sparse_place_kernel<4>, dim3(place_blocks), dim3(kThreads), smem, st, P);
-    else
-        hipLaunchKernelGGL(sparse_place_kernel<1>, dim3(place_blocks), dim3(kThreads), smem, st, P);
+    RECALGO_CHECK(G.vec == 4 ? launch_lds<sparse_place_kernel<4>>(dim3(place_blocks), dim3(kThreads), smem, st, P)
+                             : launch_lds<sparse_place_kernel<1>>(dim3(place_blocks), dim3(kThreads), smem, st, P));
     ApplyArgs A;
     for (int i = 0; i < kMaxSources; ++i) A.src[i] = P.src[i];
     A.n_src = n_sources;

@@ -342,11 +342,7 @@ inline size_t tail_smem(int K2, int Cs) {
 
 template <int KC>
 int launch_tail(const TailFuseArgs& P, int Cs, hipStream_t s) {
-    const size_t smem = tail_smem(128 * KC, Cs);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tail_dense_head_kernel<KC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(tail_dense_head_kernel<KC>, dim3(cdiv(P.B, kTR)), dim3(kThreads), smem, s, P);
+    RECALGO_CHECK(launch_lds<tail_dense_head_kernel<KC>>(dim3(cdiv(P.B, kTR)), dim3(kThreads), tail_smem(128 * KC, Cs), s, P));
     RECALGO_RETURN_LAST();
 }
 
@@ -366,8 +362,7 @@ RECALGO_EXPORT int recalgo_tail_dense_head_fwd_bwd(const float* h2, int K2, cons
     RECALGO_REQUIRE(recalgo_tail_dense_head_supported(K2, N3, Cs) && B > 0);
     RECALGO_REQUIRE(h2 && w3 && b3 && w_h3 && labels && logit && prob && dlogit && dz3 && dh2 && partials);
     RECALGO_REQUIRE(Cs == 0 || (side && w_side));
-    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    RECALGO_REQUIRE(al(h2) && al(w3) && al(side) && al(d_side));
+    RECALGO_REQUIRE(aligned16(h2, w3, side, d_side));
     TailFuseArgs P;
     P.h2 = h2; P.w3 = w3; P.b3 = b3; P.side = Cs ? side : nullptr; P.w_side = w_side; P.w_h3 = w_h3; P.head_bias = head_bias;
     P.labels = labels; P.loss_addend = loss_addend; P.logit = logit; P.prob = prob; P.dlogit = dlogit; P.d_side = d_side;

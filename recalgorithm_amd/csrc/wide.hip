@@ -170,7 +170,6 @@ __global__ __launch_bounds__(kThreads) void wide_reset_kernel(WideWs w, int32_t*
     if (r < w.hdr[0]) count[w.bucket[r]] = 0;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

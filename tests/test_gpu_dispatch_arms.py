@@ -23,13 +23,19 @@ aligned) allocations at the reference's shapes, which always lands on the fast a
                                                B = 0                                               test_concat_sumsq_empty_batch
  8  din_sum_partials_kernel vs colsum16        the six DIN weight gradients separate buffers vs    test_din_generic_arm (flat_grads)
                                                one flat buffer in the partial row's order
- 9  LDS ceilings (ENSURE_SMEM)                 pnn: IPNN F = 255 (the largest accepted) at K = 16;  test_ipnn_lds_ceiling,
+ 9  LDS ceilings (launch_lds)                  pnn: IPNN F = 255 (the largest accepted) at K = 16;  test_ipnn_lds_ceiling,
                                                fibinet: bilinear F = 128 (the largest accepted)    test_bilinear_lds_ceiling
+10  launch_lds's dynamic-LDS grant, kept per   bag_mean_bwd_kernel<4> at K = 32, 16, 64 in a fresh    test_lds_grant_grows,
+    (kernel, device) as a high-water mark      process: 70 KiB granted, 38 KiB below the default,    test_lds_grant_second_device
+                                               134 KiB above the grant; K = 64 on device 0, then 1
 
 Each arm is compared with a float64 restatement (oracle.ref_ops, or a plain formula with its reference line) under the
 strict `ref32` guard of tests/util.py; where a fast arm exists for the same arguments, the same inputs also run through it.
 The two arms are not required to agree bit for bit: their summation orders differ."""
 import ctypes
+import os
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -40,6 +46,8 @@ from recalgorithm_amd.variables import Variable, VariableStore
 from tests.util import assert_bit_exact, assert_close
 
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _p(t):
@@ -297,6 +305,54 @@ def test_bilinear_lds_ceiling(dev):
         _lib.check(lib.recalgo_bilinear_fwd(_p(x64), _p(w64), _p(x64), _p(w64), B, F, 64, 0, _p(big), 128, 0, _st()), "fwd")
     torch.cuda.synchronize()
     assert bool((big == 7.0).all())
+
+
+# ---- row 10: the dynamic-LDS grant of csrc/common.h's launch_lds --------------------------------------------------------
+def _bag_mean_bwd_check(dev, K):
+    """recalgo_embedding_bag_mean_bwd at B = 8 (bags of one to three ids, a table of 16 rows; agg_smem(K, 256) bytes of
+    dynamic LDS whatever B is) against the float64 scatter-mean gradient: d table[id] += g[b] / len(bag b)."""
+    lib = _lib.load()
+    B, rows = 8, 16
+    gen = torch.Generator().manual_seed(K)
+    lens = torch.randint(1, 4, (B,), generator=gen)
+    offsets = torch.zeros(B + 1, dtype=torch.int64)
+    offsets[1:] = lens.cumsum(0)
+    values = torch.randint(0, rows, (int(offsets[-1]),), generator=gen)
+    g = torch.randn(B, K, generator=gen)
+    bag = torch.repeat_interleave(torch.arange(B), lens)
+    ref = torch.zeros(rows, K, dtype=torch.float64).index_add(0, values, (g.double() / lens.double().unsqueeze(1))[bag])
+    ref32 = torch.zeros(rows, K).index_add(0, values, (g / lens.float().unsqueeze(1))[bag])
+    with torch.cuda.device(dev):
+        vd, od, gd = values.to(dev), offsets.to(dev), g.to(dev)
+        grad = torch.zeros(rows, K, device=dev)
+        _lib.check(lib.recalgo_embedding_bag_mean_bwd(_p(vd), _p(od), _p(gd), B, K, K, 0, _p(grad), None, _st()),
+                   f"bag mean bwd K={K} on {dev}")
+        assert_close(grad, ref, what=f"bag mean bwd K={K} on {dev}", reduced=True, ref32=ref32)
+
+
+def _lds_grant_sequence():
+    """(the child process of test_lds_grant_grows)"""
+    for K in (32, 16, 64):
+        _bag_mean_bwd_check(torch.device("cuda:0"), K)
+    print("lds grant sequence passed")
+
+
+def test_lds_grant_grows(dev):
+    """bag_mean_bwd_kernel<4> at K = 32 (71,696 B: the first grant), K = 16 (38,928 B: below the default allowance, no
+    grant) and K = 64 (137,232 B: above what was granted): a grant that is not raised again fails the third launch.  In a
+    fresh process, so that no earlier test has launched the kernel at K = 64."""
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    code = "from tests.test_gpu_dispatch_arms import _lds_grant_sequence; _lds_grant_sequence()"
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "lds grant sequence passed" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+def test_lds_grant_second_device(dev):
+    """The grant belongs to (kernel, device): K = 64 on device 0, then on device 1."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    for d in (0, 1):
+        _bag_mean_bwd_check(torch.device(f"cuda:{d}"), 64)
 
 
 # ---- rows 4, 5, 6: CIN ----------------------------------------------------------------------------------------------------

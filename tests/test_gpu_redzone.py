@@ -45,6 +45,8 @@ MODULES = [test_gpu_dense, test_gpu_kernels, test_gpu_tailfuse, test_gpu_dropout
 LEFT_OUT = {
     "test_gpu_kernels.test_cpu_tensor_is_rejected": "no device work: the call is refused on the host",
     "test_gpu_dispatch_arms.test_concat_sumsq_ticket_graph_replay": "captures a hipGraph",
+    "test_gpu_dispatch_arms.test_lds_grant_grows": "a child process",
+    "test_gpu_dispatch_arms.test_lds_grant_second_device": "needs a second device: skips on a machine with one",
     "test_gpu_mmoe.test_gate_mix_is_deterministic_and_capturable": "captures a hipGraph",
     "test_gpu_mmoe.test_model_golden": "model level: whole Estimator steps",
     "test_gpu_mmoe.test_default_configuration_step_against_float64": "model level: whole Estimator steps",
