@@ -614,6 +614,10 @@ int recalgo_tail_dense_head_fwd_bwd(const float* h2, int K2, const float* w3, co
  *   from lr_t_dev[0] when lr_t_dev != NULL (see recalgo_adam_tf1_advance).
  *   zero_grad != 0: g is reset to 0 after use (only non-zero words are rewritten).
  * n % 4 == 0 not required.
+ * Alignment (every Adam entry of this section; anything else is refused with hipErrorInvalidValue): p, g, m and v are
+ * 16-byte aligned wherever the width is a multiple of 4 (the dense buffer always) - recalgo_adam_tf1_dense and
+ * _rows always, recalgo_adam_tf1_list for K in {4,8,16,32,64}, recalgo_adam_tf1_step[_plans] for the dense buffer
+ * and for every arena with K % 4 == 0.  Arenas of any other width are walked one float at a time from any base.
  * ------------------------------------------------------------------------------------------ */
 int recalgo_adam_tf1_dense(float* p, float* g, float* m, float* v, int64_t n, float lr_t,
                            const float* lr_t_dev, float beta1, float beta2, float eps, int zero_grad,

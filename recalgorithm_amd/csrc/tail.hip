@@ -427,8 +427,8 @@ __global__ __launch_bounds__(256) void adam_tf1_step_kernel(AdamStepArgs A) {
             A.p[i] = pp; A.m[i] = mm; A.v[i] = vv;
             if (A.zero_grad) A.g[i] = 0.f;
         }
-    } else {
-        int a = 0;
+    } else if (A.n_arenas > 0) {                     // (n == 0 and no arena: the one workgroup only takes its ticket —
+        int a = 0;                                   //  ar[0] is then a padding descriptor with no count to read)
 #pragma unroll
         for (int k = 1; k < kAdamMaxArenas; ++k)
             if (k < A.n_arenas && blockIdx.x >= A.ar[k].first_block) a = k;
@@ -676,6 +676,7 @@ RECALGO_EXPORT int recalgo_adam_tf1_dense(float* p, float* g, float* m, float* v
                                           float eps, int zero_grad, recalgo_stream_t stream) {
     RECALGO_REQUIRE(n >= 0);
     if (n == 0) return 0;
+    RECALGO_REQUIRE(aligned16(p, g, m, v));            // (the float4 body; the n % 4 tail is element-wise)
     int64_t n4 = n / 4;
     int64_t want = (n4 + 255) / 256;
     int blocks = (int)(want < 1 ? 1 : (want > 256 * 16 ? 256 * 16 : want));
@@ -690,6 +691,7 @@ RECALGO_EXPORT int recalgo_adam_tf1_rows(float* p, float* g, float* m, float* v,
     RECALGO_REQUIRE(rows >= 0 && row_live != nullptr);
     RECALGO_REQUIRE(K == 4 || K == 8 || K == 16 || K == 32 || K == 64);
     if (rows == 0) return 0;
+    RECALGO_REQUIRE(aligned16(p, g, m, v));
     const int64_t total4 = rows * (K / 4);
     int64_t want = (total4 + 255) / 256;
     int blocks = (int)(want < 1 ? 1 : (want > 256 * 16 ? 256 * 16 : want));
@@ -775,6 +777,7 @@ RECALGO_EXPORT int recalgo_adam_tf1_list(float* p, float* g, float* m, float* v,
                            live_count, (unsigned)K, lr_t, lr_t_dev, beta1, beta2, eps, zero_grad);
         RECALGO_RETURN_LAST();
     }
+    RECALGO_REQUIRE(aligned16(p, g, m, v));            // (the float4 kernels; the element-wise one above takes any base)
     // the launch is sized for the largest possible list (graph replayable); surplus workgroups exit at once
     int64_t want = (max_rows * (K / 4) + 255) / 256;
     int blocks = (int)(want < 1 ? 1 : (want > 256 * 8 ? 256 * 8 : want));
@@ -863,7 +866,7 @@ RECALGO_EXPORT int recalgo_adam_tf1_step_plans(float* p, float* g, float* m, flo
     RECALGO_REQUIRE(n >= 0 && n_arenas >= 0 && n_arenas <= kAdamMaxArenas && step_dev != nullptr);
     RECALGO_REQUIRE(n_scans >= 0 && n_scans <= kAdamMaxArenas && (n_scans == 0 || scans != nullptr));
     RECALGO_REQUIRE(!advance || ticket_dev != nullptr);
-    RECALGO_REQUIRE(n == 0 || (p && g && m && v));
+    RECALGO_REQUIRE(n == 0 || (p && g && m && v && aligned16(p, g, m, v)));
     RECALGO_REQUIRE(n_arenas == 0 || arenas != nullptr);
     AdamStepArgs A;
     A.p = p; A.g = g; A.m = m; A.v = v; A.n = n;
@@ -875,6 +878,7 @@ RECALGO_EXPORT int recalgo_adam_tf1_step_plans(float* p, float* g, float* m, flo
         const recalgo_adam_arena_t& a = arenas[i];
         if (a.max_rows <= 0) continue;
         RECALGO_REQUIRE(a.p && a.g && a.m && a.v && a.live_list && a.live_count && a.K >= 1);
+        RECALGO_REQUIRE((a.K & 3) != 0 || aligned16(a.p, a.g, a.m, a.v));      // (the float4 arms)
         AdamArena& R = A.ar[A.n_arenas++];
         R.p = a.p; R.g = a.g; R.m = a.m; R.v = a.v; R.list = a.live_list; R.count = a.live_count; R.K = a.K;
         R.k4_shift = -1;
