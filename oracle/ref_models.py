@@ -70,6 +70,17 @@ def _dropout(net, params, training, masks):
     return net * masks.pop(0).to(net.dtype) / (1.0 - rate)
 
 
+def _bn(P, x, scope, training, bn_state=None):
+    """tf.layers.batch_normalization under `scope`; in training mode with a dict `bn_state`, the batch moments it
+    normalised with are left there as bn_state[scope] = (mean, biased variance) — what the moving statistics' update
+    (momentum 0.99, done by the caller) consumes."""
+    if training and bn_state is not None:
+        mean = x.detach().mean(dim=0)
+        bn_state[scope] = (mean, ((x.detach() - mean) ** 2).mean(dim=0))
+    return R.batch_norm(x, P[f"{scope}/gamma"], P[f"{scope}/beta"], P[f"{scope}/moving_mean"],
+                        P[f"{scope}/moving_variance"], training)
+
+
 def _tail(logit, labels, extra=None):
     out = {"logit": logit, "prob": torch.sigmoid(logit)}
     if labels is not None:
@@ -102,7 +113,7 @@ def dcn(P, feats, labels, params, training=False):
 
 def deepfm(P, feats, labels, params, training=False, bn_state=None, dropout_masks=None):
     """algorithm/DeepFM/deepfm.py:165-235.  MLP order dense(relu) -> dropout -> BN (:207-211); batch norm uses batch
-    statistics when `training`; training-mode dropout takes its keep masks from `dropout_masks` (call order)."""
+    statistics when `training` (and leaves them in `bn_state`, see _bn); training-mode dropout takes its keep masks from `dropout_masks` (call order)."""
     masks = list(dropout_masks or [])
     first_cols = _sorted(params["first_order_feature_columns"])
     # fm_first_order: (B, sum V) multi-hot @ kernel + bias == sum of per-column weight lookups
@@ -121,8 +132,7 @@ def deepfm(P, feats, labels, params, training=False, bn_state=None, dropout_mask
         net = _dropout(net, params, training, masks)                               # :208-209
         if params.get("batch_norm"):
             bn = "batch_normalization" if i == 0 else f"batch_normalization_{i}"
-            net = R.batch_norm(net, P[f"fm_deep/{bn}/gamma"], P[f"fm_deep/{bn}/beta"],
-                               P[f"fm_deep/{bn}/moving_mean"], P[f"fm_deep/{bn}/moving_variance"], training)
+            net = _bn(P, net, f"fm_deep/{bn}", training, bn_state)
     n = len(params["hidden_units"])
     dn = "dense" if n == 0 else f"dense_{n}"
     deep = R.dense(net, P[f"fm_deep/{dn}/kernel"], P[f"fm_deep/{dn}/bias"])
@@ -235,7 +245,7 @@ def ffm(P, feats, labels, params, training=False):
     return _tail(logit, None if labels is None else labels["read_comment"])
 
 
-def nfm(P, feats, labels, params, training=False, dropout_masks=None):
+def nfm(P, feats, labels, params, training=False, dropout_masks=None, bn_state=None):
     """algorithm/NFM/nfm.py:143-184 (SURVEY.md §8f-3 sibling).  Bi-interaction pooling
     0.5 * ((sum_f e_f)^2 - sum_f e_f^2) -> BatchNorm `bi_interaction_bn` -> dropout with the HARD-CODED rate 0.1
     (:170, independent of the dropout_rate flag) -> MLP (dense(relu) -> BN -> dropout(rate flag)) -> dense(1).
@@ -253,7 +263,7 @@ def nfm(P, feats, labels, params, training=False, dropout_masks=None):
         s_, q_ = s_ + e, q_ + e ** 2
     x = 0.5 * (s_ ** 2 - q_)                                                                                    # :163-167
     b = "bi_interaction_part/bi_interaction_bn"
-    x = R.batch_norm(x, P[f"{b}/gamma"], P[f"{b}/beta"], P[f"{b}/moving_mean"], P[f"{b}/moving_variance"], training)  # :168
+    x = _bn(P, x, b, training, bn_state)                                                                         # :168
     masks = list(dropout_masks or [])
     if training:                                                                                                # :170
         if not masks:
@@ -265,8 +275,7 @@ def nfm(P, feats, labels, params, training=False, dropout_masks=None):
         net = R.dense(net, P[f"dnn_part/{dn}/kernel"], P[f"dnn_part/{dn}/bias"], relu=True)
         if params.get("batch_norm"):
             bn = "batch_normalization" if i == 0 else f"batch_normalization_{i}"
-            net = R.batch_norm(net, P[f"dnn_part/{bn}/gamma"], P[f"dnn_part/{bn}/beta"],
-                               P[f"dnn_part/{bn}/moving_mean"], P[f"dnn_part/{bn}/moving_variance"], training)
+            net = _bn(P, net, f"dnn_part/{bn}", training, bn_state)
         net = _dropout(net, params, training, masks)                                                            # :178-179 (behind the BN)
     n = len(params["hidden_units"])
     dn = "dense" if n == 0 else f"dense_{n}"
@@ -295,7 +304,7 @@ def xdeepfm(P, feats, labels, params, training=False):
     return _tail(linear_logit + cin_logit + dnn_logit, None if labels is None else labels["read_comment"])
 
 
-def din(P, feats, labels, params, training=False, dropout_masks=None):
+def din(P, feats, labels, params, training=False, dropout_masks=None, bn_state=None):
     """algorithm/DIN/din.py:186-257; fcn order dense -> dice | prelu -> BN -> dropout (:227-236)."""
     masks = list(dropout_masks or [])
     reg = {}
@@ -326,8 +335,7 @@ def din(P, feats, labels, params, training=False, dropout_masks=None):
             net = R.prelu(net, P[f"fcn/prelu_alpha_{i + 1}"])
         if params["batch_norm"]:
             bn = "batch_normalization" if i == 0 else f"batch_normalization_{i}"
-            net = R.batch_norm(net, P[f"fcn/{bn}/gamma"], P[f"fcn/{bn}/beta"], P[f"fcn/{bn}/moving_mean"],
-                               P[f"fcn/{bn}/moving_variance"], training)
+            net = _bn(P, net, f"fcn/{bn}", training, bn_state)
         net = _dropout(net, params, training, masks)                                               # :235-236
     n = len(params["hidden_units"])
     dn = "dense" if n == 0 else f"dense_{n}"
@@ -338,7 +346,7 @@ def din(P, feats, labels, params, training=False, dropout_masks=None):
     return _tail(logit, None if labels is None else labels["read_comment"], extra)
 
 
-def _dnn_bn(P, net, scope, hidden_units, batch_norm, training, params=None, masks=None):
+def _dnn_bn(P, net, scope, hidden_units, batch_norm, training, params=None, masks=None, bn_state=None):
     """dense(relu) -> dropout -> BN, the DeepFM/PNN/FiBiNET MLP order (quirk B-7)."""
     for i, _ in enumerate(hidden_units):
         dn = "dense" if i == 0 else f"dense_{i}"
@@ -346,14 +354,13 @@ def _dnn_bn(P, net, scope, hidden_units, batch_norm, training, params=None, mask
         net = _dropout(net, params or {}, training, masks)
         if batch_norm:
             bn = "batch_normalization" if i == 0 else f"batch_normalization_{i}"
-            net = R.batch_norm(net, P[f"{scope}/{bn}/gamma"], P[f"{scope}/{bn}/beta"],
-                               P[f"{scope}/{bn}/moving_mean"], P[f"{scope}/{bn}/moving_variance"], training)
+            net = _bn(P, net, f"{scope}/{bn}", training, bn_state)
     n = len(hidden_units)
     dn = "dense" if n == 0 else f"dense_{n}"
     return R.dense(net, P[f"{scope}/{dn}/kernel"], P[f"{scope}/{dn}/bias"])
 
 
-def fibinet(P, feats, labels, params, training=False, dropout_masks=None):
+def fibinet(P, feats, labels, params, training=False, dropout_masks=None, bn_state=None):
     """algorithm/FiBiNET/fibinet.py:143-221."""
     dense_cols = params.get("dense_feature_columns") or []
     cat = input_layer(P, feats, params["category_feature_columns"], "category_input/input_layer", {})
@@ -364,14 +371,14 @@ def fibinet(P, feats, labels, params, training=False, dropout_masks=None):
                                P[f"bilinear_interaction_part/orginal_w_{t}"],
                                P[f"bilinear_interaction_part/senet_w_{t}"], t)                     # :171-187
     logit = _dnn_bn(P, bi, "dnn_part", params["hidden_units"], params.get("batch_norm"), training, params,
-                    list(dropout_masks or []))                                                     # :189-197
+                    list(dropout_masks or []), bn_state)                                           # :189-197
     if dense_cols:
         dense_in = input_layer(P, feats, dense_cols, "dense_input/input_layer")
         logit = R.dense(dense_in, P["linear_part/dense/kernel"], P["linear_part/dense/bias"]) + logit   # :168,199
     return _tail(logit, None if labels is None else labels["read_comment"])
 
 
-def pnn(P, feats, labels, params, training=False, dropout_masks=None):
+def pnn(P, feats, labels, params, training=False, dropout_masks=None, bn_state=None):
     """algorithm/PNN/pnn.py:112-214."""
     fields, reg = [], {}
     for i, c in enumerate(params["category_feature_columns"]):                                     # :126-129 list order
@@ -383,7 +390,7 @@ def pnn(P, feats, labels, params, training=False, dropout_masks=None):
     pw = P["product_part/inner_product_w"] if method == "IPNN" else P["product_part/outer_product_w"]
     _, _, product_final = R.pnn_product_fast(emb, P["linear_part/linear_w"], pw, P["bias"], F, K, method)   # :133-181
     logit = _dnn_bn(P, product_final, "fcn", params["hidden_units"], params.get("batch_norm"), training, params,
-                    list(dropout_masks or []))                                                              # :184-193
+                    list(dropout_masks or []), bn_state)                                                    # :184-193
     extra = None
     wr = float(params.get("weight_regularizer") or 0.0)
     if labels is not None and wr > 0:            # tf.contrib.layers.l2_regularizer(scale): scale * sum(w^2) / 2
