@@ -1,5 +1,5 @@
-"""ctypes binding of librecalgo_hip.so (the C-ABI declared in include/recalgo.h, include/recalgo_cgc.h and
-include/recalgo_wide.h).
+"""ctypes binding of librecalgo_hip.so (the C-ABI declared in include/recalgo.h, include/recalgo_cgc.h,
+include/recalgo_wide.h and include/recalgo_bst.h).
 
 The product path has NO CPU fallback: if the shared library is missing or a symbol
 declared in the header is absent, loading raises immediately.
@@ -30,6 +30,9 @@ ABI_CGC_VERSION = ABI_CGC.constants["RECALGO_CGC_ABI_VERSION"]
 # include/recalgo_wide.h: the third header (Wide&Deep's crossed wide column + FTRL), with a version of its own
 ABI_WIDE = _abi.read("recalgo_wide.h")
 ABI_WIDE_VERSION = ABI_WIDE.constants["RECALGO_WIDE_ABI_VERSION"]
+# include/recalgo_bst.h: the fourth header (BST's transformer block), with a version of its own
+ABI_BST = _abi.read("recalgo_bst.h")
+ABI_BST_VERSION = ABI_BST.constants["RECALGO_BST_ABI_VERSION"]
 
 _lib = None
 
@@ -54,7 +57,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
             "(there is no CPU fallback for the hot path)")
     import torch  # noqa: F401  (maps torch's libamdhip64 before ours resolves its NEEDED)
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for abi in (ABI, ABI_CGC, ABI_WIDE):
+    for abi in (ABI, ABI_CGC, ABI_WIDE, ABI_BST):
         for name, (res, args) in abi.functions.items():
             try:
                 fn = getattr(lib, name)
@@ -66,7 +69,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                 fn.errcheck = launch_errcheck(name)
     for what, got, want in (("ABI", lib.recalgo_abi_version(), ABI_VERSION),
                             ("CGC ABI", lib.recalgo_cgc_abi_version(), ABI_CGC_VERSION),
-                            ("WIDE ABI", lib.recalgo_wide_abi_version(), ABI_WIDE_VERSION)):
+                            ("WIDE ABI", lib.recalgo_wide_abi_version(), ABI_WIDE_VERSION),
+                            ("BST ABI", lib.recalgo_bst_abi_version(), ABI_BST_VERSION)):
         if got != want:
             raise RecalgoError(f"{path}: {what} version {got}, this binding expects {want} "
                                "(a stale build: python -m recalgorithm_amd.build)")

@@ -890,3 +890,45 @@ def apply_parked_grads(step_dev=None):
 def l2_regularization(scale: float, variables) -> torch.Tensor:
     """sum_v tf.contrib.layers.l2_regularizer(scale)(v) = scale * sum(v^2) / 2."""
     return _L2RegFn.apply(current_store().anchor, float(scale), tuple(variables))
+
+
+def bst_transformer(queries: torch.Tensor, keys_length: torch.Tensor, heads: int, index: int, max_length: int,
+                    pool: Optional[str] = None):
+    """algorithm/BST/transformer_layer.py bst_transformer(queries, queries, queries, keys_length, heads, index, max_length) on
+    the two fused kernels of csrc/bst.hip per direction.  Variables under the caller's scope, the reference's names:
+    position_embedding [max_length, d] (ONE table for every block of the scope: each block adds it again, its gradient is the
+    sum over the blocks), w_q_<index> / w_k_<index> / w_v_<index> [heads, d, d], w_o_<index> [heads * d, d] (glorot-uniform,
+    tf.get_variable's default), LayerNorm[_n]/{gamma, beta} twice (tf.contrib.layers.layer_norm's auto names: ones, zeros),
+    dense[_n]/{kernel, bias} (tf.layers.dense).
+    queries [B, T, d] (row 0 the target, padded rows zero), keys_length [B] = history length + 1.
+    pool=None -> the block's output [B, T, d], to chain into the next block; pool='sum' | 'mean' -> [B, d], the reduction over
+    ALL T rows (bst.py:195-198) fused into the block's last kernel.  Sizes the kernels do not serve raise ValueError."""
+    from . import ops
+    store = current_store()
+    B, T, d = queries.shape
+    heads, max_length = int(heads), int(max_length)
+    if T > max_length:
+        raise ValueError(f"bst_transformer: {T} rows but position_embedding has max_length={max_length}")
+    pos = store.get_variable("position_embedding", (max_length, d), glorot_uniform)
+    w_q, w_k, w_v = (store.get_variable(f"w_{n}_{index}", (heads, d, d), glorot_uniform) for n in ("q", "k", "v"))
+    w_o = store.get_variable(f"w_o_{index}", (heads * d, d), glorot_uniform)
+
+    def layer_norm_variables():
+        with store.variable_scope(store.auto_name("LayerNorm")):
+            return store.get_variable("gamma", (d,), ones), store.get_variable("beta", (d,), zeros)
+    norm1 = layer_norm_variables()               # (creation order of transformer_layer.py:72-79: LayerNorm, dense, LayerNorm_1)
+    with store.variable_scope(store.auto_name("dense")):
+        ffn_w = store.get_variable("kernel", (d, d), glorot_uniform)
+        ffn_b = store.get_variable("bias", (d,), zeros)
+    norms = [norm1, layer_norm_variables()]
+    if pool not in (None, "sum", "mean"):
+        raise ValueError(f"bst_transformer: pool={pool!r}")
+    if not ops.bst_supported(T, d, heads):
+        raise ValueError(f"bst_transformer: T={T} d={d} heads={heads} is outside what the BST kernels serve (1 <= T <= "
+                         f"{ops.BST_MAX_T}, d in (4, 8, 12, 16), heads <= {ops.BST_MAX_HEADS}); there is no fallback")
+    if store.building:
+        return queries.new_zeros((B, T, d) if pool is None else (B, d))
+    x = queries if queries.is_contiguous() else queries.contiguous()
+    n1 = ops.bst_attention(x, keys_length, pos, w_q, w_k, w_v, w_o, *norms[0], anchor=store.anchor)
+    out, pooled = ops.bst_ffn(n1, ffn_w, ffn_b, *norms[1], pool=pool, want_out=pool is None, anchor=store.anchor)
+    return out if pool is None else pooled

@@ -86,6 +86,7 @@ def discard_step_work() -> None:
     _colsum_pending.clear()
     _dlogit_partials.clear()
     _parked_l2.clear()
+    _bst_shared.clear()
 
 
 def anchor_store(anchor):
@@ -2439,3 +2440,160 @@ def adam_tf1_step_(flat, flat_grad, flat_m, flat_v, arenas, step_dev: torch.Tens
         lib.recalgo_adam_tf1_step_plans(_p(flat) if n else None, _p(flat_grad) if n else None, _p(flat_m) if n else None,
                                         _p(flat_v) if n else None, n, arr, len(chunk), _p(step_dev), _p(ticket_dev), int(advance),
                                         lr, beta1, beta2, eps, int(zero_grad), scans, len(plan_scans), _stream(step_dev))
+
+
+# =============================================================================================
+# BST (csrc/bst.hip, include/recalgo_bst.h): the transformer block — attention + LayerNorm, FFN + LayerNorm (+ pooling)
+# =============================================================================================
+_CB = _lib.ABI_BST.constants                 # the RECALGO_BST_* #defines of include/recalgo_bst.h
+BST_MAX_T, BST_MAX_D, BST_MAX_HEADS = _CB["RECALGO_BST_MAX_T"], _CB["RECALGO_BST_MAX_D"], _CB["RECALGO_BST_MAX_HEADS"]
+_bst_shared = {}             # id(Variable) -> how many blocks of the running step read it (position_embedding: every block
+#                              adds it again); the block whose backward runs first overwrites its gradient, the others add
+
+
+def bst_supported(T: int, d: int, H: int) -> bool:
+    return bool(_lib_().recalgo_bst_supported(int(T), int(d), int(H)))
+
+
+def _bst_split(params):
+    """-> (the tensors the kernels read, the Variables | None).  A Variable's gradient is written to Variable.grad, a tensor's
+    is returned to autograd."""
+    return [p.data if isinstance(p, Variable) else p for p in params], [p if isinstance(p, Variable) else None for p in params]
+
+
+def _bst_grad_buffers(ts, vs):
+    """per parameter, the buffer its gradient is written to: Variable.grad, or a new tensor"""
+    return [v.grad if v is not None else torch.empty_like(t) for t, v in zip(ts, vs)]
+
+
+class _BstAttnFn(Function):
+    """include/recalgo_bst.h recalgo_bst_attn_fwd / recalgo_bst_attn_bwd; params = (pos, w_q, w_k, w_v, w_o, gamma, beta),
+    `tensors` the same seven with None where params holds a Variable."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, keys_length, heads, differentiated, params, *tensors):
+        ts, vs = _bst_split(params)
+        B, T, d = x.shape
+        n1 = torch.empty(B, T, d, device=x.device, dtype=torch.float32)
+        _lib_().recalgo_bst_attn_fwd(_p(x), *[_p(t) for t in ts[:1]], _p(keys_length), *[_p(t) for t in ts[1:]], B, T, d, heads,
+                                     _p(n1), None, _stream(x))
+        ctx.ts, ctx.vs, ctx.heads, ctx.order = ts, vs, heads, 0
+        if vs[0] is not None and differentiated:         # (the caller's grad mode: inside a Function's forward it is always off)
+            ctx.order = _bst_shared[id(vs[0])] = _bst_shared.get(id(vs[0]), 0) + 1
+        ctx.save_for_backward(x, keys_length)
+        return n1
+
+    @staticmethod
+    def backward(ctx, g):
+        ts, vs, H = ctx.ts, ctx.vs, ctx.heads
+        x, keys_length = ctx.saved_tensors
+        B, T, d = x.shape
+        g = g if g.is_contiguous() else g.contiguous()
+        lib = _lib_()
+        dx = torch.empty_like(x)
+        dpos = torch.empty(T, d, device=x.device, dtype=torch.float32)
+        outs = _bst_grad_buffers(ts[1:], vs[1:])         # dw_q, dw_k, dw_v, dw_o, dgamma, dbeta
+        ws = _workspace(int(lib.recalgo_bst_attn_bwd_workspace_bytes(B, T, d, H)), x.device)
+        lib.recalgo_bst_attn_bwd(_p(x), _p(ts[0]), _p(keys_length), *[_p(t) for t in ts[1:6]], _p(g), B, T, d, H, _p(dx), _p(dpos),
+                                 *[_p(o) for o in outs], _p(ws), _stream(x))
+        pos_v = vs[0]
+        if pos_v is not None:
+            # the table is [max_length, d], the kernel's gradient its first T rows; shared by every block of the model
+            first = ctx.order == _bst_shared.get(id(pos_v), ctx.order)
+            if first:
+                pos_v.grad.zero_()
+                pos_v.grad[:T].copy_(dpos)
+            else:
+                pos_v.grad[:T].add_(dpos)
+            if ctx.order <= 1:
+                _bst_shared.pop(id(pos_v), None)
+            dpos_ret = None
+        else:
+            dpos_ret = torch.zeros_like(ts[0])
+            dpos_ret[:T].copy_(dpos)
+        rets = [dpos_ret] + [None if v is not None else o for o, v in zip(outs, vs[1:])]
+        return (None, dx if ctx.needs_input_grad[1] else None, None, None, None, None, *rets)
+
+
+class _BstFfnFn(Function):
+    """include/recalgo_bst.h recalgo_bst_ffn_fwd / recalgo_bst_ffn_bwd; params = (ffn_w, ffn_b, gamma, beta).  -> (out | None,
+    pool | None)."""
+
+    @staticmethod
+    def forward(ctx, anchor, n1, mean_pool, want_out, want_pool, params, *tensors):
+        ctx.set_materialize_grads(False)
+        ts, vs = _bst_split(params)
+        B, T, d = n1.shape
+        out = torch.empty(B, T, d, device=n1.device, dtype=torch.float32) if want_out else None
+        pool = torch.empty(B, d, device=n1.device, dtype=torch.float32) if want_pool else None
+        _lib_().recalgo_bst_ffn_fwd(_p(n1), *[_p(t) for t in ts], B, T, d, int(mean_pool), _p(out), _p(pool), None, _stream(n1))
+        ctx.ts, ctx.vs, ctx.mean_pool = ts, vs, int(mean_pool)
+        ctx.save_for_backward(n1)
+        return out, pool
+
+    @staticmethod
+    def backward(ctx, g_out, g_pool):
+        ts, vs = ctx.ts, ctx.vs
+        (n1,) = ctx.saved_tensors
+        if g_out is None and g_pool is None:
+            return (None,) * (6 + len(ts))
+        B, T, d = n1.shape
+        g_out = None if g_out is None else (g_out if g_out.is_contiguous() else g_out.contiguous())
+        g_pool = None if g_pool is None else (g_pool if g_pool.is_contiguous() else g_pool.contiguous())
+        lib = _lib_()
+        dn1 = torch.empty_like(n1)
+        outs = _bst_grad_buffers(ts, vs)                 # dw, db, dgamma, dbeta
+        ws = _workspace(int(lib.recalgo_bst_ffn_bwd_workspace_bytes(B, d)), n1.device)
+        lib.recalgo_bst_ffn_bwd(_p(n1), *[_p(t) for t in ts[:3]], _p(g_out), _p(g_pool), B, T, d, ctx.mean_pool, _p(dn1),
+                                *[_p(o) for o in outs], _p(ws), _stream(n1))
+        rets = [None if v is not None else o for o, v in zip(outs, vs)]
+        return (None, dn1 if ctx.needs_input_grad[1] else None, None, None, None, None, *rets)
+
+
+def _bst_check(x, T, d, H, params, shapes, what):
+    if not bst_supported(T, d, H):
+        raise ValueError(f"{what}: the BST kernels serve 1 <= T <= {BST_MAX_T}, d in (4, 8, 12, 16) and 1 <= heads <= "
+                         f"{BST_MAX_HEADS}; got T={T} d={d} heads={H} (there is no fallback)")
+    if x.shape[0] == 0:
+        raise ValueError(f"{what}: empty batch")
+    ts, _ = _bst_split(params)
+    for t, shape, name in zip(ts, shapes, ("pos", "w_q", "w_k", "w_v", "w_o", "gamma", "beta") if len(shapes) == 7
+                              else ("ffn_w", "ffn_b", "gamma", "beta")):
+        _chk(t, torch.float32, f"{what}: {name}")
+        if (tuple(t.shape) != shape) if name != "pos" else (t.dim() != 2 or t.shape[0] < T or t.shape[1] != d):
+            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {shape}")
+
+
+def bst_attention(x: torch.Tensor, keys_length: torch.Tensor, pos, w_q, w_k, w_v, w_o, gamma, beta, anchor=None) -> torch.Tensor:
+    """The attention half of a BST block (transformer_layer.py:27-72): LayerNorm(concat_h(softmax(Q_h K_h^T / sqrt(d) + mask)
+    V_h) w_o + Xp) with Xp = x + pos[:T], Q and K from Xp, V from x; the mask is on the QUERY rows >= keys_length.
+    x [B, T, d]; keys_length integer [B]; pos [>= T, d]; w_q / w_k / w_v [H, d, d]; w_o [H d, d]; gamma, beta [d] — Variables
+    (gradient to Variable.grad; a `pos` Variable shared by several blocks gets their sum) or tensors.  Unsupported sizes:
+    ValueError, there is no fallback."""
+    if x.dim() != 3:
+        raise ValueError("bst_attention: x must be [B, T, d]")
+    B, T, d = x.shape
+    params = [pos, w_q, w_k, w_v, w_o, gamma, beta]
+    wq_t = w_q.data if isinstance(w_q, Variable) else w_q
+    H = int(wq_t.shape[0]) if wq_t.dim() == 3 else 0
+    _bst_check(x, T, d, H, params, [(T, d), (H, d, d), (H, d, d), (H, d, d), (H * d, d), (d,), (d,)], "bst_attention")
+    _chk(x, torch.float32, "bst_attention: x")
+    keys_length = keys_length.reshape(-1).to(torch.int32).contiguous()
+    if keys_length.numel() != B:
+        raise ValueError("bst_attention: one keys_length per example")
+    tensors = [None if isinstance(p, Variable) else p for p in params]
+    return _BstAttnFn.apply(anchor, x, keys_length, H, torch.is_grad_enabled(), params, *tensors)
+
+
+def bst_ffn(n1: torch.Tensor, ffn_w, ffn_b, gamma, beta, pool: Optional[str] = None, want_out: bool = True, anchor=None):
+    """The FFN half of a BST block (transformer_layer.py:74-81): out = LayerNorm(leakyrelu(n1 W + b) + n1) -> (out, pooled):
+    pooled = out summed (pool="sum") or averaged (pool="mean") over ALL T rows, None without `pool`; out is None with
+    want_out=False."""
+    if n1.dim() != 3 or pool not in (None, "sum", "mean") or not (want_out or pool):
+        raise ValueError("bst_ffn: n1 must be [B, T, d], pool one of None, 'sum', 'mean', and some output wanted")
+    B, T, d = n1.shape
+    params = [ffn_w, ffn_b, gamma, beta]
+    _bst_check(n1, T, d, 1, params, [(d, d), (d,), (d,), (d,)], "bst_ffn")
+    _chk(n1, torch.float32, "bst_ffn: n1")
+    tensors = [None if isinstance(p, Variable) else p for p in params]
+    return _BstFfnFn.apply(anchor, n1, pool == "mean", bool(want_out), pool is not None, params, *tensors)
