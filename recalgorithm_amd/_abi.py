@@ -8,12 +8,16 @@ declarations the HIP and C++ sources compile against, so the header is the only 
     abi.structs     name -> ctypes.Structure subclass of each `typedef struct { .. } recalgo_*_t;`, fields in header order
     abi.constants   name -> int of each `#define RECALGO_* <integer>` (the ABI version among them)
 
+    declaration_hash("recalgo.h")   what an ABI version covers: the sha256 of the header's declarations
+    read_record("recalgo.h")        version -> that hash, as include/recalgo.abi recorded it when the version was set
+
 One type rule serves parameters, return types and struct fields (`ctype_of`).  The reader knows exactly the constructs the
 two headers use; anything else raises RecalgoError naming the line — it never skips a declaration.
 """
 from __future__ import annotations
 
 import ctypes
+import hashlib
 import os
 import re
 from types import SimpleNamespace
@@ -109,9 +113,32 @@ def parse(text: str, origin: str = "<string>") -> SimpleNamespace:
         pos = m.end()
 
 
-def read(header: str) -> SimpleNamespace:
+def _text(header: str) -> str:
     path = os.path.join(INCLUDE, header)
     if not os.path.exists(path):
         raise RecalgoError(f"{path} not found: the ctypes binding is derived from it")
     with open(path) as f:
-        return parse(f.read(), path)
+        return f.read()
+
+
+def read(header: str) -> SimpleNamespace:
+    return parse(_text(header), os.path.join(INCLUDE, header))
+
+
+def declaration_hash(header: str, text: str = None) -> str:
+    """sha256 over the declarations of include/<header> (or of `text`, a header's content): comments, the header's
+    `#define RECALGO_[<KEY>_]ABI_VERSION <n>` and runs of white space removed.  What this covers is what a version stands for:
+    the declarations may not change while the number stays (include/<stem>.abi, tests/test_abi.py)."""
+    src = re.sub(r"/\*.*?\*/", "", _text(header) if text is None else text, flags=re.S)
+    src = re.sub(r"#define RECALGO_(?:[A-Z0-9]+_)?ABI_VERSION \d+", "", src)
+    return hashlib.sha256(re.sub(r"\s+", " ", src).strip().encode()).hexdigest()
+
+
+def record_path(header: str) -> str:
+    return os.path.join(INCLUDE, os.path.splitext(header)[0] + ".abi")
+
+
+def read_record(header: str) -> dict:
+    """include/<stem>.abi -> {version: declaration hash}: one `version sha256` line per version, `#` starts a comment line"""
+    with open(record_path(header)) as f:
+        return {int(v): h for v, h in (ln.split() for ln in f if ln.strip() and not ln.startswith("#"))}

@@ -1,13 +1,10 @@
-"""ctypes binding of librecalgo_hip.so (the C-ABI declared in include/recalgo.h, include/recalgo_cgc.h,
-include/recalgo_wide.h and include/recalgo_bst.h).
-
-The product path has NO CPU fallback: if the shared library is missing or a symbol
-declared in the header is absent, loading raises immediately.
-"""
+"""ctypes binding of librecalgo_hip.so (the C-ABI declared in the headers that HEADERS below lists).  The product path has
+NO CPU fallback: if the shared library is missing or a symbol declared in a header is absent, loading raises immediately."""
 from __future__ import annotations
 
 import ctypes
 import os
+import re
 
 from . import _abi
 from ._abi import RecalgoError  # noqa: F401  (raised here and by every caller as _lib.RecalgoError)
@@ -18,23 +15,30 @@ LIB_PATH = os.environ.get("RECALGO_HIP_LIB") or os.path.join(_HERE, "librecalgo_
 
 P = ctypes.c_void_p  # device pointer / stream
 
-# include/recalgo.h is the one statement of the ABI: signatures, struct layouts, constants and the version are read from it
-ABI = _abi.read("recalgo.h")
+
+def _versioned(header: str):
+    """_abi.read(header) with what load() checks of it: .version, the header's ONE `RECALGO_[<KEY>_]ABI_VERSION` constant;
+    .version_query, the one `recalgo_[<key>_]abi_version` function that returns it; .label, its name in error messages."""
+    abi = _abi.read(header)
+    defines = [c for c in abi.constants if re.fullmatch(r"RECALGO_(?:[A-Z0-9]+_)?ABI_VERSION", c)]
+    queries = [f for f in abi.functions if re.fullmatch(r"recalgo_(?:[a-z0-9]+_)?abi_version", f)]
+    if len(defines) != 1 or queries != [defines[0].lower()]:
+        raise RecalgoError(f"include/{header}: a header of HEADERS has exactly one RECALGO_[<KEY>_]ABI_VERSION define and the "
+                           f"one function recalgo_[<key>_]abi_version of the same key; found {defines} and {queries}")
+    abi.version, abi.version_query = abi.constants[defines[0]], queries[0]
+    abi.label = defines[0][len("RECALGO_"):-len("_VERSION")].replace("_", " ")       # `ABI`, `CGC ABI`, ..
+    return abi
+
+
+# The headers of the HIP library, each the one statement of its part of the ABI (signatures, struct layouts, constants, a
+# version of its own, bumped on any signature change).  This is the only list of them: a new header is one more entry.
+HEADERS = {h: _versioned(h) for h in ("recalgo.h", "recalgo_cgc.h", "recalgo_wide.h", "recalgo_bst.h")}
+ABI = HEADERS["recalgo.h"]  # the first header's tables, under the names the product uses:
 SIGNATURES = ABI.functions  # name -> (restype, argtypes) of every function of the header
 STRUCTS = ABI.structs  # recalgo_*_t -> ctypes.Structure subclass
 CONSTANTS = ABI.constants  # RECALGO_* -> int
-ABI_VERSION = CONSTANTS["RECALGO_ABI_VERSION"]  # (bumped on any signature change)
-# include/recalgo_cgc.h: the second header of the same library (PLE's CGC block), with a version of its own
-ABI_CGC = _abi.read("recalgo_cgc.h")
-ABI_CGC_VERSION = ABI_CGC.constants["RECALGO_CGC_ABI_VERSION"]
-# include/recalgo_wide.h: the third header (Wide&Deep's crossed wide column + FTRL), with a version of its own
-ABI_WIDE = _abi.read("recalgo_wide.h")
-ABI_WIDE_VERSION = ABI_WIDE.constants["RECALGO_WIDE_ABI_VERSION"]
-# include/recalgo_bst.h: the fourth header (BST's transformer block), with a version of its own
-ABI_BST = _abi.read("recalgo_bst.h")
-ABI_BST_VERSION = ABI_BST.constants["RECALGO_BST_ABI_VERSION"]
-
-_lib = None
+ABI_VERSION = ABI.version
+_lib = None  # the loaded library
 
 
 def launch_errcheck(name: str):
@@ -52,27 +56,22 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
     if _lib is not None:
         return _lib
     if not os.path.exists(path):
-        raise RecalgoError(
-            f"{path} not found: build it with `python -m recalgorithm_amd.build` "
-            "(there is no CPU fallback for the hot path)")
+        raise RecalgoError(f"{path} not found: build it with `python -m recalgorithm_amd.build` "
+                           "(there is no CPU fallback for the hot path)")
     import torch  # noqa: F401  (maps torch's libamdhip64 before ours resolves its NEEDED)
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for abi in (ABI, ABI_CGC, ABI_WIDE, ABI_BST):
+    for abi in HEADERS.values():
         for name, (res, args) in abi.functions.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
                 raise RecalgoError(f"{path} does not export {name}") from e
-            fn.restype = res
-            fn.argtypes = args
+            fn.restype, fn.argtypes = res, args
             if name in abi.launches:
                 fn.errcheck = launch_errcheck(name)
-    for what, got, want in (("ABI", lib.recalgo_abi_version(), ABI_VERSION),
-                            ("CGC ABI", lib.recalgo_cgc_abi_version(), ABI_CGC_VERSION),
-                            ("WIDE ABI", lib.recalgo_wide_abi_version(), ABI_WIDE_VERSION),
-                            ("BST ABI", lib.recalgo_bst_abi_version(), ABI_BST_VERSION)):
-        if got != want:
-            raise RecalgoError(f"{path}: {what} version {got}, this binding expects {want} "
+        got = getattr(lib, abi.version_query)()
+        if got != abi.version:
+            raise RecalgoError(f"{path}: {abi.label} version {got}, this binding expects {abi.version} "
                                "(a stale build: python -m recalgorithm_amd.build)")
     _lib = lib
     return lib

@@ -2109,12 +2109,12 @@ def gate_mix(x: torch.Tensor, gate_kernels, experts, selection=None, x_grad_sink
 # =============================================================================================
 # PLE (csrc/cgc.hip, include/recalgo_cgc.h): the CGC block — wide softmax gates + expert mix, optionally summed
 # =============================================================================================
-_CC = _lib.ABI_CGC.constants                 # the RECALGO_CGC_* #defines of include/recalgo_cgc.h
+_CC = _lib.HEADERS["recalgo_cgc.h"].constants                 # the RECALGO_CGC_* #defines of include/recalgo_cgc.h
 CGC_MAX_EXPERTS = _CC["RECALGO_CGC_MAX_EXPERTS"]
 CGC_MAX_GATES = _CC["RECALGO_CGC_MAX_GATES"]
 # include/recalgo_wide.h (the op itself lives in wide.py)
-WIDE_HASH_KEY = _lib.ABI_WIDE.constants["RECALGO_WIDE_HASH_KEY"]
-WIDE_MAX_BUCKETS = _lib.ABI_WIDE.constants["RECALGO_WIDE_MAX_BUCKETS"]
+_CW = _lib.HEADERS["recalgo_wide.h"].constants
+WIDE_HASH_KEY, WIDE_MAX_BUCKETS = _CW["RECALGO_WIDE_HASH_KEY"], _CW["RECALGO_WIDE_MAX_BUCKETS"]
 
 
 class _CgcMixFn(Function):
@@ -2445,7 +2445,7 @@ def adam_tf1_step_(flat, flat_grad, flat_m, flat_v, arenas, step_dev: torch.Tens
 # =============================================================================================
 # BST (csrc/bst.hip, include/recalgo_bst.h): the transformer block — attention + LayerNorm, FFN + LayerNorm (+ pooling)
 # =============================================================================================
-_CB = _lib.ABI_BST.constants                 # the RECALGO_BST_* #defines of include/recalgo_bst.h
+_CB = _lib.HEADERS["recalgo_bst.h"].constants                 # the RECALGO_BST_* #defines of include/recalgo_bst.h
 BST_MAX_T, BST_MAX_D, BST_MAX_HEADS = _CB["RECALGO_BST_MAX_T"], _CB["RECALGO_BST_MAX_D"], _CB["RECALGO_BST_MAX_HEADS"]
 _bst_shared = {}             # id(Variable) -> how many blocks of the running step read it (position_embedding: every block
 #                              adds it again); the block whose backward runs first overwrites its gradient, the others add

@@ -20,7 +20,7 @@ from torch.autograd import Function
 from . import _lib
 from .variables import Variable, VariableStore
 
-_C = _lib.ABI_WIDE.constants
+_C = _lib.HEADERS["recalgo_wide.h"].constants
 HASH_KEY = _C["RECALGO_WIDE_HASH_KEY"]
 MAX_BUCKETS = _C["RECALGO_WIDE_MAX_BUCKETS"]
 APPLY_FTRL, APPLY_GRAD = _C["RECALGO_WIDE_APPLY_FTRL"], _C["RECALGO_WIDE_APPLY_GRAD"]

@@ -90,6 +90,46 @@ def test_known_answers_structs_and_constants():
     assert abi.constants == {"RECALGO_DEC": 16, "RECALGO_HEX": 256, "RECALGO_NEG": -1, "RECALGO_ABI_VERSION": 7}
 
 
+def test_declaration_hash_known_answers():
+    """what a version covers: the declarations, not the comments, the layout of the text or the version's own number"""
+    h = _abi.declaration_hash("recalgo_t.h", text=KNOWN)
+    assert h == "402ecdeb3dab77280ac0a3175cf20cddd380f112e35b70f1cbd554fe2c208d84"
+    same = [KNOWN.replace("/* hipStream_t */", "/* a stream;\n int recalgo_x(int a); */"),
+            KNOWN.replace("void* recalgo_open(const char* path, ", "void*   recalgo_open(const char* path,\n\t"),
+            KNOWN.replace("#define RECALGO_ABI_VERSION 7", "#define RECALGO_ABI_VERSION 12"),
+            "\n\n" + KNOWN + "  \n"]
+    assert [_abi.declaration_hash("recalgo_t.h", text=t) for t in same] == [h] * 4 and len(set(same + [KNOWN])) == 5
+    other = [KNOWN.replace("uint64_t n, uint32_t seed", "uint32_t n, uint32_t seed"),               # one parameter's type
+             KNOWN.replace("int32_t a, int64_t b,", "int64_t b, int32_t a,"),                          # two parameters' order
+             KNOWN.replace("#define RECALGO_DEC 16", "#define RECALGO_DEC 17"),                       # a constant that is no version
+             KNOWN.replace("int n_ex, F;", "int F, n_ex;")]                                            # a struct's field order
+    hashes = [_abi.declaration_hash("recalgo_t.h", text=t) for t in other]
+    assert h not in hashes and len(set(hashes)) == 4
+    # a keyed header's version define goes by the same rule (the whole line: name and number)
+    keyed = KNOWN.replace("RECALGO_ABI_VERSION 7", "RECALGO_T9_ABI_VERSION 8")
+    assert keyed != KNOWN and _abi.declaration_hash("recalgo_t.h", text=keyed) == h
+
+
+@pytest.mark.parametrize("text, found", [
+    ("int recalgo_abi_version(void);", r"found \[\] and \['recalgo_abi_version'\]"),                                # no define
+    ("#define RECALGO_ABI_VERSION 1\nint recalgo_f(void);", r"found \['RECALGO_ABI_VERSION'\] and \[\]"),           # no function
+    ("#define RECALGO_X_ABI_VERSION 1\nint recalgo_abi_version(void);", "found"),                                  # another key's
+    ("#define RECALGO_ABI_VERSION 1\n#define RECALGO_X_ABI_VERSION 1\nint recalgo_abi_version(void);", "found"),    # two defines
+    ("#define RECALGO_X_ABI_VERSION 1\nint recalgo_x_abi_version(void);\nint recalgo_abi_version(void);", "found"),   # two functions
+])
+def test_a_table_header_without_one_version_pair_raises_and_names_the_header(text, found, monkeypatch):
+    monkeypatch.setattr(_abi, "read", lambda header: _abi.parse(text, header))
+    with pytest.raises(_lib.RecalgoError, match=r"^include/recalgo_t\.h: .*" + found):
+        _lib._versioned("recalgo_t.h")
+    assert not hasattr(_abi.parse(text), "version")          # parse itself takes text without a version pair as it is
+
+
+def test_a_table_header_with_its_version_pair():
+    assert _lib.HEADERS["recalgo.h"].version == 5 and _lib.HEADERS["recalgo.h"].version_query == "recalgo_abi_version"
+    assert [(h, a.label) for h, a in _lib.HEADERS.items()][:4] == [
+        ("recalgo.h", "ABI"), ("recalgo_cgc.h", "CGC ABI"), ("recalgo_wide.h", "WIDE ABI"), ("recalgo_bst.h", "BST ABI")]
+
+
 @pytest.mark.parametrize("bad, line", [
     ("int recalgo_f(long n);", 1),                                        # a type outside the table: parameter,
     ("\nlong recalgo_f(int n);", 2),                                      # return type,

@@ -1,15 +1,14 @@
 """CPU (no kernels launched): the BST feature's host side.
   * the mask rule tests/bst_ref.py restates: query rows >= keys_length have a softmax of exactly 1/T in float32 and still
     pass a gradient to Q and K; the float64 run models that step;
-  * include/recalgo_bst.h, the fourth ABI header: declared = bound = exported, errcheck on its launches, constants
-    re-exported, include/recalgo_bst.abi at the header's version with the header's hash;
+  * include/recalgo_bst.h, the fourth ABI header: its names, signatures, launches, sizes and constants, literally, and the
+    constants re-exported (the checks every header gets, include/recalgo_bst.abi among them: tests/test_abi.py);
   * tests/bst_ref.py reproduces both goldens scripts/gen_golden_bst.py obtained by executing the reference's own bst.py on
     oracle/tf1_shim (predictions, loss, every gradient, the Adam step, the moving statistics, EVAL), the generator's --check
     round trip (where the reference folder exists);
   * the mirror's variables, flags and call surface on the launch-free registration pass; what --static_sequence_length
     changes and when it changes nothing."""
 import ctypes
-import hashlib
 import os
 import re
 
@@ -68,45 +67,25 @@ def test_float32_add_absorbs_and_float64_does_not():
     assert torch.all(R.add_mask(s.double(), kl) == R.MASK_ADD)
 
 
-# ---- include/recalgo_bst.h: the checks tests/test_wdl_host.py makes on recalgo_wide.h -----------------------------------------------
+# ---- include/recalgo_bst.h: what this feature expects of its header, literally (every generic check: tests/test_abi.py) -----------
 DECLARED = ["recalgo_bst_abi_version", "recalgo_bst_supported", "recalgo_bst_attn_bwd_partial_rows",
             "recalgo_bst_attn_bwd_workspace_bytes", "recalgo_bst_ffn_bwd_partial_rows", "recalgo_bst_ffn_bwd_workspace_bytes",
             "recalgo_bst_attn_fwd", "recalgo_bst_attn_bwd", "recalgo_bst_ffn_fwd", "recalgo_bst_ffn_bwd"]
 LAUNCHES = ["recalgo_bst_attn_fwd", "recalgo_bst_attn_bwd", "recalgo_bst_ffn_fwd", "recalgo_bst_ffn_bwd"]
 
 
-def declared_functions():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(recalgo_[a-z0-9_]+)\s*\(", src)))
-
-
-def declaration_hash():
-    """sha256 over the header's declarations: comments, the version number and white space removed."""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    src = re.sub(r"#define RECALGO_BST_ABI_VERSION \d+", "", src)
-    return hashlib.sha256(re.sub(r"\s+", " ", src).strip().encode()).hexdigest()
-
-
-def test_fourth_header_is_bound_and_exported():
-    from recalgorithm_amd import _abi, _lib, build
-    lib_path = build.build(verbose=False)
-    declared = declared_functions()
-    assert declared == sorted(DECLARED)
-    assert set(_lib.ABI_BST.functions) == set(declared)
-    others = set(_lib.SIGNATURES) | set(_lib.ABI_CGC.functions) | set(_lib.ABI_WIDE.functions)
-    assert not set(_lib.ABI_BST.functions) & others, "the other tables stay what they are"
-    assert _lib.ABI_BST.launches == LAUNCHES
-    assert not _lib.ABI_BST.structs
-    raw = ctypes.CDLL(lib_path)
-    assert not [f for f in declared if not hasattr(raw, f)], "declared in recalgo_bst.h but not exported"
+def test_fourth_header_literal_expectations():
+    from recalgorithm_amd import _lib, build, ops
+    build.build(verbose=False)
+    abi = _lib.HEADERS["recalgo_bst.h"]
+    assert sorted(abi.functions) == sorted(DECLARED)
+    assert abi.launches == LAUNCHES
+    assert not abi.structs
     lib = _lib.load()
-    assert lib.recalgo_bst_abi_version() == _lib.ABI_BST_VERSION == 1
-    for name, (res, args) in _lib.ABI_BST.functions.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-        assert (fn.errcheck is not None) == (name in LAUNCHES), name
+    assert lib.recalgo_bst_abi_version() == abi.version == 1
     c_int, i64, ptr = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
-    F = _lib.ABI_BST.functions
+    F = abi.functions
+    assert F["recalgo_bst_abi_version"] == (c_int, []) and F["recalgo_bst_ffn_bwd_partial_rows"] == (c_int, [c_int])
     assert F["recalgo_bst_supported"] == (c_int, [c_int] * 3) and F["recalgo_bst_attn_bwd_partial_rows"] == (c_int, [c_int])
     assert F["recalgo_bst_attn_bwd_workspace_bytes"] == (i64, [c_int] * 4) and F["recalgo_bst_ffn_bwd_workspace_bytes"] == (i64, [c_int] * 2)
     assert F["recalgo_bst_attn_fwd"] == (c_int, [ptr] * 9 + [c_int] * 4 + [ptr] * 3)
@@ -129,42 +108,11 @@ def test_fourth_header_is_bound_and_exported():
         lib.recalgo_bst_ffn_fwd(*([None] * 5), 1, 1, 4, 0, None, None, None, None)
     with pytest.raises(_lib.RecalgoError, match="recalgo_bst_ffn_bwd failed with hipError_t=1$"):
         lib.recalgo_bst_ffn_bwd(*([None] * 6), 1, 1, 4, 0, *([None] * 7))
-    text = open(HEADER).read()
-    assert "typedef void* recalgo_stream_t;" in text and '#include "recalgo.h"' not in text
-    assert _abi.read("recalgo_bst.h").constants == _lib.ABI_BST.constants
-
-
-def test_fourth_header_constants_are_re_exported():
-    from recalgorithm_amd import _lib, ops
     defines = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define (RECALGO_BST_\w+) (0x[0-9A-Fa-f]+|\d+)", open(HEADER).read())
                if not m.group(1).endswith("_H_")}
-    assert defines == {"RECALGO_BST_ABI_VERSION": 1, "RECALGO_BST_MAX_T": 64, "RECALGO_BST_MAX_D": 16, "RECALGO_BST_MAX_HEADS": 4}
-    assert _lib.ABI_BST.constants == defines
+    assert abi.constants == defines == {"RECALGO_BST_ABI_VERSION": 1, "RECALGO_BST_MAX_T": 64, "RECALGO_BST_MAX_D": 16,
+                                        "RECALGO_BST_MAX_HEADS": 4}
     assert (ops.BST_MAX_T, ops.BST_MAX_D, ops.BST_MAX_HEADS) == (64, 16, 4)
-    for other in (_lib.CONSTANTS, _lib.ABI_CGC.constants, _lib.ABI_WIDE.constants):
-        assert not [k for k in other if k.startswith("RECALGO_BST_")]
-
-
-def test_fourth_header_declarations_do_not_change_without_a_version_bump():
-    """include/recalgo_bst.abi: one `version sha256` line per version, the convention of include/recalgo.abi"""
-    version = int(re.search(r"#define RECALGO_BST_ABI_VERSION (\d+)", open(HEADER).read()).group(1))
-    recorded = dict((int(v), h) for v, h in (ln.split() for ln in open(os.path.join(ROOT, "include", "recalgo_bst.abi"))
-                                             if ln.strip() and not ln.startswith("#")))
-    h = declaration_hash()
-    assert version == max(recorded), f"recalgo_bst.h is at version {version}, include/recalgo_bst.abi ends at {max(recorded)}"
-    assert recorded[version] == h, (
-        f"the declarations of include/recalgo_bst.h changed (sha256 {h}) but RECALGO_BST_ABI_VERSION is still {version}: bump "
-        f"it and append `<version> {h}` to include/recalgo_bst.abi")
-    assert len(set(recorded.values())) == len(recorded), "two versions with identical declarations"
-
-
-def test_stale_fourth_header_version_fails_loudly(monkeypatch):
-    from recalgorithm_amd import _lib, build
-    build.build(verbose=False)
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "ABI_BST_VERSION", _lib.ABI_BST_VERSION + 1)
-    with pytest.raises(_lib.RecalgoError, match="BST ABI version 1, this binding expects 2"):
-        _lib.load()
 
 
 # ---- the goldens: tests/bst_ref.py against the reference's own sources run on oracle/tf1_shim ------------------------------------

@@ -6,11 +6,10 @@
   * the generator's --check round trip (where the reference folder exists);
   * the two properties of FTRL the sparse update rests on;
   * the mirror's variables, flags, columns and parse spec on the launch-free registration pass;
-  * include/recalgo_wide.h, the third ABI header: declared = bound, exported, errcheck on its launches, constants
-    re-exported, include/recalgo_wide.abi at the header's version with the header's hash;
+  * include/recalgo_wide.h, the third ABI header: its names, signatures, launches, sizes and constants, literally, and the
+    constants re-exported (the checks every header gets, include/recalgo_wide.abi among them: tests/test_abi.py);
   * the FTRL slots under TF's names through the checkpoint writer."""
 import ctypes
-import hashlib
 import os
 import re
 import subprocess
@@ -308,41 +307,21 @@ def test_data_parallel_is_refused_clearly(tmp_path):
         other.build(feats, {"read_comment": labels.float()})
 
 
-# ---- 6. include/recalgo_wide.h: the checks tests/test_ple_host.py makes on recalgo_cgc.h ----------------------------------------
-def declared_functions():
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(recalgo_[a-z0-9_]+)\s*\(", src)))
-
-
-def declaration_hash():
-    """sha256 over the header's declarations: comments, the version number and white space removed."""
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    src = re.sub(r"#define RECALGO_WIDE_ABI_VERSION \d+", "", src)
-    return hashlib.sha256(re.sub(r"\s+", " ", src).strip().encode()).hexdigest()
-
-
-def test_third_header_is_bound_and_exported():
-    from recalgorithm_amd import _abi, _lib, build
-    lib_path = build.build(verbose=False)
-    declared = declared_functions()
-    assert declared == sorted(["recalgo_wide_abi_version", "recalgo_wide_workspace_bytes", "recalgo_wide_state_workspace_bytes",
-                               "recalgo_wide_cross_fwd", "recalgo_wide_cross_plan", "recalgo_wide_cross_apply",
-                               "recalgo_wide_cross_reset"])
-    assert set(_lib.ABI_WIDE.functions) == set(declared)
-    assert not set(_lib.ABI_WIDE.functions) & (set(_lib.SIGNATURES) | set(_lib.ABI_CGC.functions)), "the other tables stay what they are"
-    assert _lib.ABI_WIDE.launches == ["recalgo_wide_cross_fwd", "recalgo_wide_cross_plan", "recalgo_wide_cross_apply",
-                                      "recalgo_wide_cross_reset"]
-    assert not _lib.ABI_WIDE.structs
-    raw = ctypes.CDLL(lib_path)
-    assert not [f for f in declared if not hasattr(raw, f)], "declared in recalgo_wide.h but not exported"
+# ---- 6. include/recalgo_wide.h: what this feature expects of its header, literally (every generic check: tests/test_abi.py) ----
+def test_third_header_literal_expectations():
+    from recalgorithm_amd import _lib, build, ops, wide
+    build.build(verbose=False)
+    abi = _lib.HEADERS["recalgo_wide.h"]
+    assert sorted(abi.functions) == sorted(["recalgo_wide_abi_version", "recalgo_wide_workspace_bytes",
+                                            "recalgo_wide_state_workspace_bytes", "recalgo_wide_cross_fwd", "recalgo_wide_cross_plan",
+                                            "recalgo_wide_cross_apply", "recalgo_wide_cross_reset"])
+    assert abi.launches == ["recalgo_wide_cross_fwd", "recalgo_wide_cross_plan", "recalgo_wide_cross_apply", "recalgo_wide_cross_reset"]
+    assert not abi.structs
     lib = _lib.load()
-    assert lib.recalgo_wide_abi_version() == _lib.ABI_WIDE_VERSION == 1
-    for name, (res, args) in _lib.ABI_WIDE.functions.items():
-        fn = getattr(lib, name)
-        assert fn.restype is res and list(fn.argtypes) == args, name
-        assert (fn.errcheck is not None) == (name in _lib.ABI_WIDE.launches), name
+    assert lib.recalgo_wide_abi_version() == abi.version == 1
     c_int, i64, u64, ptr, flt = ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_float
-    F = _lib.ABI_WIDE.functions
+    F = abi.functions
+    assert F["recalgo_wide_abi_version"] == (c_int, [])
     assert F["recalgo_wide_workspace_bytes"] == (i64, [c_int]) and F["recalgo_wide_state_workspace_bytes"] == (i64, [i64])
     assert F["recalgo_wide_cross_fwd"] == (c_int, [ptr, i64, ptr, ptr, i64, c_int, c_int, i64, u64, ptr, ptr, ptr, ptr, ptr, ptr])
     assert F["recalgo_wide_cross_plan"] == (c_int, [ptr, ptr, c_int, i64, ptr, ptr])
@@ -361,45 +340,12 @@ def test_third_header_is_bound_and_exported():
         lib.recalgo_wide_cross_apply(None, None, 1, 7, 0, *([None] * 8), 0.005, 0.0, 0.0, 0, None)
     with pytest.raises(_lib.RecalgoError, match="recalgo_wide_cross_reset failed with hipError_t=[1-9]"):
         lib.recalgo_wide_cross_reset(None, None, 1, None)
-    text = open(HEADER).read()
-    assert "typedef void* recalgo_stream_t;" in text and '#include "recalgo.h"' not in text
-    assert _abi.read("recalgo_wide.h").constants == _lib.ABI_WIDE.constants
-
-
-def test_third_header_constants_are_re_exported():
-    from recalgorithm_amd import _lib, ops, wide
     defines = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"#define (RECALGO_WIDE_\w+) (0x[0-9A-Fa-f]+|\d+)", open(HEADER).read())
                if not m.group(1).endswith("_H_")}
-    assert defines == {"RECALGO_WIDE_ABI_VERSION": 1, "RECALGO_WIDE_HASH_KEY": 0xDECAFCAFFE, "RECALGO_WIDE_MAX_BUCKETS": 2 ** 31 - 1,
-                       "RECALGO_WIDE_APPLY_FTRL": 0, "RECALGO_WIDE_APPLY_GRAD": 1}
-    assert _lib.ABI_WIDE.constants == defines
+    assert abi.constants == defines == {"RECALGO_WIDE_ABI_VERSION": 1, "RECALGO_WIDE_HASH_KEY": 0xDECAFCAFFE,
+                                        "RECALGO_WIDE_MAX_BUCKETS": 2 ** 31 - 1, "RECALGO_WIDE_APPLY_FTRL": 0, "RECALGO_WIDE_APPLY_GRAD": 1}
     assert ops.WIDE_HASH_KEY == wide.HASH_KEY == W.HASH_KEY == defines["RECALGO_WIDE_HASH_KEY"]
     assert ops.WIDE_MAX_BUCKETS == wide.MAX_BUCKETS == defines["RECALGO_WIDE_MAX_BUCKETS"]
-    # the other headers' tables are untouched by the third
-    assert _lib.CONSTANTS is _lib.ABI.constants and not [k for k in _lib.CONSTANTS if k.startswith("RECALGO_WIDE_")]
-    assert not [k for k in _lib.ABI_CGC.constants if k.startswith("RECALGO_WIDE_")]
-
-
-def test_third_header_declarations_do_not_change_without_a_version_bump():
-    """include/recalgo_wide.abi: one `version sha256` line per version, the convention of include/recalgo.abi"""
-    version = int(re.search(r"#define RECALGO_WIDE_ABI_VERSION (\d+)", open(HEADER).read()).group(1))
-    recorded = dict((int(v), h) for v, h in (ln.split() for ln in open(os.path.join(ROOT, "include", "recalgo_wide.abi"))
-                                             if ln.strip() and not ln.startswith("#")))
-    h = declaration_hash()
-    assert version == max(recorded), f"recalgo_wide.h is at version {version}, include/recalgo_wide.abi ends at {max(recorded)}"
-    assert recorded[version] == h, (
-        f"the declarations of include/recalgo_wide.h changed (sha256 {h}) but RECALGO_WIDE_ABI_VERSION is still {version}: bump "
-        f"it and append `<version> {h}` to include/recalgo_wide.abi")
-    assert len(set(recorded.values())) == len(recorded), "two versions with identical declarations"
-
-
-def test_stale_third_header_version_fails_loudly(monkeypatch):
-    from recalgorithm_amd import _lib, build
-    build.build(verbose=False)
-    monkeypatch.setattr(_lib, "_lib", None)
-    monkeypatch.setattr(_lib, "ABI_WIDE_VERSION", _lib.ABI_WIDE_VERSION + 1)
-    with pytest.raises(_lib.RecalgoError, match="WIDE ABI version 1, this binding expects 2"):
-        _lib.load()
 
 
 # ---- 7. the slots through the checkpoints ------------------------------------------------------------------------------------------
