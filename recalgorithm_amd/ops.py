@@ -10,7 +10,7 @@ Parameter gradients are written by the kernels directly into `Variable.grad` /
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 from torch.autograd import Function
@@ -1979,15 +1979,33 @@ def _colsum_now(jobs, device_tensor: torch.Tensor) -> None:
     _lib_().recalgo_dense_bwd_weights_reduce((_DenseSplit * 1)(), 0, sums, len(jobs), None, _stream(device_tensor))
 
 
-class GateMixSpec:
-    """What `_GateMixFn` / `_CgcMixFn` need besides their tensors: the gate kernels (Variables: the gradient goes to Variable.grad
-    through the step's deferred column sums; tensors: returned by backward), the selection table, whether the experts are ReLU
-    outputs whose gradient the op masks, where the gates' share of d x goes (x_grad_sink.first instead of autograd), and
-    (`_CgcMixFn` only) whether the G outputs are summed into one."""
+class _MixEntry(NamedTuple):
+    """What differs between the two gate-mix ops (`gate_mix`: csrc/mmoe.hip, include/recalgo.h; `cgc_mix`: csrc/cgc.hip,
+    include/recalgo_cgc.h) around their one autograd Function and their one argument check."""
+    op: str                     # the public op's name: the prefix of every error text
+    fwd: str                    # the forward entry point
+    bwd: str                    # the backward entry point
+    partial_rows: Callable      # (lib, B, In, n_total) -> rows of the backward's gate-kernel partials
+    has_sum_outputs: bool       # the ABI carries `sum_outputs` (after H, in both entries)
+    skip_unused_backward: bool  # a backward whose upstream gradients are all None launches nothing
+    strict_gates: bool          # the argument check also refuses G < 1 and a gate kernel that is not 2-d
 
-    def __init__(self, kernels, selection, relu_sources, x_grad_sink, sum_outputs: bool = False):
+
+_GATE_MIX = _MixEntry("gate_mix", "recalgo_gate_mix_fwd", "recalgo_gate_mix_bwd",
+                      lambda lib, B, In, n_total: lib.recalgo_gate_mix_partial_rows(B), False, False, False)
+_CGC_MIX = _MixEntry("cgc_mix", "recalgo_cgc_fwd", "recalgo_cgc_bwd",
+                     lambda lib, B, In, n_total: lib.recalgo_cgc_partial_rows(B, In, n_total), True, True, True)
+
+
+class GateMixSpec:
+    """What `_MixFn` needs besides its tensors: the gate kernels (Variables: the gradient goes to Variable.grad
+    through the step's deferred column sums; tensors: returned by backward), the selection table, whether the experts are ReLU
+    outputs whose gradient the op masks, where the gates' share of d x goes (x_grad_sink.first instead of autograd),
+    (`cgc_mix` only) whether the G outputs are summed into one, and which of the two ops' entry points serve it."""
+
+    def __init__(self, kernels, selection, relu_sources, x_grad_sink, sum_outputs: bool = False, entry: _MixEntry = _GATE_MIX):
         self.kernels, self.selection, self.relu_sources, self.x_grad_sink = kernels, selection, relu_sources, x_grad_sink
-        self.sum_outputs = bool(sum_outputs)
+        self.sum_outputs, self.entry = bool(sum_outputs), entry
         self.n_sel = (ctypes.c_int * len(selection))(*[len(s) for s in selection])
         flat = [int(e) for s in selection for e in s]
         self.sel = (ctypes.c_int * len(flat))(*flat)
@@ -2022,8 +2040,9 @@ def _mix_backward_tail(spec: GateMixSpec, ws, need_w, partials, rows, x, dx, dex
     return (None, None, dx, *dex, *dws)
 
 
-class _GateMixFn(Function):
-    """include/recalgo.h recalgo_gate_mix_fwd / recalgo_gate_mix_bwd: G outputs [B, H]."""
+class _MixFn(Function):
+    """The softmax gates + expert mix of either op (spec.entry): include/recalgo.h recalgo_gate_mix_fwd / recalgo_gate_mix_bwd,
+    G outputs [B, H]; include/recalgo_cgc.h recalgo_cgc_fwd / recalgo_cgc_bwd, G outputs or their sum as ONE (spec.sum_outputs)."""
 
     @staticmethod
     def forward(ctx, anchor, spec: GateMixSpec, x, *tensors):
@@ -2033,10 +2052,11 @@ class _GateMixFn(Function):
         ws = [k.data if isinstance(k, Variable) else t for k, t in zip(spec.kernels, gate_ts)]
         B, In = x.shape
         E, H = len(experts), experts[0].shape[1]
-        outs = [torch.empty(B, H, device=x.device, dtype=torch.float32) for _ in range(G)]
+        outs = [torch.empty(B, H, device=x.device, dtype=torch.float32) for _ in range(1 if spec.sum_outputs else G)]
         p = torch.empty(B, spec.n_total, device=x.device, dtype=torch.float32)
-        _lib_().recalgo_gate_mix_fwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts),
-                                     B, In, E, G, H, _ptr_array(outs), _p(p), _stream(x))
+        summed = (int(spec.sum_outputs),) if spec.entry.has_sum_outputs else ()
+        getattr(_lib_(), spec.entry.fwd)(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts),
+                                         B, In, E, G, H, *summed, _ptr_array(outs), _p(p), _stream(x))
         ctx.spec, ctx.ws, ctx.E = spec, ws, E
         ctx.save_for_backward(x, p, *experts)
         ctx.mark_non_differentiable(p)
@@ -2047,7 +2067,10 @@ class _GateMixFn(Function):
         spec, ws, E = ctx.spec, ctx.ws, ctx.E
         x, p, *experts = ctx.saved_tensors
         G = len(ws)
-        gs = [None if g is None else (g if g.is_contiguous() else g.contiguous()) for g in grads[:G]]
+        M = 1 if spec.sum_outputs else G
+        gs = [None if g is None else (g if g.is_contiguous() else g.contiguous()) for g in grads[:M]]
+        if spec.entry.skip_unused_backward and all(g is None for g in gs):
+            return (None,) * (3 + E + G)
         B, In = x.shape
         H = experts[0].shape[1]
         lib = _lib_()
@@ -2055,12 +2078,44 @@ class _GateMixFn(Function):
         need_e = ctx.needs_input_grad[3:3 + E]
         dx = torch.empty(B, In, device=x.device, dtype=torch.float32) if need_x else None
         dex = [torch.empty_like(t) if nd else None for t, nd in zip(experts, need_e)]
-        rows = int(lib.recalgo_gate_mix_partial_rows(B))
+        rows = int(spec.entry.partial_rows(lib, B, In, spec.n_total))
         partials = torch.empty(rows, In * spec.n_total, device=x.device, dtype=torch.float32)
         relu = spec.relu_sources is not None
-        lib.recalgo_gate_mix_bwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts), _p(p),
-                                 _ptr_array(gs), B, In, E, G, H, int(relu), _ptr_array(dex), _p(dx), In, _p(partials), _stream(x))
+        summed = (int(spec.sum_outputs),) if spec.entry.has_sum_outputs else ()
+        getattr(lib, spec.entry.bwd)(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts), _p(p),
+                                     _ptr_array(gs), B, In, E, G, H, *summed, int(relu), _ptr_array(dex), _p(dx), In,
+                                     _p(partials), _stream(x))
         return _mix_backward_tail(spec, ws, ctx.needs_input_grad[3 + E:], partials, rows, x, dx, dex)
+
+
+def _mix_check(entry: _MixEntry, x, gate_kernels, experts, selection) -> int:
+    """The shape checks both ops make before they ask their `_supported` query (-> H): ValueError, prefixed by the op's name."""
+    op, E, G = entry.op, len(experts), len(gate_kernels)
+    ws = [k.data if isinstance(k, Variable) else k for k in gate_kernels]
+    if x.dim() != 2 or (entry.strict_gates and G < 1) or len(selection) != G or \
+            any((entry.strict_gates and w.dim() != 2) or tuple(w.shape) != (x.shape[1], len(s)) for w, s in zip(ws, selection)):
+        raise ValueError(f"{op}: one [In, n_g] gate kernel per selection row")
+    if any(len(s) < 1 for s in selection) or any(e < 0 or e >= E for s in selection for e in s):
+        raise ValueError(f"{op}: every gate selects at least one expert, indices in [0, E)")
+    if E < 1 or any(t.dim() != 2 or t.shape != experts[0].shape or t.shape[0] != x.shape[0] for t in experts):
+        raise ValueError(f"{op}: experts must be E same-shaped [B, H] tensors")
+    return experts[0].shape[1]
+
+
+def _mix_launch(entry: _MixEntry, x, gate_kernels, experts, selection, sum_outputs, x_grad_sink, anchor):
+    """What both ops do once the shapes are inside their kernel's limits -> (outputs, gate probabilities)."""
+    if x.shape[0] == 0:
+        raise NotImplementedError(f"{entry.op}: empty batch")
+    x = _mat(x, "x")
+    for k in gate_kernels:
+        _chk(k.data if isinstance(k, Variable) else k, torch.float32, "gate kernel")
+    srcs = [getattr(t, "_recalgo_relu_src", None) if getattr(t, "_recalgo_relu_scale", 1.0) == 1.0 else None for t in experts]
+    srcs = srcs if all(s is not None for s in srcs) else None
+    experts = [_mat(t if t.is_contiguous() else t.contiguous(), "expert") for t in experts]
+    spec = GateMixSpec(gate_kernels, selection, srcs, x_grad_sink, sum_outputs=sum_outputs, entry=entry)
+    gate_ts = [None if isinstance(k, Variable) else k for k in gate_kernels]
+    *outs, p = _MixFn.apply(anchor, spec, x, *experts, *gate_ts)
+    return outs, p
 
 
 def gate_mix_supported(In: int, E: int, G: int, H: int, n_total: int) -> bool:
@@ -2079,30 +2134,13 @@ def gate_mix(x: torch.Tensor, gate_kernels, experts, selection=None, x_grad_sink
     gate_kernels, experts = list(gate_kernels), list(experts)
     E, G = len(experts), len(gate_kernels)
     selection = [list(range(E)) for _ in range(G)] if selection is None else [list(s) for s in selection]
-    ws = [k.data if isinstance(k, Variable) else k for k in gate_kernels]
-    if x.dim() != 2 or len(selection) != G or any(tuple(w.shape) != (x.shape[1], len(s)) for w, s in zip(ws, selection)):
-        raise ValueError("gate_mix: one [In, n_g] gate kernel per selection row")
-    if any(len(s) < 1 for s in selection) or any(e < 0 or e >= E for s in selection for e in s):
-        raise ValueError("gate_mix: every gate selects at least one expert, indices in [0, E)")
-    if E < 1 or any(t.dim() != 2 or t.shape != experts[0].shape or t.shape[0] != x.shape[0] for t in experts):
-        raise ValueError("gate_mix: experts must be E same-shaped [B, H] tensors")
-    H = experts[0].shape[1]
+    H = _mix_check(_GATE_MIX, x, gate_kernels, experts, selection)
     n_total = sum(len(s) for s in selection)
     if max(len(s) for s in selection) > GATE_MIX_MAX or not gate_mix_supported(x.shape[1], E, G, H, n_total):
         raise NotImplementedError(
             f"gate_mix serves H % 4 == 0, E, G, n_g <= {GATE_MIX_MAX}, In <= 512 and In * (sum n_g | 1) <= 4096; got In={x.shape[1]} "
             f"E={E} G={G} H={H} sum n_g={n_total}")
-    if x.shape[0] == 0:
-        raise NotImplementedError("gate_mix: empty batch")
-    x = _mat(x, "x")
-    for w in ws:
-        _chk(w, torch.float32, "gate kernel")
-    srcs = [getattr(t, "_recalgo_relu_src", None) if getattr(t, "_recalgo_relu_scale", 1.0) == 1.0 else None for t in experts]
-    srcs = srcs if all(s is not None for s in srcs) else None
-    experts = [_mat(t if t.is_contiguous() else t.contiguous(), "expert") for t in experts]
-    spec = GateMixSpec(gate_kernels, selection, srcs, x_grad_sink)
-    gate_ts = [None if isinstance(k, Variable) else k for k in gate_kernels]
-    *outs, p = _GateMixFn.apply(anchor, spec, x, *experts, *gate_ts)
+    outs, p = _mix_launch(_GATE_MIX, x, gate_kernels, experts, selection, False, x_grad_sink, anchor)
     return (outs, p) if return_gates else outs
 
 
@@ -2115,52 +2153,6 @@ CGC_MAX_GATES = _CC["RECALGO_CGC_MAX_GATES"]
 # include/recalgo_wide.h (the op itself lives in wide.py)
 _CW = _lib.HEADERS["recalgo_wide.h"].constants
 WIDE_HASH_KEY, WIDE_MAX_BUCKETS = _CW["RECALGO_WIDE_HASH_KEY"], _CW["RECALGO_WIDE_MAX_BUCKETS"]
-
-
-class _CgcMixFn(Function):
-    """include/recalgo_cgc.h recalgo_cgc_fwd / recalgo_cgc_bwd: G outputs [B, H], or their sum as ONE (spec.sum_outputs)."""
-
-    @staticmethod
-    def forward(ctx, anchor, spec: GateMixSpec, x, *tensors):
-        ctx.set_materialize_grads(False)     # a gate nobody differentiates: NULL upstream gradient, no zero tensor
-        G = len(spec.kernels)
-        experts, gate_ts = tensors[:len(tensors) - G], tensors[len(tensors) - G:]
-        ws = [k.data if isinstance(k, Variable) else t for k, t in zip(spec.kernels, gate_ts)]
-        B, In = x.shape
-        E, H = len(experts), experts[0].shape[1]
-        outs = [torch.empty(B, H, device=x.device, dtype=torch.float32) for _ in range(1 if spec.sum_outputs else G)]
-        p = torch.empty(B, spec.n_total, device=x.device, dtype=torch.float32)
-        _lib_().recalgo_cgc_fwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts),
-                                B, In, E, G, H, int(spec.sum_outputs), _ptr_array(outs), _p(p), _stream(x))
-        ctx.spec, ctx.ws, ctx.E = spec, ws, E
-        ctx.save_for_backward(x, p, *experts)
-        ctx.mark_non_differentiable(p)
-        return (*outs, p)
-
-    @staticmethod
-    def backward(ctx, *grads):
-        spec, ws, E = ctx.spec, ctx.ws, ctx.E
-        x, p, *experts = ctx.saved_tensors
-        G = len(ws)
-        M = 1 if spec.sum_outputs else G
-        gs = [None if g is None else (g if g.is_contiguous() else g.contiguous()) for g in grads[:M]]
-        n_in = 3 + E + G
-        if all(g is None for g in gs):
-            return (None,) * n_in
-        B, In = x.shape
-        H = experts[0].shape[1]
-        lib = _lib_()
-        need_x = ctx.needs_input_grad[2]
-        need_e = ctx.needs_input_grad[3:3 + E]
-        dx = torch.empty(B, In, device=x.device, dtype=torch.float32) if need_x else None
-        dex = [torch.empty_like(t) if nd else None for t, nd in zip(experts, need_e)]
-        rows = int(lib.recalgo_cgc_partial_rows(B, In, spec.n_total))
-        partials = torch.empty(rows, In * spec.n_total, device=x.device, dtype=torch.float32)
-        relu = spec.relu_sources is not None
-        lib.recalgo_cgc_bwd(_p(x), x.stride(0), _ptr_array(ws), spec.n_sel, spec.sel, _ptr_array(experts), _p(p),
-                            _ptr_array(gs), B, In, E, G, H, int(spec.sum_outputs), int(relu), _ptr_array(dex), _p(dx), In,
-                            _p(partials), _stream(x))
-        return _mix_backward_tail(spec, ws, ctx.needs_input_grad[3 + E:], partials, rows, x, dx, dex)
 
 
 def cgc_supported(In: int, E: int, G: int, H: int, n_total: int, n_max: int) -> bool:
@@ -2180,31 +2172,13 @@ def cgc_mix(x: torch.Tensor, gate_kernels, experts, selection, sum_outputs: bool
     gate_kernels, experts = list(gate_kernels), list(experts)
     E, G = len(experts), len(gate_kernels)
     selection = [list(s) for s in selection]
-    ws = [k.data if isinstance(k, Variable) else k for k in gate_kernels]
-    if x.dim() != 2 or G < 1 or len(selection) != G or \
-            any(w.dim() != 2 or tuple(w.shape) != (x.shape[1], len(s)) for w, s in zip(ws, selection)):
-        raise ValueError("cgc_mix: one [In, n_g] gate kernel per selection row")
-    if any(len(s) < 1 for s in selection) or any(e < 0 or e >= E for s in selection for e in s):
-        raise ValueError("cgc_mix: every gate selects at least one expert, indices in [0, E)")
-    if E < 1 or any(t.dim() != 2 or t.shape != experts[0].shape or t.shape[0] != x.shape[0] for t in experts):
-        raise ValueError("cgc_mix: experts must be E same-shaped [B, H] tensors")
-    H = experts[0].shape[1]
+    H = _mix_check(_CGC_MIX, x, gate_kernels, experts, selection)
     n_total, n_max = sum(len(s) for s in selection), max(len(s) for s in selection)
     if not cgc_supported(x.shape[1], E, G, H, n_total, n_max):
         raise NotImplementedError(
             f"cgc_mix serves H % 4 == 0, E <= {CGC_MAX_EXPERTS}, G <= {CGC_MAX_GATES}, n_g <= {CGC_MAX_EXPERTS}, In <= 512 and "
             f"In * (sum n_g | 1) <= 20480; got In={x.shape[1]} E={E} G={G} H={H} sum n_g={n_total} max n_g={n_max}")
-    if x.shape[0] == 0:
-        raise NotImplementedError("cgc_mix: empty batch")
-    x = _mat(x, "x")
-    for w in ws:
-        _chk(w, torch.float32, "gate kernel")
-    srcs = [getattr(t, "_recalgo_relu_src", None) if getattr(t, "_recalgo_relu_scale", 1.0) == 1.0 else None for t in experts]
-    srcs = srcs if all(s is not None for s in srcs) else None
-    experts = [_mat(t if t.is_contiguous() else t.contiguous(), "expert") for t in experts]
-    spec = GateMixSpec(gate_kernels, selection, srcs, x_grad_sink, sum_outputs=sum_outputs)
-    gate_ts = [None if isinstance(k, Variable) else k for k in gate_kernels]
-    *outs, p = _CgcMixFn.apply(anchor, spec, x, *experts, *gate_ts)
+    outs, p = _mix_launch(_CGC_MIX, x, gate_kernels, experts, selection, sum_outputs, x_grad_sink, anchor)
     outs = outs[0] if sum_outputs else outs
     return (outs, p) if return_gates else outs
 

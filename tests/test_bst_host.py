@@ -121,12 +121,11 @@ import sys  # noqa: E402
 
 import numpy as np  # noqa: E402
 
-from oracle import ref_ops as O  # noqa: E402
 from tests import golden_util as GU  # noqa: E402
-from tests.test_mmoe_host import close, encode  # noqa: E402
+from tests.golden_protocol import GoldenCase, close, restate_on_host  # noqa: E402
+from tests.test_mmoe_host import encode  # noqa: E402
 
 GOLDENS = {"model_bst": 28, "model_bst_two_blocks_mean_dropout": 38}          # name -> gradient arrays
-TOL = 1e-10         # the bound of every comparison with a golden below (tests/test_wdl_host.py's)
 
 
 def mirror_setup(name, vocab_dir, **extra):
@@ -147,47 +146,26 @@ def mirror_setup(name, vocab_dir, **extra):
         "num_transformer_heads": int(fl["num_transformer_heads"]), "pooling_method": str(fl["pooling_method"])}, **extra)
 
 
+CASE = GoldenCase(mirror_setup=mirror_setup, oracle=R.bst, encode=encode, predictions={"probabilities": ("prob",)},
+                  ordered_prediction_keys=True, n_grads=GOLDENS, n_masks=2)
+
+
 @pytest.mark.parametrize("name", list(GOLDENS))
 def test_restatement_reproduces_the_golden(name, tmp_path):
     """The goldens are float64 (the shim's stand-in for tf.float32, the mask's float32 step modelled): the restatement runs in
-    float64, with the straight-through mask, at the bound tests/test_wdl_host.py uses."""
-    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    _, params = mirror_setup(name, vocab_dir)
-    d = GU.load(name)
-    sfeats, labels = GU.string_batch()
-    feats = encode(params, sfeats)
+    float64, with the straight-through mask, at the bound of every model's restatement."""
+    bn_state = {}
+    golden, run = restate_on_host(CASE, name, tmp_path, bn_state=bn_state)
+    feats, P, gg, ga = run["feats"], run["P"], golden.grad, golden.var_after
     lens = feats["his_read_comment_7d_seq"][1][1:] - feats["his_read_comment_7d_seq"][1][:-1]
     assert int(lens.min()) == 0 and int(lens.max()) == 8 and int((lens < 8).sum()) > 0, "the batch has padded rows and an empty history"
-    lab = {"read_comment": labels}
-    P = {k: torch.from_numpy(v.copy()).requires_grad_(not k.split("/")[-1].startswith("moving_")) for k, v in GU.section(d, "var/").items()}
-    out = R.bst(P, feats, None, params, training=False)
-    close(out["prob"], d["predict/probabilities"], f"{name} probabilities", tol=TOL)
-    masks = GU.dropout_masks(d)
-    assert len(masks) == (2 if float(params["dropout_rate"]) > 0 else 0)
-    bn_state = {}
-    out = R.bst(P, feats, lab, params, training=True, dropout_masks=masks, bn_state=bn_state)
-    close(out["loss"], d["train/loss"], f"{name} loss", tol=TOL)
-    out["loss"].backward()
-    gg, ga = GU.section(d, "grad/"), GU.section(d, "var_after/")
-    assert len(gg) == GOLDENS[name] and not [k for k in gg if k not in P]
-    lr = float(d["meta/learning_rate"])
-    for k, g in gg.items():
-        got = P[k].grad if P[k].grad is not None else torch.zeros_like(P[k])
-        close(got, g, f"{name} d({k})", tol=TOL)
-        p, gt = P[k].detach().clone(), torch.from_numpy(g.copy())
-        O.adam_tf1_step(p, gt, torch.zeros_like(p), torch.zeros_like(p), 1, lr)
-        close(p, ga[k], f"{name} adam({k})", tol=TOL)
     # the position embedding: rows nobody reads keep a zero gradient; with two blocks the read rows hold both blocks' share
     gpos = gg["transformer_part/position_embedding"]
     assert gpos.shape == (51, 16) and np.all(gpos[9:] == 0.0) and np.all(np.abs(gpos[:9]).sum(axis=1) > 0)
+    assert bn_state
     for scope, (mean, var) in bn_state.items():
-        close(0.99 * P[f"{scope}/moving_mean"].detach() + 0.01 * mean, ga[f"{scope}/moving_mean"], f"{name} {scope} moving_mean", tol=TOL)
-        close(0.99 * P[f"{scope}/moving_variance"].detach() + 0.01 * var, ga[f"{scope}/moving_variance"], f"{name} {scope} moving_variance", tol=TOL)
-    Pa = {k: torch.from_numpy(v.copy()) for k, v in ga.items()}
-    ev = R.bst(Pa, feats, lab, params, training=False)
-    close(ev["loss"], d["eval/loss"], f"{name} eval loss", tol=TOL)
-    close(((ev["prob"] >= 0.5).double() == labels).double().mean(), d["eval/accuracy"], f"{name} eval accuracy", tol=TOL)
-    close(O.tf_metrics_auc(labels, ev["prob"]), d["eval/auc"], f"{name} eval auc", tol=TOL)
+        close(0.99 * P[f"{scope}/moving_mean"].detach() + 0.01 * mean, ga[f"{scope}/moving_mean"], f"{name} {scope} moving_mean")
+        close(0.99 * P[f"{scope}/moving_variance"].detach() + 0.01 * var, ga[f"{scope}/moving_variance"], f"{name} {scope} moving_variance")
 
 
 def test_restatement_in_float32_stays_at_float32_distance_from_the_golden(tmp_path):
@@ -287,6 +265,6 @@ def test_static_sequence_length_equals_the_reference_exactly_when_a_history_is_f
     P = {k: torch.from_numpy(v.copy()) for k, v in GU.section(d, "var/").items()}
     full = R.bst(P, feats, None, dict(params, static_sequence_length=True, sequence_max_length=8), training=False)
     assert torch.equal(full["prob"], R.bst(P, feats, None, params, training=False)["prob"])
-    close(full["prob"], d["predict/probabilities"], "static T = longest history + 1", tol=TOL)
+    close(full["prob"], d["predict/probabilities"], "static T = longest history + 1")
     padded = R.bst(P, feats, None, dict(params, static_sequence_length=True), training=False)
     assert float((padded["prob"] - full["prob"]).abs().max()) > 1e-3

@@ -202,90 +202,20 @@ def test_autograd_ops_against_float64(dev, pooling):
 
 
 # ---- the model ------------------------------------------------------------------------------------------------------------------
-import numpy as np  # noqa: E402
-
 from recalgorithm_amd import feature_column as fc  # noqa: E402
 from recalgorithm_amd.estimator import HOUSEKEEPING_EVERY, Estimator, GraphedTrainStep, ModeKeys, RunConfig, _tree_tensors  # noqa: E402
 from recalgorithm_amd.io import synth  # noqa: E402
-from recalgorithm_amd.variables import named_grads  # noqa: E402
 from tests import golden_util as GU  # noqa: E402
-from tests.test_bst_host import GOLDENS, mirror_setup  # noqa: E402
+from tests.golden_protocol import check_on_device  # noqa: E402
+from tests.test_bst_host import CASE, GOLDENS, mirror_setup  # noqa: E402
 from tests.test_mmoe_host import encode  # noqa: E402
-from tests.util import assert_adam_update  # noqa: E402
 
 
 @pytest.mark.parametrize("name", list(GOLDENS))
 def test_model_golden(dev, name, tmp_path):
     """Both goldens through the mirrored bst_model_fn: variable names, PREDICT, loss, every gradient (the shared
     position_embedding's sum over two blocks among them), the Adam step, EVAL."""
-    from recalgorithm_amd import nn
-    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    model_fn, params = mirror_setup(name, vocab_dir)
-    d = GU.load(name)
-    sfeats, labels = GU.string_batch()
-    gv = GU.section(d, "var/")
-    # the reference arithmetic's own fp32 rounding on this batch: the restatement in float32 on the golden's variables
-    P32 = {k: torch.from_numpy(v.copy()).float().requires_grad_(not k.split("/")[-1].startswith("moving_")) for k, v in gv.items()}
-    f32 = {k: (v.float() if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in encode(params, sfeats).items()}
-    masks = GU.dropout_masks(d)
-    o32p = R.bst(P32, f32, None, params, training=False)
-    o32 = R.bst(P32, f32, {"read_comment": labels.float()}, params, training=True, dropout_masks=[m.float() for m in masks])
-    o32["loss"].backward()
-    g32 = {k: (p.grad if p.grad is not None else torch.zeros_like(p)) for k, p in P32.items()}
-    feats = {k: (v.float() if isinstance(v, torch.Tensor) else v) for k, v in sfeats.items()}
-    lab = {"read_comment": labels.float()}
-    est = Estimator(model_fn, params, RunConfig(device=dev, seed=3, use_hip_graph=False))
-    est.build(feats, lab)
-    feats, lab = est._to_device(feats, lab)
-    arrays = est.store.named_arrays()
-    assert not [k for k in gv if k not in arrays], "golden (reference) variables absent from the mirror"
-    assert not [k for k in arrays if k not in gv], "mirror variables the reference does not have"
-    for k, v in gv.items():
-        arrays[k].copy_(torch.from_numpy(v).float().reshape(arrays[k].shape))
-    before = {k: v.detach().cpu().double().clone() for k, v in est.store.named_arrays().items()}
-    pr = est._call_model_fn(feats, None, ModeKeys.PREDICT)
-    assert list(pr.predictions) == ["probabilities"]
-    assert_close(pr.predictions["probabilities"], torch.from_numpy(d["predict/probabilities"]), what=f"{name} predict/probabilities",
-                 ref32=o32p["prob"])
-    nn.DROPOUT_KEEP_MASKS[:] = masks
-    spec = est._call_model_fn(feats, lab, ModeKeys.TRAIN)
-    assert not nn.DROPOUT_KEEP_MASKS, "the mirror made fewer dropout calls than the reference"
-    assert_close(spec.loss, torch.from_numpy(d["train/loss"]), what=f"{name} loss", ref32=o32["loss"])
-    spec.loss.backward()
-    grads = named_grads(est.store)
-    gg = GU.section(d, "grad/")
-    assert sorted(gg) == sorted(k for k in grads if k in gg) and len(gg) == GOLDENS[name]
-    gmax = {k: float(np.abs(v).max()) for k, v in gg.items()}
-    # batch-summed gradients downstream of a BatchNorm cancel (sum_b g_b = 0): their fp32 error is set by the size of the
-    # terms, i.e. by the largest gradients of the dense stack (as tests/test_gpu_ple.py::test_model_golden)
-    dense_floor = 1e-6 * max(v for k, v in gmax.items() if "embedding_weights" not in k)
-    for k, g in gg.items():
-        sib = k.replace("/bias", "/kernel")
-        floor = dense_floor + (1e-5 * gmax[sib] if k.endswith("/bias") and sib in gmax else 0.0)
-        assert_close(grads[k], torch.from_numpy(g), what=f"{name} d({k})", reduced=True, floor=floor, ref32=g32.get(k))
-    spec.train_op.optimizer.apply_gradients(est.store)
-    after = est.store.named_arrays()
-    ga = GU.section(d, "var_after/")
-    lr = float(d["meta/learning_rate"])
-    for k, va in ga.items():
-        ref_upd = torch.from_numpy(va).reshape(before[k].shape) - torch.from_numpy(gv[k]).reshape(before[k].shape)
-        upd = after[k].detach().cpu().double() - before[k]
-        if "moving_" in k:                   # BatchNorm moving statistics (momentum 0.99), updated by the forward
-            assert_close(upd, ref_upd, what=f"{name} {k} update", reduced=True, floor=1e-7)
-            continue
-        gref = torch.from_numpy(gg[k]).reshape(before[k].shape).abs()
-        tol_g = 1e-5 * (gref + gref.pow(2).mean().sqrt()) + 1e-6 * gref.max() + dense_floor + \
-            (1e-5 * gmax.get(k.replace("/bias", "/kernel"), 0.0) if k.endswith("/bias") else 0.0)
-        assert_adam_update(upd, ref_upd, before[k], gref, tol_g, lr, what=f"{name} adam update {k}")
-    for k, v in ga.items():
-        after[k].copy_(torch.from_numpy(v).float().reshape(after[k].shape))
-    ev = est._call_model_fn(feats, lab, ModeKeys.EVAL)
-    assert_close(ev.loss, torch.from_numpy(d["eval/loss"]), what=f"{name} eval loss")
-    assert sorted(ev.eval_metric_ops) == ["eval_accuracy", "eval_auc"]
-    for kind in ("accuracy", "auc"):
-        m = ev.eval_metric_ops[f"eval_{kind}"][0]
-        m.update()
-        assert_close(torch.tensor(m.result()), torch.from_numpy(d[f"eval/{kind}"]), what=f"{name} eval {kind}")
+    check_on_device(dev, CASE, name, tmp_path)
 
 
 def make_bst(dev, B=256, history_len=20, blocks=2, heads=3, pooling="mean", dropout_rate=0.1, static=True, hidden=("64", "32"),

@@ -6,7 +6,6 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 import torch
 
@@ -14,15 +13,13 @@ from oracle import ref_ops as R
 from recalgorithm_amd import feature_column as fc
 from recalgorithm_amd.estimator import Estimator, GraphedTrainStep, ModeKeys, RunConfig
 from recalgorithm_amd.io import synth
-from recalgorithm_amd.variables import named_grads
-from tests import golden_util as GU
 from tests import mmoe_ref
-from tests.test_mmoe_host import GOLDENS, encode, mirror_setup, task_labels
-from tests.util import assert_adam_update, assert_bit_exact, assert_close
+from tests.golden_protocol import check_on_device, judge_step_against_oracle
+from tests.test_mmoe_host import CASE, GOLDENS, TASKS
+from tests.util import assert_bit_exact, assert_close
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TASKS = ["read_comment", "like", "click_avatar"]
 
 
 def ple_selection():
@@ -266,80 +263,7 @@ def test_multitask_loss_against_float64(dev, T, B):
 # ---- the model ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", GOLDENS)
 def test_model_golden(dev, name, tmp_path):
-    from recalgorithm_amd import nn
-    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    model_fn, params = mirror_setup(name, vocab_dir)
-    d = GU.load(name)
-    sfeats, labels = GU.string_batch()
-    lab64 = task_labels(d, labels, TASKS)
-    # the reference arithmetic's own fp32 rounding on this batch: the restatement in float32 on the golden's variables
-    gv = GU.section(d, "var/")
-    P32 = {k: torch.from_numpy(v.copy()).float().requires_grad_(True) for k, v in gv.items()}
-    f32 = {k: (v.float() if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in encode(params, sfeats).items()}
-    masks = GU.dropout_masks(d)
-    o32p = mmoe_ref.mmoe(P32, f32, None, params, training=False)
-    o32 = mmoe_ref.mmoe(P32, f32, {t: v.float() for t, v in lab64.items()}, params, training=True,
-                        dropout_masks=[m.float() for m in masks])
-    o32["loss"].backward()
-    g32 = {k: (p.grad if p.grad is not None else torch.zeros_like(p)) for k, p in P32.items()}
-    feats = {k: (v.float() if isinstance(v, torch.Tensor) else v) for k, v in sfeats.items()}
-    lab = {t: v.float() for t, v in lab64.items()}
-    est = Estimator(model_fn, params, RunConfig(device=dev, seed=3, use_hip_graph=False))
-    est.build(feats, lab)
-    feats, lab = est._to_device(feats, lab)
-    arrays = est.store.named_arrays()
-    assert not [k for k in gv if k not in arrays], "golden (reference) variables absent from the mirror"
-    assert not [k for k in arrays if k not in gv], "mirror variables the reference does not have"
-    for k, v in gv.items():
-        arrays[k].copy_(torch.from_numpy(v).float().reshape(arrays[k].shape))
-    before = {k: v.detach().cpu().double().clone() for k, v in est.store.named_arrays().items()}
-    pr = est._call_model_fn(feats, None, ModeKeys.PREDICT)
-    assert sorted(pr.predictions) == sorted(f"{t}_probabilities" for t in TASKS)
-    for t in TASKS:
-        assert_close(pr.predictions[f"{t}_probabilities"], torch.from_numpy(d[f"predict/{t}_probabilities"]),
-                     what=f"{name} predict/{t}_probabilities", ref32=o32p["probs"][t])
-    nn.DROPOUT_KEEP_MASKS[:] = masks
-    spec = est._call_model_fn(feats, lab, ModeKeys.TRAIN)
-    assert not nn.DROPOUT_KEEP_MASKS, "the mirror made fewer dropout calls than the reference"
-    assert_close(spec.loss, torch.from_numpy(d["train/loss"]), what=f"{name} loss", ref32=o32["loss"])
-    spec.loss.backward()
-    grads = named_grads(est.store)
-    gg = GU.section(d, "grad/")
-    assert sorted(gg) == sorted(k for k in grads if k in gg) and len(gg) == 46
-    gmax = {k: float(np.abs(v).max()) for k, v in gg.items()}
-    # batch-summed gradients downstream of a BatchNorm cancel (sum_b g_b = 0): their fp32 error is set by the size of the
-    # terms, i.e. by the largest gradients of the dense stack (as tests/test_gpu_golden.py::test_model_golden)
-    dense_floor = 1e-6 * max(v for k, v in gmax.items() if "embedding_weights" not in k)
-    for k, g in gg.items():
-        sib = k.replace("/bias", "/kernel")
-        floor = dense_floor + (1e-5 * gmax[sib] if k.endswith("/bias") and sib in gmax else 0.0)
-        assert_close(grads[k], torch.from_numpy(g), what=f"{name} d({k})", reduced=True, floor=floor, ref32=g32.get(k))
-    spec.train_op.optimizer.apply_gradients(est.store)
-    after = est.store.named_arrays()
-    ga = GU.section(d, "var_after/")
-    lr = float(d["meta/learning_rate"])
-    for k, va in ga.items():
-        ref_upd = torch.from_numpy(va).reshape(before[k].shape) - torch.from_numpy(gv[k]).reshape(before[k].shape)
-        upd = after[k].detach().cpu().double() - before[k]
-        if "moving_" in k:                   # BatchNorm moving statistics (momentum 0.99), updated by the forward
-            assert_close(upd, ref_upd, what=f"{name} {k} update", reduced=True, floor=1e-7)
-            continue
-        gref = torch.from_numpy(gg[k]).reshape(before[k].shape).abs()
-        tol_g = 1e-5 * (gref + gref.pow(2).mean().sqrt()) + 1e-6 * gref.max() + dense_floor + \
-            (1e-5 * gmax.get(k.replace("/bias", "/kernel"), 0.0) if k.endswith("/bias") else 0.0)
-        assert_adam_update(upd, ref_upd, before[k], gref, tol_g, lr, what=f"{name} adam update {k}")
-    # EVAL on the golden's state after the step (its variables and moving statistics loaded: the mirror's own step was judged
-    # above, element by element with the bound that knows where a first Adam step is ill-conditioned; EVAL is judged on its own)
-    for k, v in ga.items():
-        after[k].copy_(torch.from_numpy(v).float().reshape(after[k].shape))
-    ev = est._call_model_fn(feats, lab, ModeKeys.EVAL)
-    assert_close(ev.loss, torch.from_numpy(d["eval/loss"]), what=f"{name} eval loss")
-    assert sorted(ev.eval_metric_ops) == sorted([f"eval_{t}_accuracy" for t in TASKS] + [f"eval_{t}_auc" for t in TASKS])
-    for t in TASKS:
-        for kind in ("accuracy", "auc"):
-            m = ev.eval_metric_ops[f"eval_{t}_{kind}"][0]
-            m.update()
-            assert_close(torch.tensor(m.result()), torch.from_numpy(d[f"eval/{t}_{kind}"]), what=f"{name} eval {t} {kind}")
+    check_on_device(dev, CASE, name, tmp_path)
 
 
 DIMS = (16, 16, 16, 4, 4, 4, 4, 2)          # 66 embedding columns + 16 dense features = the reference's 82 inputs
@@ -365,14 +289,12 @@ def _oracle_inputs(est, feats, labels, dtype):
     return P, cf, {k: v.cpu().to(dtype) for k, v in labels.items()}
 
 
-def test_default_configuration_step_against_float64(dev):
-    """B 4096, hidden_units 512,256,128, 3 experts of 512 units, 3 tasks, BatchNorm on, dropout 0.1 (the keep masks of the
-    library's hash stream recorded and handed to both oracles).  Gradients are compared conditional on the HIP forward's ReLU
-    pattern, as tests/test_gpu_baseline_shapes.py does (see its _ReluPattern)."""
-    from recalgorithm_amd import nn, ops
+def expert_pattern():
+    """tests/test_gpu_baseline_shapes.py's _ReluPattern + the expert layers, which do not go through nn.dense"""
+    from recalgorithm_amd import nn
     from tests.test_gpu_baseline_shapes import _ReluPattern
 
-    class Pattern(_ReluPattern):            # (+ the expert layers, which do not go through nn.dense)
+    class Pattern(_ReluPattern):
         def record_hip(self, call):
             real = nn.expert_layers
 
@@ -385,6 +307,14 @@ def test_default_configuration_step_against_float64(dev):
                 return super().record_hip(call)
             finally:
                 nn.expert_layers = real
+    return Pattern()
+
+
+def test_default_configuration_step_against_float64(dev):
+    """B 4096, hidden_units 512,256,128, 3 experts of 512 units, 3 tasks, BatchNorm on, dropout 0.1 (the keep masks of the
+    library's hash stream recorded and handed to both oracles).  Gradients are compared conditional on the HIP forward's ReLU
+    pattern, as tests/test_gpu_baseline_shapes.py does (see its _ReluPattern)."""
+    from recalgorithm_amd import nn, ops
     B = 4096
     est, params, batches = make(dev)
     feats, labels = batches[0]
@@ -392,7 +322,7 @@ def test_default_configuration_step_against_float64(dev):
     P, cf, cl = _oracle_inputs(est, feats, labels, torch.float64)
     P32, cf32, cl32 = _oracle_inputs(est, feats, labels, torch.float32)
     before = {k: v.detach().cpu().double().clone() for k, v in est.store.named_arrays().items()}
-    pattern = Pattern()
+    pattern = expert_pattern()
     nn.DROPOUT_SPECS[:] = []
     spec = pattern.record_hip(lambda: est._call_model_fn(feats, labels, ModeKeys.TRAIN))
     dspecs = list(nn.DROPOUT_SPECS)
@@ -411,40 +341,7 @@ def test_default_configuration_step_against_float64(dev):
     assert_close(spec.loss, ref["loss"], what="mmoe loss", ref32=r32["loss"])
     for t in TASKS:
         assert_close(spec.predictions[f"{t}_probabilities"], ref["probs"][t], what=f"mmoe {t} prob", ref32=r32["probs"][t])
-    spec.loss.backward()
-    grads = named_grads(est.store)
-    tol_gs, n = {}, 0
-    for name, p in P.items():
-        if p.grad is None:
-            continue
-        g32 = P32[name].grad
-        noise = float((g32.double() - p.grad).abs().max())
-        gref = p.grad.abs()
-        tol_gs[name] = 1e-5 * (gref + gref.pow(2).mean().sqrt()) + 1e-6 * gref.max() + 4 * noise
-        sib = name.replace("bias", "kernel")
-        n += 1
-        if name.endswith("/bias") and sib in P and P[sib].grad is not None and "logit" not in name and "expert" not in name:
-            # a bias in front of a training-mode BatchNorm: its batch-summed gradient cancels analytically; judged at the scale
-            # of its sibling kernel's gradient (tests/test_gpu_baseline_shapes.py)
-            scale = float(P[sib].grad.abs().max())
-            err = float((grads[name].cpu().double() - p.grad).abs().max())
-            assert err <= 1e-5 * scale + 4 * noise, f"d({name}): err {err} scale {scale} noise {noise}"
-            tol_gs[name] = tol_gs[name] + 1e-5 * scale
-            continue
-        # floor: 4x the deviation of the reference arithmetic itself in fp32 (batch sums of 4096 terms)
-        assert_close(grads[name], p.grad, what=f"mmoe d({name})", reduced=True, floor=4 * noise, ref32=g32)
-    assert n >= 40
-    spec.train_op.optimizer.apply_gradients(est.store)
-    after = est.store.named_arrays()
-    for name, p in P.items():
-        if p.grad is None:
-            continue
-        pp, m_, v_ = before[name].clone(), torch.zeros_like(before[name]), torch.zeros_like(before[name])
-        R.adam_tf1_step(pp, p.grad, m_, v_, 1, params["learning_rate"])
-        upd = after[name].detach().cpu().double() - before[name]
-        assert_adam_update(upd, pp - before[name], before[name], p.grad, tol_gs[name], params["learning_rate"],
-                           what=f"mmoe adam update {name}")
-    assert float(est.store.flat_grad.abs().sum()) == 0.0
+    judge_step_against_oracle(est, spec, P, P32, before, params["learning_rate"], "mmoe", 40)
 
 
 def _state(est):
@@ -457,8 +354,9 @@ def _state(est):
     return out
 
 
-def test_captured_run_equals_eager_bit_for_bit(dev):
-    """the reference's default configuration: five steps eager, and three eager + capture + two replays"""
+def check_captured_run_equals_eager(make, dev):
+    """five steps eager, and three eager + capture + two replays, of the estimators `make(dev)` builds (shared with
+    tests/test_gpu_ple.py)"""
     a, _, batches = make(dev)
     b, _, _ = make(dev)
     feats, labels = batches[0]
@@ -476,17 +374,22 @@ def test_captured_run_equals_eager_bit_for_bit(dev):
         assert_bit_exact(B_[k], A[k], f"captured vs eager {k}")
 
 
+def test_captured_run_equals_eager_bit_for_bit(dev):
+    """the reference's default configuration"""
+    check_captured_run_equals_eager(make, dev)
+
+
 class _AbandonedStep(Exception):
     pass
 
 
-def test_abandoned_step_leaves_nothing_to_the_next(dev, monkeypatch):
-    """A step whose backward stops with an exception at its last dense_bwd (the expert layers: the gate-mix backward has
-    parked the gate kernels' column sums by then) never reaches the optimizer's drain; the steps that follow are bit-identical
-    to those of an estimator that never ran it (the contract tests/test_gpu_models.py pins for DCN, DeepFM and PNN).
-    No BatchNorm: a training-mode forward updates the moving averages by design, also in an abandoned step."""
+def check_abandoned_step(make, dev, monkeypatch, kw, n_dense_bwd, colsums_left):
+    """A step whose backward stops with an exception at its last dense_bwd (of `n_dense_bwd`; at least `colsums_left` of the
+    gates' column sums and the towers' six split sums are parked by then) never reaches the optimizer's drain; the steps that
+    follow are bit-identical to those of an estimator that never ran it (the contract tests/test_gpu_models.py pins for DCN,
+    DeepFM and PNN).  `kw` has no BatchNorm: a training-mode forward updates the moving averages by design, also in an
+    abandoned step.  Shared with tests/test_gpu_ple.py."""
     from recalgorithm_amd import ops
-    kw = dict(B=300, hidden=("64", "32"), H=64, dropout_rate=0.0, batch_norm=False)
     a, _, batches = make(dev, **kw)
     b, _, _ = make(dev, **kw)
     real = ops.dense_bwd
@@ -501,12 +404,12 @@ def test_abandoned_step_leaves_nothing_to_the_next(dev, monkeypatch):
     monkeypatch.setattr(ops, "dense_bwd", dense_bwd)
     b.train_step(*batches[1])
     n_calls, calls["n"] = calls["n"], 0
-    assert n_calls == 6 + 3                  # two hidden layers per tower, then the three expert layers
+    assert n_calls == n_dense_bwd
     a.train_step(*batches[1])
     calls["n"], calls["at"] = 0, n_calls
     with pytest.raises(_AbandonedStep):
         a.train_step(*batches[0])
-    assert calls["left"][0] >= 3 and calls["left"][1] >= 6, calls["left"]      # the gates' column sums, the towers' split sums
+    assert calls["left"][0] >= colsums_left and calls["left"][1] >= 6, calls["left"]
     calls["at"] = None
     for est in (a, b):
         for bt in (batches[2], batches[0], batches[3]):
@@ -518,6 +421,13 @@ def test_abandoned_step_leaves_nothing_to_the_next(dev, monkeypatch):
     assert set(A) == set(B_)
     for k in B_:
         assert_bit_exact(A[k], B_[k], f"after the abandoned step: {k}")
+
+
+def test_abandoned_step_leaves_nothing_to_the_next(dev, monkeypatch):
+    """the last dense_bwd is the expert layers': the gate-mix backward has parked the gate kernels' column sums by then.
+    Two hidden layers per tower, then the three expert layers; the three gates' column sums."""
+    kw = dict(B=300, hidden=("64", "32"), H=64, dropout_rate=0.0, batch_norm=False)
+    check_abandoned_step(make, dev, monkeypatch, kw, 6 + 3, 3)
 
 
 def _write_dataset(tmp_path, n):

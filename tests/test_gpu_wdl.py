@@ -3,18 +3,22 @@ logit, the deterministic per-bucket gradient and three FTRL steps against float6
 tests/redzone.py; the bias's path through the flat buffer; the mirrored model_fn against the two reference-generated
 goldens, and a captured run against an eager one; an existing model through the changed minimize / finish_model_fn path.
 Tolerance: the project's standing 1e-5 bound and strict guard (tests/util.py assert_close with ref32=)."""
+import dataclasses
+
 import numpy as np
 import pytest
 import torch
 
-from recalgorithm_amd.estimator import Estimator, GraphedTrainStep, ModeKeys, RunConfig
+from recalgorithm_amd.estimator import Estimator, GraphedTrainStep, RunConfig
 from recalgorithm_amd.feature_column import Ragged
-from recalgorithm_amd.variables import Variable, VariableStore, named_grads
+from recalgorithm_amd.variables import Variable, VariableStore
 from tests import golden_util as GU
 from tests import wdl_ref as W
+from tests.golden_protocol import build_on_device, check_on_device, gradient_floors, judge_adam_update, load_golden, load_variables
 from tests.redzone import guarded
-from tests.test_wdl_host import GOLDENS, f32, mirror_setup
-from tests.util import assert_adam_update, assert_bit_exact, assert_close
+from tests.test_gpu_golden import suite_case
+from tests.test_wdl_host import CASE, GOLDENS, f32
+from tests.util import assert_bit_exact, assert_close
 
 pytestmark = pytest.mark.gpu
 LR = f32(0.005)
@@ -242,30 +246,12 @@ def test_an_abandoned_step_leaves_no_counts_behind(dev):
 
 
 # ---- 3 / 4. the bias, the model -----------------------------------------------------------------------------------------------
-def golden_estimator(dev, name, tmp_path, seed=3):
-    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    model_fn, params = mirror_setup(name, vocab_dir)
-    d = GU.load(name)
-    sfeats, labels = GU.string_batch()
-    feats = {k: (v.float() if isinstance(v, torch.Tensor) else v) for k, v in sfeats.items()}
-    lab = {"read_comment": labels.float()}
-    est = Estimator(model_fn, params, RunConfig(device=dev, seed=seed, use_hip_graph=False))
-    est.build(feats, lab)
-    # the batch as encoded ids on the device (what a training loop feeds): every categorical key the columns read
-    enc = W.encode(params, sfeats)
-    dfeats = {}
-    for k, v in enc.items():
-        if isinstance(v, tuple):
-            dfeats[k] = Ragged(v[0].to(dev), v[1].to(dev))
-        else:
-            dfeats[k] = v.float().to(dev) if v.is_floating_point() else v.to(dev)
-    dlab = {"read_comment": labels.float().to(dev)}
-    arrays = est.store.named_arrays()
-    gv = GU.section(d, "var/")
-    assert sorted(gv) == sorted(arrays)
-    for k, v in gv.items():
-        arrays[k].copy_(torch.from_numpy(v).float().reshape(arrays[k].shape))
-    return est, params, d, dfeats, dlab, sfeats, labels
+def golden_estimator(dev, name, tmp_path):
+    """-> (estimator holding the golden's variables, the batch as encoded ids on the device, its labels)"""
+    est, golden, feats, lab = build_on_device(dev, GPU_CASE, name, tmp_path)
+    assert sorted(golden.var) == sorted(est.store.named_arrays())
+    load_variables(est, golden.var)
+    return est, feats, lab
 
 
 def flat_slice(store, var):
@@ -274,73 +260,53 @@ def flat_slice(store, var):
     return slice(off, off + var.data.numel())
 
 
+def _wide_state_after_the_step(est, produced):
+    """what the golden judges of the wide part besides the variables: the FTRL slots, and what the Adam launch that sweeps the
+    flat buffer left of the wide variables' moments and of the gradient slots"""
+    from recalgorithm_amd import wide
+    (st,) = wide.states(est.store).values()
+    after = est.store.named_arrays()
+    x = produced["extra"]
+    x["wide_after"] = {v.name: after[v.name].detach().cpu() for v in (st.kernel, st.bias)}
+    x["slots"] = {k: v.detach().cpu() for k, v in st.slots.items()}
+    x["wide_adam_moments"] = {v.name: float(est.store.flat_m[flat_slice(est.store, v)].abs().sum()) +
+                              float(est.store.flat_v[flat_slice(est.store, v)].abs().sum()) for v in (st.kernel, st.bias)}
+    x["flat_grad"] = float(est.store.flat_grad.abs().sum())
+
+
+def _judge_ftrl(golden, produced, k):
+    """the wide variables: FTRL (then the Adam launch: the identity here) against var_after/ and the slots"""
+    if not k.startswith("wide_part/"):
+        return False
+    name, x, slots = golden.name, produced["extra"], GU.section(golden.d, "slot/")
+    assert_close(x["wide_after"][k], torch.from_numpy(golden.var_after[k]), what=f"{name} ftrl {k}", reduced=True)
+    assert_close(x["slots"][k + "/Ftrl"], torch.from_numpy(slots[k + "/Ftrl"]), what=f"{name} {k}/Ftrl", reduced=True)
+    assert_close(x["slots"][k + "/Ftrl_1"], torch.from_numpy(slots[k + "/Ftrl_1"]), what=f"{name} {k}/Ftrl_1", reduced=True)
+    return True
+
+
+def _judge_wide_zeros(case, golden, produced):
+    x = produced["extra"]
+    # buckets the batch did not touch: exactly zero, as in the golden
+    zero = torch.from_numpy(golden.var_after[W.WIDE_KERNEL] == 0).reshape(-1)
+    left = x["wide_after"][W.WIDE_KERNEL].reshape(-1)[zero]
+    assert int(zero.sum()) >= 1 and bool((left == 0).all()), f"{golden.name}: an untouched bucket of {W.WIDE_KERNEL} is not zero"
+    # the wide variables' Adam slots and gradient slots: exactly zero
+    for k, total in x["wide_adam_moments"].items():
+        assert total == 0.0, f"{golden.name}: {k} has Adam moments"
+    assert x["flat_grad"] == 0.0, f"{golden.name}: flat_grad is not zero after the step"
+
+
+# Wide&Deep on the device: the batch as encoded ids; ops.loss_seed(1.0) around TRAIN (a training step's setting: the wide logit
+# joins the fused logit / loss launch) and an explicit ones seed; EVAL under no_grad (with grad enabled the lookups would
+# register with the sparse plan as a training lookup); FTRL for the wide variables
+GPU_CASE = dataclasses.replace(CASE, feed_encoded=True, loss_seed=1.0, eval_no_grad=True, other_optimizer=_judge_ftrl,
+                               produce_extra=_wide_state_after_the_step, judge_extra=_judge_wide_zeros)
+
+
 @pytest.mark.parametrize("name", list(GOLDENS))
 def test_model_golden(dev, name, tmp_path):
-    from recalgorithm_amd import nn, ops, wide
-    est, params, d, feats, lab, sfeats, labels = golden_estimator(dev, name, tmp_path)
-    gv = GU.section(d, "var/")
-    # the reference arithmetic's own fp32 rounding on this batch: the restatement in float32 on the golden's variables
-    P32 = {k: torch.from_numpy(v.copy()).float().requires_grad_(True) for k, v in gv.items()}
-    enc = W.encode(params, sfeats)
-    f32s = {k: (v.float() if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in enc.items()}
-    masks = GU.dropout_masks(d)
-    o32p = W.wide_and_deep(P32, f32s, None, params, training=False)
-    o32 = W.wide_and_deep(P32, f32s, {"read_comment": labels.float()}, params, training=True, dropout_masks=[m.float() for m in masks])
-    o32["loss"].backward()
-    g32 = {k: (p.grad if p.grad is not None else torch.zeros_like(p)) for k, p in P32.items()}
-    before = {k: v.detach().cpu().double().clone() for k, v in est.store.named_arrays().items()}
-    pr = est._call_model_fn(feats, None, ModeKeys.PREDICT)
-    assert list(pr.predictions) == ["probabilities"]
-    assert_close(pr.predictions["probabilities"], torch.from_numpy(d["predict/probabilities"]), what=f"{name} predict", ref32=o32p["prob"])
-    nn.DROPOUT_KEEP_MASKS[:] = masks
-    with ops.loss_seed(1.0):                 # (a training step's setting: the wide logit joins the fused logit / loss launch)
-        spec = est._call_model_fn(feats, lab, ModeKeys.TRAIN)
-    assert not nn.DROPOUT_KEEP_MASKS, "the mirror made fewer dropout calls than the reference"
-    spec.loss.backward(torch.ones_like(spec.loss))
-    grads = named_grads(est.store)           # (finishes the step's deferred sums: the fused tail's loss value among them)
-    assert_close(spec.loss, torch.from_numpy(d["train/loss"]), what=f"{name} loss", ref32=o32["loss"])
-    gg = GU.section(d, "grad/")
-    assert sorted(gg) == sorted(k for k in grads if k in gg) and len(gg) == GOLDENS[name]
-    gmax = {k: float(np.abs(v).max()) for k, v in gg.items()}
-    dense_floor = 1e-6 * max(v for k, v in gmax.items() if "embedding_weights" not in k)
-    for k, g in gg.items():
-        sib = k.replace("/bias", "/kernel")
-        floor = dense_floor + (1e-5 * gmax[sib] if k.endswith("/bias") and sib in gmax else 0.0)
-        assert_close(grads[k], torch.from_numpy(g), what=f"{name} d({k})", reduced=True, floor=floor, ref32=g32.get(k))
-    spec.train_op.optimizer.apply_gradients(est.store)
-    after = est.store.named_arrays()
-    ga, slots = GU.section(d, "var_after/"), GU.section(d, "slot/")
-    lr_d = float(d["meta/deep_part_learning_rate"])
-    (st,) = wide.states(est.store).values()
-    for k, va in ga.items():
-        ref_after = torch.from_numpy(va).reshape(before[k].shape)
-        if k.startswith("wide_part/"):       # FTRL (then the Adam launch: the identity here)
-            assert_close(after[k], ref_after, what=f"{name} ftrl {k}", reduced=True)
-            assert_close(st.slots[k + "/Ftrl"], torch.from_numpy(slots[k + "/Ftrl"]), what=f"{name} {k}/Ftrl", reduced=True)
-            assert_close(st.slots[k + "/Ftrl_1"], torch.from_numpy(slots[k + "/Ftrl_1"]), what=f"{name} {k}/Ftrl_1", reduced=True)
-            continue
-        ref_upd, upd = ref_after - torch.from_numpy(gv[k]).reshape(before[k].shape), after[k].detach().cpu().double() - before[k]
-        if "moving_" in k:
-            assert_close(upd, ref_upd, what=f"{name} {k} update", reduced=True, floor=1e-7)
-            continue
-        gref = torch.from_numpy(gg[k]).reshape(before[k].shape).abs()
-        tol_g = 1e-5 * (gref + gref.pow(2).mean().sqrt()) + 1e-6 * gref.max() + dense_floor + \
-            (1e-5 * gmax.get(k.replace("/bias", "/kernel"), 0.0) if k.endswith("/bias") else 0.0)
-        assert_adam_update(upd, ref_upd, before[k], gref, tol_g, lr_d, what=f"{name} adam update {k}")
-    # buckets the batch did not touch: exactly zero, as in the golden
-    zero = torch.from_numpy(ga[W.WIDE_KERNEL] == 0).reshape(-1)
-    assert int(zero.sum()) >= 1 and bool((after[W.WIDE_KERNEL].reshape(-1).cpu()[zero] == 0).all())
-    # the wide variables' Adam slots and gradient slots: exactly zero
-    for v in (st.kernel, st.bias):
-        sl = flat_slice(est.store, v)
-        assert float(est.store.flat_m[sl].abs().sum()) == 0.0 and float(est.store.flat_v[sl].abs().sum()) == 0.0
-    assert float(est.store.flat_grad.abs().sum()) == 0.0
-    # EVAL on the golden's state after the step
-    for k, v in ga.items():
-        after[k].copy_(torch.from_numpy(v).float().reshape(after[k].shape))
-    with torch.no_grad():
-        ev = est._call_model_fn(feats, lab, ModeKeys.EVAL)
-    assert_close(ev.loss, torch.from_numpy(d["eval/loss"]), what=f"{name} eval loss")
+    check_on_device(dev, GPU_CASE, name, tmp_path)
 
 
 def rotated(feats, lab, k):
@@ -376,8 +342,8 @@ def full_state(est):
 @pytest.mark.parametrize("name", list(GOLDENS))
 def test_three_captured_replays_equal_three_eager_steps_and_the_bias_keeps_no_adam_state(dev, name, tmp_path):
     from recalgorithm_amd import wide
-    a, _, _, feats, lab, _, _ = golden_estimator(dev, name, tmp_path / "a")
-    b, _, _, _, _, _, _ = golden_estimator(dev, name, tmp_path / "b")
+    a, feats, lab = golden_estimator(dev, name, tmp_path / "a")
+    b, _, _ = golden_estimator(dev, name, tmp_path / "b")
     batches = [rotated(feats, lab, k) for k in (0, 5, 11, 17)]
     la = [a.train_step(*bt) for bt in batches]
     b.train_step(*batches[0])                # (the first FTRL step zeroes the untouched buckets once: never part of a graph)
@@ -403,7 +369,6 @@ def test_three_captured_replays_equal_three_eager_steps_and_the_bias_keeps_no_ad
 
 # ---- 5. an existing model through the changed path -----------------------------------------------------------------------------
 def test_deepfm_golden_step_through_the_changed_minimize_and_tail(dev, tmp_path):
-    from oracle import ref_ops as R
     from recalgorithm_amd import estimator as E
     vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
     name = "model_deepfm"
@@ -415,9 +380,8 @@ def test_deepfm_golden_step_through_the_changed_minimize_and_tail(dev, tmp_path)
     est = Estimator(model_fn, params, RunConfig(device=dev, seed=3, use_hip_graph=False))
     est.build(feats, lab)
     feats, lab = est._to_device(feats, lab)
-    gv = GU.golden_to_oracle_vars(name, GU.section(d, "var/"), params)
-    ga = GU.golden_to_oracle_vars(name, GU.section(d, "var_after/"), params)
-    gg = GU.golden_to_oracle_vars(name, GU.section(d, "grad/"), params)
+    golden = load_golden(suite_case(name), name, params)
+    gv, ga, gg = golden.var, golden.var_after, golden.grad
     arrays = est.store.named_arrays()
     for k, v in gv.items():
         arrays[k].copy_(torch.from_numpy(v).float().reshape(arrays[k].shape))
@@ -425,19 +389,11 @@ def test_deepfm_golden_step_through_the_changed_minimize_and_tail(dev, tmp_path)
     loss = est.train_step(feats, lab)        # model_fn -> finish_model_fn -> AdamOptimizer.minimize(loss) -> apply_gradients
     assert_close(loss, torch.from_numpy(d["train/loss"]), what="deepfm loss")
     after = est.store.named_arrays()
-    lr = float(d["meta/learning_rate"])
-    gmax = max(float(np.abs(v).max()) for k, v in gg.items() if "embedding_weights" not in k)
-    n = 0
-    for k, va in ga.items():
+    floors, n = gradient_floors(gg), 0
+    for k in ga:
         if "moving_" in k or k not in gg:
             continue
-        ref_upd = torch.from_numpy(va).reshape(before[k].shape) - torch.from_numpy(gv[k]).reshape(before[k].shape)
-        upd = after[k].detach().cpu().double() - before[k]
-        gref = torch.from_numpy(gg[k]).reshape(before[k].shape).abs()
-        sib = k.replace("/bias", "/kernel")
-        tol_g = 1e-5 * (gref + gref.pow(2).mean().sqrt()) + 1e-6 * gref.max() + 1e-6 * gmax + \
-            (1e-5 * float(np.abs(gg[sib]).max()) if k.endswith("/bias") and sib in gg else 0.0)
-        assert_adam_update(upd, ref_upd, before[k], gref, tol_g, lr, what=f"deepfm adam update {k}")
+        judge_adam_update(golden, k, after[k].detach().cpu().double() - before[k], before[k], floors, what=f"deepfm adam update {k}")
         n += 1
     assert n >= 15
     # the default train op is what it was: one Adam op over every variable, no var_list

@@ -9,28 +9,16 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 import torch
 
-from oracle import ref_ops as R
 from tests import golden_util as GU
 from tests import mmoe_ref
+from tests.golden_protocol import GoldenCase, close, restate_on_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDENS = ["model_mmoe", "model_mmoe_dropout"]
-TOL = 1e-10
-
-
-def close(a, b, what, tol=TOL):
-    """tests/test_oracle_golden.py's comparison: max error against tol * max|b| (+ 1e-15: gradients that vanish analytically —
-    a bias ahead of a training-mode BatchNorm — are fp64 rounding noise on both sides)."""
-    a = torch.as_tensor(np.asarray(a.detach() if isinstance(a, torch.Tensor) else a), dtype=torch.float64).reshape(-1)
-    b = torch.as_tensor(np.asarray(b), dtype=torch.float64).reshape(-1)
-    assert a.shape == b.shape, f"{what}: {a.shape} vs {b.shape}"
-    scale = max(float(b.abs().max()), 1e-30) if b.numel() else 1.0
-    err = float((a - b).abs().max()) if b.numel() else 0.0
-    assert err <= tol * scale + 1e-15, f"{what}: max err {err:.3e} at scale {scale:.3e}"
+TASKS = ["read_comment", "like", "click_avatar"]
 
 
 def mirror_setup(name, vocab_dir):
@@ -65,45 +53,19 @@ def encode(params, sfeats):
     return feats
 
 
-def task_labels(d, labels, tasks):
-    """the shared batch carries `read_comment`; the other tasks' labels are part of the golden (in/label_<task>)"""
-    return {t: (labels if t == "read_comment" else torch.from_numpy(d[f"in/label_{t}"].copy())) for t in tasks}
+def multitask_case(mirror_setup, oracle, n_grads):
+    """the golden-parity case of a three-task model (MMoE here, PLE in tests/test_ple_host.py): labels, predictions and EVAL
+    metrics per task, six dropout calls (two hidden layers in each of three towers)"""
+    return GoldenCase(mirror_setup=mirror_setup, oracle=oracle, encode=encode, tasks=TASKS,
+                      predictions={f"{t}_probabilities": ("probs", t) for t in TASKS}, n_grads=n_grads, n_masks=6)
+
+
+CASE = multitask_case(mirror_setup, mmoe_ref.mmoe, 46)
 
 
 @pytest.mark.parametrize("name", GOLDENS)
 def test_restatement_reproduces_the_golden(name, tmp_path):
-    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    _, params = mirror_setup(name, vocab_dir)
-    d = GU.load(name)
-    tasks = params["task_names"]
-    sfeats, labels = GU.string_batch()
-    feats = encode(params, sfeats)
-    lab = task_labels(d, labels, tasks)
-    P = {k: torch.from_numpy(v.copy()).requires_grad_(True) for k, v in GU.section(d, "var/").items()}
-    out = mmoe_ref.mmoe(P, feats, None, params, training=False)
-    for t in tasks:
-        close(out["probs"][t], d[f"predict/{t}_probabilities"], f"{name} {t}_probabilities")
-    masks = GU.dropout_masks(d)
-    assert len(masks) == (6 if float(params["dropout_rate"]) > 0 else 0)
-    out = mmoe_ref.mmoe(P, feats, lab, params, training=True, dropout_masks=masks)
-    close(out["loss"], d["train/loss"], f"{name} loss")
-    out["loss"].backward()
-    gg, ga = GU.section(d, "grad/"), GU.section(d, "var_after/")
-    assert len(gg) == 46 and not [k for k in gg if k not in P]
-    for k, g in gg.items():
-        got = P[k].grad if P[k].grad is not None else torch.zeros_like(P[k])
-        close(got, g, f"{name} d({k})")
-        p = P[k].detach().clone()            # one TF1-Adam step (A-10) on the golden's gradient
-        R.adam_tf1_step(p, torch.from_numpy(g.copy()), torch.zeros_like(p), torch.zeros_like(p), 1, float(d["meta/learning_rate"]))
-        close(p, ga[k], f"{name} adam({k})")
-    # EVAL after the step: the updated variables, the moving statistics the TRAIN run left
-    Pa = {k: torch.from_numpy(v.copy()) for k, v in ga.items()}
-    ev = mmoe_ref.mmoe(Pa, feats, lab, params, training=False)
-    close(ev["loss"], d["eval/loss"], f"{name} eval loss")
-    for t in tasks:
-        acc = ((ev["probs"][t] >= 0.5).double() == lab[t]).double().mean()
-        close(acc, d[f"eval/{t}_accuracy"], f"{name} eval {t} accuracy")
-        close(R.tf_metrics_auc(lab[t], ev["probs"][t]), d[f"eval/{t}_auc"], f"{name} eval {t} auc")
+    restate_on_host(CASE, name, tmp_path)
 
 
 def test_generator_check_round_trip():
@@ -225,16 +187,18 @@ def test_device_batch_extra_labels_are_opt_in():
         synth.device_features(spec, 64, torch.device("cpu"), extra_labels=("nope",))
 
 
-@pytest.mark.parametrize("name", GOLDENS)
-def test_mirror_variables_and_tail_keys_on_the_registration_pass(name, tmp_path):
+def check_registration_pass(case, name, tmp_path):
+    """the mirror's variables and the multi-task tail's keys on the launch-free registration pass (shared with
+    tests/test_ple_host.py)"""
     from recalgorithm_amd.estimator import Estimator, ModeKeys, RunConfig
     vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    model_fn, params = mirror_setup(name, vocab_dir)
+    model_fn, params = case.mirror_setup(name, vocab_dir)
     d = GU.load(name)
     tasks = params["task_names"]
     sfeats, labels = GU.string_batch()
     feats = {k: (v.float() if isinstance(v, torch.Tensor) else v) for k, v in sfeats.items()}
-    lab = {t: v.float() for t, v in task_labels(d, labels, tasks).items()}
+    lab = {t: v.float() for t, v in case.labels(d, labels).items()}
+    assert list(lab) == tasks
     est = Estimator(model_fn, params, RunConfig(device="cpu", seed=3, use_hip_graph=False))
     est.build(feats, lab)                    # registration pass only: no HIP call
     arrays = est.store.named_arrays()
@@ -256,6 +220,11 @@ def test_mirror_variables_and_tail_keys_on_the_registration_pass(name, tmp_path)
     assert all(tuple(v.shape) == (48, 1) for v in pred.predictions.values())
     assert sorted(ev.eval_metric_ops) == sorted([f"eval_{t}_accuracy" for t in tasks] + [f"eval_{t}_auc" for t in tasks])
     assert ev.loss is not None and ev.loss.dim() == 0
+
+
+@pytest.mark.parametrize("name", GOLDENS)
+def test_mirror_variables_and_tail_keys_on_the_registration_pass(name, tmp_path):
+    check_registration_pass(CASE, name, tmp_path)
 
 
 def test_limits_raise_not_implemented():

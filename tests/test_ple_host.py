@@ -14,19 +14,17 @@ import re
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 import torch
 
-from oracle import ref_ops as R
 from tests import golden_util as GU
 from tests import ple_ref
-from tests.test_mmoe_host import close, encode, task_labels
+from tests.golden_protocol import close, restate_on_host
+from tests.test_mmoe_host import check_registration_pass, multitask_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "recalgo_cgc.h")
 GOLDENS = {"model_ple": 76, "model_ple_two_levels_dropout": 96}        # name -> gradient arrays
-TOL = 1e-10         # the bound of every comparison with a golden below
 
 
 def mirror_setup(name, vocab_dir):
@@ -49,42 +47,14 @@ def mirror_setup(name, vocab_dir):
         "num_experts_in_shared": int(fl["num_experts_in_shared"])}
 
 
+CASE = multitask_case(mirror_setup, ple_ref.ple, GOLDENS)
+
+
 @pytest.mark.parametrize("name", list(GOLDENS))
 def test_restatement_reproduces_the_golden(name, tmp_path):
-    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    _, params = mirror_setup(name, vocab_dir)
+    _, params = mirror_setup(name, GU.write_vocab_dir(str(tmp_path / "vocabulary")))
     assert params["num_experts_per_task"] == [2, 1, 3] and params["num_experts_in_shared"] == 2
-    d = GU.load(name)
-    tasks = params["task_names"]
-    sfeats, labels = GU.string_batch()
-    feats = encode(params, sfeats)
-    lab = task_labels(d, labels, tasks)
-    P = {k: torch.from_numpy(v.copy()).requires_grad_(True) for k, v in GU.section(d, "var/").items()}
-    out = ple_ref.ple(P, feats, None, params, training=False)
-    for t in tasks:
-        close(out["probs"][t], d[f"predict/{t}_probabilities"], f"{name} {t}_probabilities", tol=TOL)
-    masks = GU.dropout_masks(d)
-    assert len(masks) == (6 if float(params["dropout_rate"]) > 0 else 0)
-    out = ple_ref.ple(P, feats, lab, params, training=True, dropout_masks=masks)
-    close(out["loss"], d["train/loss"], f"{name} loss", tol=TOL)
-    out["loss"].backward()
-    gg, ga = GU.section(d, "grad/"), GU.section(d, "var_after/")
-    assert len(gg) == GOLDENS[name] and not [k for k in gg if k not in P]
-    assert not [k for k, g in gg.items() if not np.any(g)], "an all-zero gradient in the golden"
-    for k, g in gg.items():
-        got = P[k].grad if P[k].grad is not None else torch.zeros_like(P[k])
-        close(got, g, f"{name} d({k})", tol=TOL)
-        p = P[k].detach().clone()            # one TF1-Adam step (A-10) on the golden's gradient
-        R.adam_tf1_step(p, torch.from_numpy(g.copy()), torch.zeros_like(p), torch.zeros_like(p), 1, float(d["meta/learning_rate"]))
-        close(p, ga[k], f"{name} adam({k})", tol=TOL)
-    # EVAL after the step: the updated variables, the moving statistics the TRAIN run left
-    Pa = {k: torch.from_numpy(v.copy()) for k, v in ga.items()}
-    ev = ple_ref.ple(Pa, feats, lab, params, training=False)
-    close(ev["loss"], d["eval/loss"], f"{name} eval loss", tol=TOL)
-    for t in tasks:
-        acc = ((ev["probs"][t] >= 0.5).double() == lab[t]).double().mean()
-        close(acc, d[f"eval/{t}_accuracy"], f"{name} eval {t} accuracy", tol=TOL)
-        close(R.tf_metrics_auc(lab[t], ev["probs"][t]), d[f"eval/{t}_auc"], f"{name} eval {t} auc", tol=TOL)
+    restate_on_host(CASE, name, tmp_path)
 
 
 def test_generator_check_round_trip():
@@ -153,34 +123,7 @@ def test_cgc_summed_backward_formulas_against_autograd(shape):
 
 @pytest.mark.parametrize("name", list(GOLDENS))
 def test_mirror_variables_and_tail_keys_on_the_registration_pass(name, tmp_path):
-    from recalgorithm_amd.estimator import Estimator, ModeKeys, RunConfig
-    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    model_fn, params = mirror_setup(name, vocab_dir)
-    d = GU.load(name)
-    tasks = params["task_names"]
-    sfeats, labels = GU.string_batch()
-    feats = {k: (v.float() if isinstance(v, torch.Tensor) else v) for k, v in sfeats.items()}
-    lab = {t: v.float() for t, v in task_labels(d, labels, tasks).items()}
-    est = Estimator(model_fn, params, RunConfig(device="cpu", seed=3, use_hip_graph=False))
-    est.build(feats, lab)                    # registration pass only: no HIP call
-    arrays = est.store.named_arrays()
-    gv = GU.section(d, "var/")
-    assert not [k for k in gv if k not in arrays], "reference variables absent from the mirror"
-    assert not [k for k in arrays if k not in gv], "mirror variables the reference does not have"
-    for k, v in gv.items():
-        assert tuple(arrays[k].shape) == tuple(v.shape), (k, arrays[k].shape, v.shape)
-    est.store.building = True
-    try:
-        with torch.no_grad():
-            pred = est._call_model_fn(feats, None, ModeKeys.PREDICT)
-            ev = est._call_model_fn(feats, lab, ModeKeys.EVAL)
-    finally:
-        est.store.building = False
-    assert sorted(pred.predictions) == sorted(f"{t}_probabilities" for t in tasks)
-    assert pred.export_outputs == {"prediction": pred.predictions}
-    assert all(tuple(v.shape) == (48, 1) for v in pred.predictions.values())
-    assert sorted(ev.eval_metric_ops) == sorted([f"eval_{t}_accuracy" for t in tasks] + [f"eval_{t}_auc" for t in tasks])
-    assert ev.loss is not None and ev.loss.dim() == 0
+    check_registration_pass(CASE, name, tmp_path)
 
 
 def test_reference_flag_defaults_and_call_surface():

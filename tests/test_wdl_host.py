@@ -19,15 +19,13 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ref_ops as R
 from tests import golden_util as GU
 from tests import wdl_ref as W
-from tests.test_mmoe_host import close
+from tests.golden_protocol import GoldenCase, close, restate_on_host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "recalgo_wide.h")
 GOLDENS = {"model_wdl": 19, "model_wdl_dropout": 19}          # name -> gradient arrays
-TOL = 1e-10         # the bound of every comparison with a golden below
 
 
 def f32(x):
@@ -85,42 +83,36 @@ def test_hash_two_implementations_agree():
 
 
 # ---- 2. the restatement against the goldens ------------------------------------------------------------------------------------
+WIDE = [W.WIDE_KERNEL, W.WIDE_BIAS]
+# the golden-parity case; tests/test_gpu_wdl.py adds what its device run needs
+CASE = GoldenCase(mirror_setup=mirror_setup, oracle=W.wide_and_deep, encode=W.encode, predictions={"probabilities": ("prob",)},
+                  ordered_prediction_keys=True, predict_what="{name} predict", n_grads=GOLDENS, n_masks=2,
+                  lr_key="meta/deep_part_learning_rate")
+
+
+def _ftrl_step(golden, k, p, g):
+    """the wide variables: one dense FTRL step (accum 0.1 as float32, linear 0) on the golden's gradient"""
+    if k not in WIDE:
+        return False
+    d, name, slots = golden.d, golden.name, GU.section(golden.d, "slot/")
+    v, a, l = W.ftrl_dense(p, torch.full_like(p, f32(W.FTRL_INITIAL_ACCUMULATOR)), torch.zeros_like(p), g,
+                           f32(d["meta/wide_part_learning_rate"]))
+    close(v, golden.var_after[k], f"{name} ftrl({k})")
+    close(a, slots[f"{k}/Ftrl"], f"{name} accum({k})")
+    close(l, slots[f"{k}/Ftrl_1"], f"{name} linear({k})")
+    return True
+
+
 @pytest.mark.parametrize("name", list(GOLDENS))
 def test_restatement_reproduces_the_golden(name, tmp_path):
-    vocab_dir = GU.write_vocab_dir(str(tmp_path / "vocabulary"))
-    _, params = mirror_setup(name, vocab_dir)
     d = GU.load(name)
     H = int(d["meta/hash_bucket_size"])
+    _, params = mirror_setup(name, GU.write_vocab_dir(str(tmp_path / "vocabulary")))
     assert H == 64 and params["wide_part_feature_columns"][0].categorical_column.hash_bucket_size == H
-    sfeats, labels = GU.string_batch()
-    feats = W.encode(params, sfeats)
-    lab = {"read_comment": labels}
-    P = {k: torch.from_numpy(v.copy()).requires_grad_(True) for k, v in GU.section(d, "var/").items()}
-    out = W.wide_and_deep(P, feats, None, params, training=False)
-    close(out["prob"], d["predict/probabilities"], f"{name} probabilities", tol=TOL)
-    masks = GU.dropout_masks(d)
-    assert len(masks) == (2 if float(params["dropout_rate"]) > 0 else 0)
-    out = W.wide_and_deep(P, feats, lab, params, training=True, dropout_masks=masks)
-    close(out["loss"], d["train/loss"], f"{name} loss", tol=TOL)
-    out["loss"].backward()
-    gg, ga, slots = GU.section(d, "grad/"), GU.section(d, "var_after/"), GU.section(d, "slot/")
-    assert len(gg) == GOLDENS[name] and not [k for k in gg if k not in P]
-    assert not [k for k, g in gg.items() if not np.any(g)], "an all-zero gradient in the golden"
-    wide = [W.WIDE_KERNEL, W.WIDE_BIAS]
-    assert sorted(slots) == sorted(f"{k}/{s}" for k in wide for s in ("Ftrl", "Ftrl_1"))
-    lr_w, lr_d = f32(d["meta/wide_part_learning_rate"]), float(d["meta/deep_part_learning_rate"])
-    for k, g in gg.items():
-        got = P[k].grad if P[k].grad is not None else torch.zeros_like(P[k])
-        close(got, g, f"{name} d({k})", tol=TOL)
-        p, gt = P[k].detach().clone(), torch.from_numpy(g.copy())
-        if k in wide:                        # one dense FTRL step (accum 0.1 as float32, linear 0) on the golden's gradient
-            v, a, l = W.ftrl_dense(p, torch.full_like(p, f32(W.FTRL_INITIAL_ACCUMULATOR)), torch.zeros_like(p), gt, lr_w)
-            close(v, ga[k], f"{name} ftrl({k})", tol=TOL)
-            close(a, slots[f"{k}/Ftrl"], f"{name} accum({k})", tol=TOL)
-            close(l, slots[f"{k}/Ftrl_1"], f"{name} linear({k})", tol=TOL)
-        else:                                # one TF1-Adam step (A-10)
-            R.adam_tf1_step(p, gt, torch.zeros_like(p), torch.zeros_like(p), 1, lr_d)
-            close(p, ga[k], f"{name} adam({k})", tol=TOL)
+    slots = GU.section(d, "slot/")
+    assert sorted(slots) == sorted(f"{k}/{s}" for k in WIDE for s in ("Ftrl", "Ftrl_1"))
+    golden, run = restate_on_host(CASE, name, tmp_path, other_step=_ftrl_step)
+    gg, ga, feats, lr_w = golden.grad, golden.var_after, run["feats"], f32(d["meta/wide_part_learning_rate"])
     # the wide kernel: buckets nothing touched are EXACTLY zero after the step; the golden holds some, and collisions
     ex, bk = W.buckets(feats["userid"], *feats["manual_tag_list"], H)
     touched = np.zeros(H, dtype=bool)
@@ -136,16 +128,10 @@ def test_restatement_reproduces_the_golden(name, tmp_path):
     tj = torch.from_numpy(np.nonzero(touched)[0])
     v, a, l = W.ftrl_sparse(kern, torch.full_like(kern, f32(0.1)), torch.zeros_like(kern), tj,
                             torch.from_numpy(gg[W.WIDE_KERNEL].copy()).reshape(-1)[tj], lr_w, first_step=True)
-    close(v, after, f"{name} sparse ftrl kernel", tol=TOL)
+    close(v, after, f"{name} sparse ftrl kernel")
     assert torch.all(v[torch.from_numpy(~touched)] == 0.0)
-    close(a, slots[W.WIDE_KERNEL + "/Ftrl"], f"{name} sparse ftrl accum", tol=TOL)
-    close(l, slots[W.WIDE_KERNEL + "/Ftrl_1"], f"{name} sparse ftrl linear", tol=TOL)
-    # EVAL after the step: the updated variables, the moving statistics the TRAIN run left
-    Pa = {k: torch.from_numpy(v.copy()) for k, v in ga.items()}
-    ev = W.wide_and_deep(Pa, feats, lab, params, training=False)
-    close(ev["loss"], d["eval/loss"], f"{name} eval loss", tol=TOL)
-    close(((ev["prob"] >= 0.5).double() == labels).double().mean(), d["eval/accuracy"], f"{name} eval accuracy", tol=TOL)
-    close(R.tf_metrics_auc(labels, ev["prob"]), d["eval/auc"], f"{name} eval auc", tol=TOL)
+    close(a, slots[W.WIDE_KERNEL + "/Ftrl"], f"{name} sparse ftrl accum")
+    close(l, slots[W.WIDE_KERNEL + "/Ftrl_1"], f"{name} sparse ftrl linear")
 
 
 # ---- 3. the generator ------------------------------------------------------------------------------------------------------------
