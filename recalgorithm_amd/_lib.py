@@ -32,7 +32,8 @@ def _versioned(header: str):
 
 # The headers of the HIP library, each the one statement of its part of the ABI (signatures, struct layouts, constants, a
 # version of its own, bumped on any signature change).  This is the only list of them: a new header is one more entry.
-HEADERS = {h: _versioned(h) for h in ("recalgo.h", "recalgo_cgc.h", "recalgo_wide.h", "recalgo_bst.h")}
+HEADERS = {h: _versioned(h) for h in ("recalgo.h", "recalgo_cgc.h", "recalgo_wide.h", "recalgo_bst.h",
+                                              "recalgo_res.h")}
 ABI = HEADERS["recalgo.h"]  # the first header's tables, under the names the product uses:
 SIGNATURES = ABI.functions  # name -> (restype, argtypes) of every function of the header
 STRUCTS = ABI.structs  # recalgo_*_t -> ctypes.Structure subclass

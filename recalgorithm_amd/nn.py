@@ -932,3 +932,61 @@ def bst_transformer(queries: torch.Tensor, keys_length: torch.Tensor, heads: int
     n1 = ops.bst_attention(x, keys_length, pos, w_q, w_k, w_v, w_o, *norms[0], anchor=store.anchor)
     out, pooled = ops.bst_ffn(n1, ffn_w, ffn_b, *norms[1], pool=pool, want_out=pool is None, anchor=store.anchor)
     return out if pool is None else pooled
+
+
+# From this width on nn.residual_stack runs the composed dense layers by default; below it the fused kernels of
+# csrc/residual.hip.  The choice is a function of the shape alone (residual_fused_default): one path trains, evaluates and serves
+# a model.  scripts/bench_deepcrossing.py (profiles/deepcrossing_bench.json, B = 4096, H = 128; DESIGN.md §5 "DeepCrossing
+# residual stack"), fused against composed, forward + backward with the weight gradients, 1 unit / 3 units:
+#   D = 82: 0.94 x / 1.03 x      D = 128: 0.80 x / 0.89 x      D = 256: 0.71 x / 0.76 x      D = 432: 0.63 x / 0.68 x
+# At the measured widths from 128 on the composed layers are faster at both depths and are the default.  At D = 82, the
+# reference's width, the two are within 6 % of each other and the fused path is the default because it is the one that meets the
+# strict parity rule on both committed goldens (the composed layers leave 28 elements of one kernel gradient of the three-unit
+# golden outside it, limit 24).  Widths between 82 and 128 were not measured; they go with 82.
+RESIDUAL_COMPOSED_FROM_D = 128
+
+
+def residual_fused_default(D: int, H: int, L: int) -> bool:
+    """Whether residual_stack(fused=None) runs a [*, D] stack of L units of internal width H on the fused kernels."""
+    from . import ops
+    return L >= 1 and D < RESIDUAL_COMPOSED_FROM_D and ops.residual_supported(D, H, L)
+
+
+def residual_stack(x: torch.Tensor, internal_dim: int, num_units: int, first_index: int = 0,
+                   fused: Optional[bool] = None) -> torch.Tensor:
+    """algorithm/DeepCrossing/deepcrossing.py:154-157: `num_units` residual units (residual_unit.py:4-22) chained,
+        h = tf.layers.dense(x, internal_dim, name="dense_<i>_0", activation=relu)
+        x = relu(x + tf.layers.dense(h, D, name="dense_<i>_1"))                      i = first_index, first_index + 1, ..
+    Variables under the caller's scope, the reference's names: dense_<i>_0/{kernel [D, internal_dim], bias},
+    dense_<i>_1/{kernel [internal_dim, D], bias} (glorot-uniform, zeros); both paths own the same ones.
+    fused=None (not a reference argument): the whole stack as ONE launch each way (ops.residual_stack) where
+    residual_fused_default(D, internal_dim, num_units) says so, else the same arithmetic as two `dense` layers and an
+    add + ReLU per unit (internal_dim % 16 != 0, wide stacks, more than 8 units, a CPU tensor).  fused=True / False: that
+    path; True where csrc/residual.hip does not serve the sizes is a ValueError."""
+    from . import ops
+    store = current_store()
+    D, H, L = int(x.shape[-1]), int(internal_dim), int(num_units)
+    on_device = x.dim() == 2 and store.device.type == "cuda" and (store.building or (x.is_cuda and x.dtype == torch.float32))
+    if fused is None:
+        fused = on_device and residual_fused_default(D, H, L)
+    elif fused and not (on_device and L >= 1 and ops.residual_supported(D, H, L)):
+        raise ValueError(f"residual_stack(fused=True): the kernels do not serve D={D} H={H} units={L} on {store.device}")
+    if not fused:
+        for i in range(first_index, first_index + L):
+            h = dense(x, H, activation="relu", name=f"dense_{i}_0")
+            x = torch.relu(x + dense(h, D, activation=None, name=f"dense_{i}_1"))
+        return x
+    params = ([], [], [], [])                # W0, b0, W1, b1 of every unit, created in the reference's order
+    for i in range(first_index, first_index + L):
+        for j, shape in enumerate(((D, H), (H, D))):
+            with store.variable_scope(f"dense_{i}_{j}"):
+                params[2 * j].append(store.get_variable("kernel", shape, glorot_uniform))
+                params[2 * j + 1].append(store.get_variable("bias", shape[1:], zeros))
+    if store.building:
+        return torch.zeros_like(x)
+    return ops.residual_stack(x if x.is_contiguous() else x.contiguous(), *params, anchor=store.anchor)
+
+
+def residual_unit(x: torch.Tensor, internal_dim: int, index: int, fused: Optional[bool] = None) -> torch.Tensor:
+    """One residual unit (residual_unit.py:4-22) with the variables dense_<index>_0 / dense_<index>_1: the one-unit stack."""
+    return residual_stack(x, internal_dim, 1, first_index=index, fused=fused)

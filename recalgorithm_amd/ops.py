@@ -2571,3 +2571,74 @@ def bst_ffn(n1: torch.Tensor, ffn_w, ffn_b, gamma, beta, pool: Optional[str] = N
     _chk(n1, torch.float32, "bst_ffn: n1")
     tensors = [None if isinstance(p, Variable) else p for p in params]
     return _BstFfnFn.apply(anchor, n1, pool == "mean", bool(want_out), pool is not None, params, *tensors)
+
+
+# =============================================================================================
+# DeepCrossing (csrc/residual.hip, include/recalgo_res.h): the stack of residual units, one kernel each way
+# =============================================================================================
+_CR = _lib.HEADERS["recalgo_res.h"].constants                 # the RECALGO_RES_* #defines of include/recalgo_res.h
+RES_MAX_D, RES_MAX_H, RES_MAX_UNITS = _CR["RECALGO_RES_MAX_D"], _CR["RECALGO_RES_MAX_H"], _CR["RECALGO_RES_MAX_UNITS"]
+
+
+def residual_supported(D: int, H: int, L: int) -> bool:
+    return bool(_lib_().recalgo_res_supported(int(D), int(H), int(L)))
+
+
+class _ResidualStackFn(Function):
+    """include/recalgo_res.h recalgo_res_stack_fwd / recalgo_res_stack_bwd; the four parameter gradients of a unit are batch
+    sums over what the backward kernel wrote: two launches of the dense engine's weight gradient per unit."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, w0s, b0s, w1s, b1s, differentiated):
+        B, D = x.shape
+        L, H = len(w0s), int(w0s[0].data.shape[1])
+        tables = [_ptr_array([v.data for v in vs]) for vs in (w0s, b0s, w1s, b1s)]
+        save = bool(differentiated)          # (the caller's grad mode: inside a Function's forward it is always off)
+        hs = torch.empty(L, B, H, device=x.device, dtype=torch.float32) if save else None
+        ys = torch.empty((L, B, D) if save else (B, D), device=x.device, dtype=torch.float32)
+        _lib_().recalgo_res_stack_fwd(_p(x), *tables, B, D, H, L, int(save), _p(hs), _p(ys), _stream(x))
+        if not save:
+            return ys
+        ctx.vars = (w0s, b0s, w1s, b1s)
+        ctx.in_step = _loss_seed is not None      # built inside Estimator.train_step: its optimizer runs the deferred sums
+        ctx.save_for_backward(x, hs, ys)
+        return ys[L - 1]
+
+    @staticmethod
+    def backward(ctx, g):
+        w0s, b0s, w1s, b1s = ctx.vars
+        x, hs, ys = ctx.saved_tensors
+        L, B, D = ys.shape
+        H = hs.shape[2]
+        g = g if g.is_contiguous() else g.contiguous()
+        dzs, dhs, dx = torch.empty_like(ys), torch.empty_like(hs), torch.empty_like(x)
+        _lib_().recalgo_res_stack_bwd(_p(g), _p(hs), _p(ys), _ptr_array([v.data for v in w0s]), _ptr_array([v.data for v in w1s]),
+                                      B, D, H, L, _p(dzs), _p(dhs), _p(dx), _stream(x))
+        for l in range(L):
+            dense_bwd_weights(x if l == 0 else ys[l - 1], dhs[l], None, w0s[l].grad, b0s[l].grad, defer=ctx.in_step)
+            dense_bwd_weights(hs[l], dzs[l], None, w1s[l].grad, b1s[l].grad, defer=ctx.in_step)
+        return (None, dx if ctx.needs_input_grad[1] else None, None, None, None, None, None)
+
+
+def residual_stack(x: torch.Tensor, w0s, b0s, w1s, b1s, anchor=None) -> torch.Tensor:
+    """DeepCrossing's residual units (residual_unit.py:4-22) chained: x_{l+1} = relu(x_l + relu(x_l W0_l + b0_l) W1_l + b1_l)
+    for the L units of the four lists of Variables (W0_l [D, H], b0_l [H], W1_l [H, D], b1_l [D]); x [B, D] -> [B, D].
+    With grad enabled the forward keeps every unit's two activations and the backward is one launch plus two weight-gradient
+    launches per unit (gradients to Variable.grad; inside a training step their sums join the step's deferred reduction,
+    flush_dense_splits).  Sizes the kernels do not serve (residual_supported): ValueError — nn.residual_stack composes those
+    from dense layers."""
+    if x.dim() != 2 or x.shape[0] == 0:
+        raise ValueError("residual_stack: x must be a non-empty [B, D] matrix")
+    _chk(x, torch.float32, "residual_stack: x")
+    B, D = x.shape
+    L = len(w0s)
+    H = int(w0s[0].data.shape[1]) if L and w0s[0].data.dim() == 2 else 0
+    if not (len(b0s) == len(w1s) == len(b1s) == L) or not residual_supported(D, H, L):
+        raise ValueError(f"residual_stack: the kernels serve 1 <= D <= {RES_MAX_D}, 16 <= H <= {RES_MAX_H} with H % 16 == 0 and "
+                         f"1 <= units <= {RES_MAX_UNITS}; got D={D} H={H} units={L}")
+    for vs, shape, name in ((w0s, (D, H), "W0"), (b0s, (H,), "b0"), (w1s, (H, D), "W1"), (b1s, (D,), "b1")):
+        for v in vs:
+            _chk(v.data, torch.float32, f"residual_stack: {name}")
+            if tuple(v.data.shape) != shape:
+                raise ValueError(f"residual_stack: {name} has shape {tuple(v.data.shape)}, expected {shape}")
+    return _ResidualStackFn.apply(anchor, x, tuple(w0s), tuple(b0s), tuple(w1s), tuple(b1s), torch.is_grad_enabled())
