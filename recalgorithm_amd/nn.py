@@ -934,6 +934,67 @@ def bst_transformer(queries: torch.Tensor, keys_length: torch.Tensor, heads: int
     return out if pool is None else pooled
 
 
+def _gru_cell_variables(store, nx: int, nh: int):
+    """TF 1.14 GRUCell's four variables under the current scope: gates/{kernel [nx + nh, 2 nh], bias = 1},
+    candidate/{kernel [nx + nh, nh], bias = 0}, kernels glorot-uniform (the variable scope's default initializer)."""
+    with store.variable_scope("gates"):
+        wg, bg = store.get_variable("kernel", (nx + nh, 2 * nh), glorot_uniform), store.get_variable("bias", (2 * nh,), ones)
+    with store.variable_scope("candidate"):
+        wc, bc = store.get_variable("kernel", (nx + nh, nh), glorot_uniform), store.get_variable("bias", (nh,), zeros)
+    return wg, bg, wc, bc
+
+
+def _dien_served(what: str, T: int, na: int, nh: int):
+    from . import ops
+    if not ops.dien_supported(T, na, nh):
+        raise ValueError(f"{what}: T={T} na={na} nh={nh} is outside what the DIEN kernels serve (1 <= T <= {ops.DIEN_MAX_T}, an "
+                         f"input width in (4, 8, 12, 16), a state width in (4, 8, 12, 16)); there is no fallback")
+
+
+def dien_gru(inputs: torch.Tensor, sequence_length: Optional[torch.Tensor], num_units: int) -> torch.Tensor:
+    """dynamic_rnn(GRUCell(num_units), inputs) of algorithm/DIEN/dien.py:202 on csrc/dien.hip: inputs [B, T, na] -> the
+    outputs [B, T, nh], rows t >= sequence_length zero (None: all T steps run, as the reference calls it).  Variables under the
+    caller's scope, TF's names: rnn/gru_cell/{gates, candidate}/{kernel, bias}."""
+    from . import ops
+    store = current_store()
+    B, T, na = inputs.shape
+    nh = int(num_units)
+    with store.variable_scope("rnn"), store.variable_scope("gru_cell"):
+        cell = _gru_cell_variables(store, na, nh)
+    _dien_served("dien_gru", T, na, nh)
+    if store.building:
+        return inputs.new_zeros((B, T, nh))
+    x = inputs if inputs.is_contiguous() else inputs.contiguous()
+    return ops.dien_gru(x, sequence_length, *cell, anchor=store.anchor)
+
+
+def dien_evolve(h: torch.Tensor, target: torch.Tensor, sequence_length: torch.Tensor, custom_gru_type: str = "AGRU",
+                return_states: bool = False):
+    """algorithm/DIEN/dien.py:205-229 as one launch each way: the attention of `target` [B, na] over the rows of h [B, T, nh]
+    (scores past sequence_length replaced by -2^32, softmax over all T) and dynamic_rnn(AGRUCell | AUGRUCell, h, scores,
+    sequence_length) -> (final state [B, nh], attention scores [B, T]), with return_states also the cell's outputs [B, T, nh]
+    (neither the scores nor the outputs carry a gradient).  Variables under the caller's scope:
+    attention_project_matrix [nh, na], and rnn/{gates, candidate}/{kernel, bias} — the custom cells override __call__, so
+    there is no cell-name scope, and the second dynamic_rnn re-enters the scope `rnn`."""
+    from . import ops
+    store = current_store()
+    B, T, nh = h.shape
+    na = int(target.shape[1])
+    if custom_gru_type not in ops.DIEN_MODES:
+        raise ValueError(f"dien_evolve: custom_gru_type={custom_gru_type!r}, expected one of {sorted(ops.DIEN_MODES)}")
+    w_att = store.get_variable("attention_project_matrix", (nh, na), glorot_uniform)
+    with store.variable_scope("rnn"):
+        cell = _gru_cell_variables(store, nh, nh)
+    _dien_served("dien_evolve", T, na, nh)
+    if store.building:
+        outs = (h.new_zeros((B, nh)), h.new_zeros((B, T)), h.new_zeros((B, T, nh)))
+    else:
+        hc = h if h.is_contiguous() else h.contiguous()
+        tc = target if target.is_contiguous() else target.contiguous()
+        outs = ops.dien_evolve(hc, tc, sequence_length, w_att, *cell, mode=custom_gru_type, anchor=store.anchor)
+    return outs if return_states else outs[:2]
+
+
 # From this width on nn.residual_stack runs the composed dense layers by default; below it the fused kernels of
 # csrc/residual.hip.  The choice is a function of the shape alone (residual_fused_default): one path trains, evaluates and serves
 # a model.  scripts/bench_deepcrossing.py (profiles/deepcrossing_bench.json, B = 4096, H = 128; DESIGN.md §5 "DeepCrossing

@@ -2642,3 +2642,144 @@ def residual_stack(x: torch.Tensor, w0s, b0s, w1s, b1s, anchor=None) -> torch.Te
             if tuple(v.data.shape) != shape:
                 raise ValueError(f"residual_stack: {name} has shape {tuple(v.data.shape)}, expected {shape}")
     return _ResidualStackFn.apply(anchor, x, tuple(w0s), tuple(b0s), tuple(w1s), tuple(b1s), torch.is_grad_enabled())
+
+
+# =============================================================================================
+# DIEN (csrc/dien.hip, include/recalgo_dien.h): the GRU recurrence; attention + the AGRU / AUGRU recurrence
+# =============================================================================================
+_CD = _lib.MORE_HEADERS["recalgo_dien.h"].constants           # the RECALGO_DIEN_* #defines of include/recalgo_dien.h
+DIEN_MAX_T, DIEN_MAX_NA, DIEN_MAX_NH = _CD["RECALGO_DIEN_MAX_T"], _CD["RECALGO_DIEN_MAX_NA"], _CD["RECALGO_DIEN_MAX_NH"]
+DIEN_MODES = {"AGRU": _CD["RECALGO_DIEN_MODE_AGRU"], "AUGRU": _CD["RECALGO_DIEN_MODE_AUGRU"]}
+
+
+def dien_supported(T: int, na: int, nh: int) -> bool:
+    return bool(_lib_().recalgo_dien_supported(int(T), int(na), int(nh)))
+
+
+class _DienGruFn(Function):
+    """include/recalgo_dien.h recalgo_dien_gru_fwd / recalgo_dien_gru_bwd; params = (Wg, bg, Wc, bc), `tensors` the same four
+    with None where params holds a Variable."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, lengths, params, *tensors):
+        ts, vs = _bst_split(params)
+        B, T, na = x.shape
+        nh = ts[3].shape[0]
+        h = torch.empty(B, T, nh, device=x.device, dtype=torch.float32)
+        _lib_().recalgo_dien_gru_fwd(_p(x), _p(lengths), *[_p(t) for t in ts], B, T, na, nh, _p(h), _stream(x))
+        ctx.ts, ctx.vs, ctx.lengths = ts, vs, lengths
+        ctx.save_for_backward(x, h)
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        ts, vs, lengths = ctx.ts, ctx.vs, ctx.lengths
+        x, h = ctx.saved_tensors
+        B, T, na = x.shape
+        nh = h.shape[2]
+        g = g if g.is_contiguous() else g.contiguous()
+        lib = _lib_()
+        dx = torch.empty_like(x)
+        outs = _bst_grad_buffers(ts, vs)                 # dWg, dbg, dWc, dbc
+        ws = _workspace(int(lib.recalgo_dien_gru_bwd_workspace_bytes(B, na, nh)), x.device)
+        lib.recalgo_dien_gru_bwd(_p(x), _p(lengths), _p(h), *[_p(t) for t in ts], _p(g), B, T, na, nh, _p(dx),
+                                 *[_p(o) for o in outs], _p(ws), _stream(x))
+        rets = [None if v is not None else o for o, v in zip(outs, vs)]
+        return (None, dx if ctx.needs_input_grad[1] else None, None, None, *rets)
+
+
+class _DienEvolveFn(Function):
+    """include/recalgo_dien.h recalgo_dien_evolve_fwd / recalgo_dien_evolve_bwd; params = (w_att, Wg, bg, Wc, bc).  -> (final,
+    att, states); only `final` is differentiable."""
+
+    @staticmethod
+    def forward(ctx, anchor, h, target, lengths, mode, params, *tensors):
+        ts, vs = _bst_split(params)
+        B, T, nh = h.shape
+        na = target.shape[1]
+        att = torch.empty(B, T, device=h.device, dtype=torch.float32)
+        states = torch.empty(B, T, nh, device=h.device, dtype=torch.float32)
+        final = torch.empty(B, nh, device=h.device, dtype=torch.float32)
+        _lib_().recalgo_dien_evolve_fwd(_p(h), _p(target), _p(lengths), *[_p(t) for t in ts], B, T, na, nh, mode, _p(att),
+                                        _p(states), _p(final), _stream(h))
+        ctx.ts, ctx.vs, ctx.mode, ctx.lengths = ts, vs, mode, lengths
+        ctx.save_for_backward(h, target, att, states)
+        ctx.mark_non_differentiable(att, states)
+        return final, att, states
+
+    @staticmethod
+    def backward(ctx, g_final, _g_att, _g_states):
+        ts, vs, lengths = ctx.ts, ctx.vs, ctx.lengths
+        h, target, att, states = ctx.saved_tensors
+        B, T, nh = h.shape
+        na = target.shape[1]
+        g_final = g_final if g_final.is_contiguous() else g_final.contiguous()
+        lib = _lib_()
+        dh, dtarget = torch.empty_like(h), torch.empty_like(target)
+        outs = _bst_grad_buffers(ts, vs)                 # dw_att, dWg, dbg, dWc, dbc
+        ws = _workspace(int(lib.recalgo_dien_evolve_bwd_workspace_bytes(B, na, nh)), h.device)
+        lib.recalgo_dien_evolve_bwd(_p(h), _p(target), _p(lengths), *[_p(t) for t in ts], _p(att), _p(states), _p(g_final), B, T,
+                                    na, nh, ctx.mode, _p(dh), _p(dtarget), *[_p(o) for o in outs], _p(ws), _stream(h))
+        rets = [None if v is not None else o for o, v in zip(outs, vs)]
+        return (None, dh if ctx.needs_input_grad[1] else None, dtarget if ctx.needs_input_grad[2] else None, None, None, None,
+                *rets)
+
+
+def _dien_check(what, B, T, na, nh, params, shapes, names):
+    if not dien_supported(T, na, nh):
+        raise ValueError(f"{what}: the DIEN kernels serve 1 <= T <= {DIEN_MAX_T}, an input width in (4, 8, 12, 16) up to "
+                         f"{DIEN_MAX_NA} and a state width in (4, 8, 12, 16) up to {DIEN_MAX_NH}; got T={T} na={na} nh={nh} "
+                         "(there is no fallback)")
+    if B == 0:
+        raise ValueError(f"{what}: empty batch")
+    ts, _ = _bst_split(params)
+    for t, shape, name in zip(ts, shapes, names):
+        _chk(t, torch.float32, f"{what}: {name}")
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {shape}")
+
+
+def _dien_lengths(lengths, B, what):
+    if lengths is None:
+        return None
+    lengths = lengths.reshape(-1).to(torch.int32).contiguous()
+    if lengths.numel() != B:
+        raise ValueError(f"{what}: one length per example")
+    return lengths
+
+
+def dien_gru(x: torch.Tensor, lengths: Optional[torch.Tensor], Wg, bg, Wc, bc, anchor=None) -> torch.Tensor:
+    """dynamic_rnn over TF 1.14's GRUCell from a zero state (dien.py:196-203): x [B, T, na] -> h [B, T, nh]; with `lengths`
+    (integer [B]) the rows t >= L of h are zero, without it all T steps run.  Wg [na + nh, 2 nh], bg [2 nh], Wc [na + nh, nh],
+    bc [nh]: Variables (gradient to Variable.grad) or tensors.  Unsupported sizes: ValueError, there is no fallback."""
+    if x.dim() != 3:
+        raise ValueError("dien_gru: x must be [B, T, na]")
+    B, T, na = x.shape
+    params = [Wg, bg, Wc, bc]
+    bc_t = bc.data if isinstance(bc, Variable) else bc
+    nh = int(bc_t.shape[0]) if bc_t.dim() == 1 else 0
+    _dien_check("dien_gru", B, T, na, nh, params, [(na + nh, 2 * nh), (2 * nh,), (na + nh, nh), (nh,)], ("Wg", "bg", "Wc", "bc"))
+    _chk(x, torch.float32, "dien_gru: x")
+    tensors = [None if isinstance(p, Variable) else p for p in params]
+    return _DienGruFn.apply(anchor, x, _dien_lengths(lengths, B, "dien_gru"), params, *tensors)
+
+
+def dien_evolve(h: torch.Tensor, target: torch.Tensor, lengths: torch.Tensor, w_att, Wg, bg, Wc, bc, mode: str = "AGRU",
+                anchor=None):
+    """DIEN's interest evolution (dien.py:205-229) -> (final [B, nh], att [B, T], states [B, T, nh]): att = softmax over all T
+    of h[b, t] . (w_att target_b) with the entries t >= L replaced by -2^32, then the AGRU / AUGRU recurrence over the rows of
+    h with those weights; final is the state after step L - 1.  h [B, T, nh], target [B, na], lengths integer [B],
+    w_att [nh, na], the cell's Wg [2 nh, 2 nh], bg [2 nh], Wc [2 nh, nh], bc [nh].  Only `final` carries a gradient."""
+    if h.dim() != 3 or target.dim() != 2 or target.shape[0] != h.shape[0] or mode not in DIEN_MODES:
+        raise ValueError("dien_evolve: h must be [B, T, nh], target [B, na] and mode one of " + ", ".join(DIEN_MODES))
+    B, T, nh = h.shape
+    na = target.shape[1]
+    params = [w_att, Wg, bg, Wc, bc]
+    _dien_check("dien_evolve", B, T, na, nh, params, [(nh, na), (2 * nh, 2 * nh), (2 * nh,), (2 * nh, nh), (nh,)],
+                ("w_att", "Wg", "bg", "Wc", "bc"))
+    _chk(h, torch.float32, "dien_evolve: h")
+    _chk(target, torch.float32, "dien_evolve: target")
+    if lengths is None:
+        raise ValueError("dien_evolve: lengths are required")
+    tensors = [None if isinstance(p, Variable) else p for p in params]
+    return _DienEvolveFn.apply(anchor, h, target, _dien_lengths(lengths, B, "dien_evolve"), DIEN_MODES[mode], params, *tensors)
