@@ -81,6 +81,35 @@ const char* recalgo_pipeline_error(void* pipeline);
 int recalgo_pipeline_threads(void* pipeline);
 void recalgo_pipeline_close(void* pipeline);
 
+/* ---- in-memory requests: a batch of serialized tf.train.Example protos the caller already holds (a serving request; no file,
+ * no record framing) decoded by the file reader's own Example walk and vocabulary tables.  One decoder object per set of features:
+ * id_keys[n_ids] / id_vocabs: single-valued string features; bag_keys[n_bags] / bag_vocabs: multi-valued ("bag", sequence) string
+ * features; float_keys[n_floats] with float_n / float_default / float_has_default: FixedLenFeature((n,), float32[, default]) —
+ * the descriptions recalgo_pipeline_open takes.  NULL on a bad argument.  A decoder keeps no reference to a request; calls on ONE
+ * decoder must not overlap (it owns the error message). */
+void* recalgo_examples_open(int n_ids, const char* const* id_keys, const void* const* id_vocabs, int n_bags,
+                            const char* const* bag_keys, const void* const* bag_vocabs, int n_floats,
+                            const char* const* float_keys, const int32_t* float_n, const float* float_default,
+                            const int32_t* float_has_default);
+/* records[i] / lengths[i], i < n: the protos; nothing is read outside [records[i], records[i] + lengths[i]).
+ *   ids          [n, n_ids] row-major, column f = id_keys[f]; -1 = no value, or a value that is not in the vocabulary
+ *   floats       [n, sum float_n], columns in float_keys order; of a FloatList longer than float_n the first float_n values
+ *                (tf.parse_example would refuse the record; algorithm.utils.parse_example cuts it the same way)
+ *   bag_offsets  [n_bags, n + 1]: row g = the offsets of bag_keys[g] INTO ITS OWN values, which start at the sum of the totals
+ *                (row[n]) of the keys before it
+ *   bag_values   [bag_cap]: every key's looked-up values one key after the other; a value that is not in the vocabulary
+ *                stays in place as -1 (recalgo_reader_id_feature's rule)
+ * Returns the number of bag values (0 without bag keys).  When that exceeds bag_cap, ids, floats and bag_offsets are complete
+ * and bag_values is untouched: call again with room for the returned count.  Negative, with recalgo_examples_error saying
+ * which feature or record: -1 a record that does not parse (or a NULL buffer), -2 an id_keys feature holds several values in a
+ * record (it is a bag: open a decoder that lists it under bag_keys), -3 a float feature without a default is missing or short.
+ * threads <= 0: the whole decode on the calling thread; threads > 0: at most that many threads (this one included), one more
+ * per 64 records, started and joined inside the call.  Nothing is sized by the number of hardware threads. */
+int64_t recalgo_examples_decode(void* handle, const void* const* records, const uint64_t* lengths, int64_t n, int64_t* ids,
+                                float* floats, int64_t* bag_offsets, int64_t* bag_values, int64_t bag_cap, int threads);
+const char* recalgo_examples_error(const void* handle);
+void recalgo_examples_close(void* handle);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-"""ctypes binding of librecalgo_hip.so (the C-ABI declared in the headers that HEADERS and MORE_HEADERS below list).  The
+"""ctypes binding of librecalgo_hip.so (the C-ABI declared in the headers that HEADERS, MORE_HEADERS and SERVING_HEADERS below list).  The
 product path has NO CPU fallback: if the shared library is missing or a symbol declared in a header is absent, loading
 raises immediately."""
 from __future__ import annotations
@@ -32,12 +32,14 @@ def _versioned(header: str):
 
 
 # The headers of the HIP library, each the one statement of its part of the ABI (signatures, struct layouts, constants, a
-# version of its own, bumped on any signature change).  Two tables, one meaning: HEADERS is the list the host tests of the
-# first five features pin by length and order, so it stays as they state it; a header added since is one more entry of
-# MORE_HEADERS.  load() and scripts/abi_record.py walk both (all_headers()).
+# version of its own, bumped on any signature change).  Three tables, one meaning: HEADERS is the list the host tests of the
+# first five features pin by length and order, MORE_HEADERS (and all_headers(), the two as one) the list DIEN's host tests pin
+# the same way, so both stay as those tests state them; a header added since is one more entry of SERVING_HEADERS, which no
+# test pins by length.  load() and scripts/abi_record.py walk all three (every_header()).
 HEADERS = {h: _versioned(h) for h in ("recalgo.h", "recalgo_cgc.h", "recalgo_wide.h", "recalgo_bst.h",
                                               "recalgo_res.h")}
 MORE_HEADERS = {"recalgo_dien.h": _versioned("recalgo_dien.h")}
+SERVING_HEADERS = {"recalgo_serve.h": _versioned("recalgo_serve.h")}
 ABI = HEADERS["recalgo.h"]  # the first header's tables, under the names the product uses:
 SIGNATURES = ABI.functions  # name -> (restype, argtypes) of every function of the header
 STRUCTS = ABI.structs  # recalgo_*_t -> ctypes.Structure subclass
@@ -49,6 +51,11 @@ _lib = None  # the loaded library
 def all_headers() -> dict:
     """HEADERS and MORE_HEADERS as one table, in that order (read at call time: a test may replace either)."""
     return {**HEADERS, **MORE_HEADERS}
+
+
+def every_header() -> dict:
+    """Every header of the library: all_headers() and SERVING_HEADERS, in that order (read at call time, as all_headers())."""
+    return {**all_headers(), **SERVING_HEADERS}
 
 
 def launch_errcheck(name: str):
@@ -70,7 +77,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
                            "(there is no CPU fallback for the hot path)")
     import torch  # noqa: F401  (maps torch's libamdhip64 before ours resolves its NEEDED)
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    for abi in all_headers().values():
+    for abi in every_header().values():
         for name, (res, args) in abi.functions.items():
             try:
                 fn = getattr(lib, name)

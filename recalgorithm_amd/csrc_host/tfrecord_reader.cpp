@@ -1351,3 +1351,294 @@ EXPORT void recalgo_pipeline_close(void* pipeline) {
 }
 
 }  // extern "C"
+
+// =====================================================================================================
+// In-memory requests: a batch of serialized tf.train.Example protos that is already in the caller's memory (what a serving
+// request is) -> the same three products the file pipeline makes — the [n, n_ids] id matrix, the [n, sum n] float matrix —
+// plus offsets / values of the multi-valued ("bag", sequence) id features.  Same wire helpers, same map-entry walk, same
+// vocabulary table as the file reader; no file, no ring, no thread of its own.
+// =====================================================================================================
+namespace {
+
+// The map entries of an Example's Features (SequenceExample: of its context) in wire order: fn(name, Feature span).  The walk
+// of recalgo_reader_id_matrix / Pipeline::decode_chunk — the canonical entry by a few byte compares, anything else by the
+// generic field walk — with every level's verdict kept: false = some length or tag of the record does not parse.
+template <class Fn>
+bool each_entry(Span rec, Fn&& fn) {
+    bool inner = true;
+    const bool outer = for_fields(rec, [&](uint32_t field, uint32_t wt, Span features, uint64_t) {
+        if (field != 1 || wt != 2) return;                    // SequenceExample.feature_lists (2) is skipped
+        const bool ok = for_fields(features, [&](uint32_t f2, uint32_t w2, Span entry, uint64_t) {
+            if (f2 != 1 || w2 != 2) return;
+            std::string_view name;
+            Span feat;
+            if (!fast_map_entry(entry, name, feat)) {
+                const bool eok = for_fields(entry, [&](uint32_t f3, uint32_t w3, Span pl, uint64_t) {
+                    if (w3 != 2) return;
+                    if (f3 == 1) name = std::string_view((const char*)pl.p, pl.n);
+                    else if (f3 == 2) feat = pl;
+                });
+                if (!eok) inner = false;
+            }
+            fn(name, feat);
+        });
+        if (!ok) inner = false;
+    });
+    return outer && inner;
+}
+
+// the byte strings of a Feature's BytesList, in order
+template <class Fn>
+bool each_bytes(Span feat, Fn&& fn) {
+    bool inner = true;
+    const bool outer = for_fields(feat, [&](uint32_t f4, uint32_t w4, Span list, uint64_t) {
+        if (f4 != 1 || w4 != 2) return;
+        const bool ok = for_fields(list, [&](uint32_t f5, uint32_t w5, Span pl, uint64_t) {
+            if (f5 == 1 && w5 == 2) fn(pl);
+        });
+        if (!ok) inner = false;
+    });
+    return outer && inner;
+}
+
+// up to n values of a Feature's FloatList (packed or not) -> o; *filled = how many were there (at most n)
+bool read_floats(Span feat, float* o, int n, int* filled) {
+    bool inner = true;
+    int got = 0;
+    const bool outer = for_fields(feat, [&](uint32_t f4, uint32_t w4, Span list, uint64_t) {
+        if (f4 != 2 || w4 != 2) return;
+        const bool ok = for_fields(list, [&](uint32_t f5, uint32_t w5, Span pl, uint64_t) {
+            if (f5 != 1) return;
+            if (w5 == 2) {
+                for (size_t b = 0; b + 4 <= pl.n && got < n; b += 4) memcpy(&o[got++], pl.p + b, 4);
+            } else if (w5 == 5 && got < n) {
+                memcpy(&o[got++], pl.p, 4);
+            }
+        });
+        if (!ok) inner = false;
+    });
+    *filled = got;
+    return outer && inner;
+}
+
+constexpr int kExMalformed = -1, kExSeveral = -2, kExMissing = -3;    // recalgo_examples_decode's error returns
+constexpr size_t kExChunk = 64;                            // records a thread must have before one more thread is started
+
+struct Examples {
+    size_t F = 0, G = 0, NF = 0;                           // single-valued id keys, bag keys, float columns
+    std::vector<std::string> keys;                         // ids, then bags
+    std::vector<const Vocab*> vocabs;                      // ids, then bags
+    std::vector<PipeFloat> floats;
+    std::vector<std::string_view> names;                   // ids, bags, floats: the requested feature names
+    std::vector<int> ntab;                                 // name -> index into `names` (open addressing)
+    size_t tcap = 16;
+    std::string error;
+
+    int lookup(std::string_view name) const {
+        size_t t = name_hash(name) & (tcap - 1);
+        while (ntab[t] >= 0 && names[(size_t)ntab[t]] != name) t = (t + 1) & (tcap - 1);
+        return ntab[t];
+    }
+};
+
+struct ExFault {                                           // the first record of a range that could not be decoded
+    int code = 0;
+    int64_t rec = -1;
+    std::string what;
+};
+
+// Records [i0, i1): ids, floats, and per bag key the value COUNT (at offsets[g][i + 1]) and the Feature span (for the second pass).
+void examples_pass1(const Examples& E, const void* const* records, const uint64_t* lengths, int64_t n, int64_t i0, int64_t i1,
+                    int64_t* ids, float* floats, int64_t* bag_offsets, Span* bag_feat, ExFault& fault) {
+    const size_t F = E.F, G = E.G, NF = E.NF;
+    std::vector<char> got(E.floats.size());
+    auto fail = [&](int code, int64_t i, std::string what) {
+        if (fault.code == 0) fault = ExFault{code, i, std::move(what)};
+    };
+    for (int64_t i = i0; i < i1; ++i) {
+        for (size_t f = 0; f < F; ++f) ids[(size_t)i * F + f] = -1;
+        for (size_t g = 0; g < G; ++g) {
+            bag_offsets[g * (size_t)(n + 1) + (size_t)i + 1] = 0;
+            bag_feat[(size_t)i * G + g] = Span{};
+        }
+        std::fill(got.begin(), got.end(), 0);
+        if (!records[i] && lengths[i]) {
+            fail(kExMalformed, i, "record " + std::to_string(i) + " is a NULL pointer");
+            continue;
+        }
+        bool values_ok = true;
+        const bool ok = each_entry(Span{(const uint8_t*)records[i], (size_t)lengths[i]}, [&](std::string_view name, Span feat) {
+            const int col = E.lookup(name);
+            if (col < 0) return;                           // not a requested feature
+            if ((size_t)col < F) {                         // a repeated map key: the last entry wins (protobuf map semantics)
+                int cnt = 0;
+                Span first;
+                if (!fast_single_bytes(feat, first, cnt)) {
+                    cnt = 0;
+                    if (!each_bytes(feat, [&](Span pl) { if (cnt++ == 0) first = pl; })) values_ok = false;
+                }
+                if (cnt > 1) fail(kExSeveral, i, "feature " + E.keys[(size_t)col] + " holds more than one value in a record");
+                ids[(size_t)i * F + (size_t)col] = cnt == 0 ? -1 : E.vocabs[(size_t)col]->find(std::string_view((const char*)first.p, first.n));
+            } else if ((size_t)col < F + G) {
+                const size_t g = (size_t)col - F;
+                int64_t cnt = 0;
+                if (!each_bytes(feat, [&](Span) { ++cnt; })) values_ok = false;
+                bag_offsets[g * (size_t)(n + 1) + (size_t)i + 1] = cnt;
+                bag_feat[(size_t)i * G + g] = feat;
+            } else {
+                const size_t k = (size_t)col - F - G;
+                const PipeFloat& pf = E.floats[k];
+                int filled = 0;
+                if (!read_floats(feat, floats + (size_t)i * NF + pf.off, pf.n, &filled)) values_ok = false;
+                got[k] = filled >= pf.n ? 1 : (filled == 0 ? 0 : 2);
+            }
+        });
+        if (!ok || !values_ok) {
+            if (fault.code == 0 || fault.rec == i) fault = ExFault{kExMalformed, i, "malformed Example in record " + std::to_string(i)};
+            for (size_t g = 0; g < G; ++g) {               // (nothing of a malformed record is walked again)
+                bag_offsets[g * (size_t)(n + 1) + (size_t)i + 1] = 0;
+                bag_feat[(size_t)i * G + g] = Span{};
+            }
+            continue;
+        }
+        for (size_t k = 0; k < E.floats.size(); ++k) {
+            if (got[k] == 1) continue;
+            const PipeFloat& pf = E.floats[k];
+            if (got[k] == 0 && pf.has_def) {
+                for (int c = 0; c < pf.n; ++c) floats[(size_t)i * NF + pf.off + (size_t)c] = pf.def;
+            } else {
+                fail(kExMissing, i, "feature " + pf.key + " is required but missing in record " + std::to_string(i));
+            }
+        }
+    }
+}
+
+// Records [i0, i1): the bag values, looked up, at base[g] + offsets[g][i] (the offsets are prefix sums by now).
+void examples_pass2(const Examples& E, int64_t n, int64_t i0, int64_t i1, const int64_t* bag_offsets, const Span* bag_feat,
+                    const std::vector<int64_t>& base, int64_t* bag_values) {
+    for (int64_t i = i0; i < i1; ++i)
+        for (size_t g = 0; g < E.G; ++g) {
+            const Vocab& vm = *E.vocabs[E.F + g];
+            int64_t at = base[g] + bag_offsets[g * (size_t)(n + 1) + (size_t)i];
+            each_bytes(bag_feat[(size_t)i * E.G + g], [&](Span pl) {
+                bag_values[at++] = vm.find(std::string_view((const char*)pl.p, pl.n));
+            });
+        }
+}
+
+// f(part, i0, i1) over [0, n) cut into `parts` contiguous ranges: part 0 on the calling thread, the others on threads of
+// this call (joined before it returns)
+template <class Fn>
+void examples_fan_out(int64_t n, size_t parts, Fn&& f) {
+    if (parts <= 1) {
+        f((size_t)0, (int64_t)0, n);
+        return;
+    }
+    const int64_t per = (n + (int64_t)parts - 1) / (int64_t)parts;
+    std::vector<std::thread> th;
+    th.reserve(parts - 1);
+    for (size_t p = 1; p < parts; ++p) {
+        const int64_t a = std::min(n, per * (int64_t)p), b = std::min(n, a + per);
+        th.emplace_back([&f, p, a, b] { f(p, a, b); });
+    }
+    f((size_t)0, (int64_t)0, std::min(n, per));
+    for (auto& t : th) t.join();
+}
+
+}  // namespace
+
+extern "C" {
+
+// id_keys[n_ids] / id_vocabs: single-valued string features; bag_keys[n_bags] / bag_vocabs: multi-valued ones; float_keys[n_floats]
+// with float_n / float_default / float_has_default as recalgo_pipeline_open takes them.  NULL on a bad argument.
+EXPORT void* recalgo_examples_open(int n_ids, const char* const* id_keys, const void* const* id_vocabs, int n_bags,
+                                   const char* const* bag_keys, const void* const* bag_vocabs, int n_floats,
+                                   const char* const* float_keys, const int32_t* float_n, const float* float_default,
+                                   const int32_t* float_has_default) {
+    if (n_ids < 0 || n_bags < 0 || n_floats < 0) return nullptr;
+    if ((n_ids > 0 && (!id_keys || !id_vocabs)) || (n_bags > 0 && (!bag_keys || !bag_vocabs)) ||
+        (n_floats > 0 && (!float_keys || !float_n || !float_default || !float_has_default)))
+        return nullptr;
+    auto* E = new Examples();
+    E->F = (size_t)n_ids;
+    E->G = (size_t)n_bags;
+    bool bad = false;
+    for (int f = 0; f < n_ids; ++f) {
+        if (!id_keys[f] || !id_vocabs[f]) { bad = true; break; }
+        E->keys.emplace_back(id_keys[f]);
+        E->vocabs.push_back((const Vocab*)id_vocabs[f]);
+    }
+    for (int g = 0; g < n_bags && !bad; ++g) {
+        if (!bag_keys[g] || !bag_vocabs[g]) { bad = true; break; }
+        E->keys.emplace_back(bag_keys[g]);
+        E->vocabs.push_back((const Vocab*)bag_vocabs[g]);
+    }
+    size_t off = 0;
+    for (int k = 0; k < n_floats && !bad; ++k) {
+        if (!float_keys[k] || float_n[k] < 1) { bad = true; break; }
+        E->floats.push_back(PipeFloat{float_keys[k], float_n[k], float_default[k], float_has_default[k] != 0, off});
+        off += (size_t)float_n[k];
+    }
+    if (bad) {
+        delete E;
+        return nullptr;
+    }
+    E->NF = off;
+    for (auto& k : E->keys) E->names.emplace_back(k);
+    for (auto& pf : E->floats) E->names.emplace_back(pf.key);
+    while (E->tcap < 4 * E->names.size() + 4) E->tcap <<= 1;
+    E->ntab.assign(E->tcap, -1);
+    for (size_t f = 0; f < E->names.size(); ++f) {           // a name given twice maps to its first entry
+        size_t i = name_hash(E->names[f]) & (E->tcap - 1);
+        while (E->ntab[i] >= 0 && E->names[(size_t)E->ntab[i]] != E->names[f]) i = (i + 1) & (E->tcap - 1);
+        if (E->ntab[i] < 0) E->ntab[i] = (int)f;
+    }
+    return E;
+}
+
+// See include/recalgo_host.h.  Returns the number of bag values (>= 0), or -1 / -2 / -3.
+EXPORT int64_t recalgo_examples_decode(void* handle, const void* const* records, const uint64_t* lengths, int64_t n,
+                                       int64_t* ids, float* floats, int64_t* bag_offsets, int64_t* bag_values,
+                                       int64_t bag_cap, int threads) {
+    auto* E = (Examples*)handle;
+    if (!E) return kExMalformed;
+    E->error.clear();
+    if (n < 0 || (n > 0 && (!records || !lengths || (E->F && !ids) || (E->NF && !floats))) || (E->G && !bag_offsets) || bag_cap < 0 ||
+        (bag_cap > 0 && !bag_values)) {
+        E->error = "recalgo_examples_decode: a NULL buffer or a negative count";
+        return kExMalformed;
+    }
+    size_t parts = 1;
+    if (threads > 0) parts = std::max<size_t>(1, std::min<size_t>((size_t)threads, (size_t)n / kExChunk));
+    std::vector<Span> bag_feat((size_t)n * E->G);
+    std::vector<ExFault> faults(parts);
+    examples_fan_out(n, parts, [&](size_t p, int64_t a, int64_t b) {
+        examples_pass1(*E, records, lengths, n, a, b, ids, floats, bag_offsets, bag_feat.data(), faults[p]);
+    });
+    for (auto& f : faults)                                   // (ranges are in record order: the first fault is the lowest record's)
+        if (f.code != 0) {
+            E->error = f.what;
+            return f.code;
+        }
+    std::vector<int64_t> base(E->G, 0);
+    int64_t total = 0;
+    for (size_t g = 0; g < E->G; ++g) {
+        int64_t* o = bag_offsets + g * (size_t)(n + 1);
+        o[0] = 0;
+        for (int64_t i = 0; i < n; ++i) o[i + 1] += o[i];
+        base[g] = total;
+        total += o[n];
+    }
+    if (total > bag_cap) return total;
+    if (total > 0)
+        examples_fan_out(n, parts, [&](size_t, int64_t a, int64_t b) {
+            examples_pass2(*E, n, a, b, bag_offsets, bag_feat.data(), base, bag_values);
+        });
+    return total;
+}
+
+EXPORT const char* recalgo_examples_error(const void* handle) { return handle ? ((const Examples*)handle)->error.c_str() : ""; }
+
+EXPORT void recalgo_examples_close(void* handle) { delete (Examples*)handle; }
+
+}  // extern "C"

@@ -13,7 +13,9 @@ protos.  Here a model is its model_fn + params (code) and its variables: an expo
                                                        serving.json       receiver feature spec, prediction keys, eval result
 
 and `ServingModel(model_fn, params, export_dir)` is the serving side: `predict(serialized_examples)` parses the protos
-with the exported feature spec (the parsing receiver) and runs the PREDICT graph on the HIP kernels.  The variable file
+with the exported feature spec (the parsing receiver) and runs the PREDICT graph on the HIP kernels; `serve` is the same
+contract with the native decoder of include/recalgo_host.h in front and, after `compile(batch_sizes)`, one captured graph per
+batch bucket behind it (DESIGN.md §5 "Serving").  The variable file
 uses the reference's names and shapes (Estimator.export_variables), so it is interchangeable with a dump of a
 reference-trained TF checkpoint (scripts/tf_ckpt_to_npz.py) — either loads into either.
 """
@@ -147,9 +149,77 @@ def latest_export(export_path: str) -> Optional[str]:
     return ex[-1] if ex else None
 
 
+def plan_chunks(n: int, buckets: Sequence[int]) -> List[tuple]:
+    """How a request of n rows runs on graphs captured for the batch sizes `buckets`: [(first row, rows, bucket)], in row
+    order, every row once.  Full chunks of the largest bucket while more than that is left, then the smallest bucket that
+    holds the rest (padded up to it).  Pure: no device, no model."""
+    sizes = sorted({int(b) for b in buckets})
+    if not sizes or sizes[0] < 1:
+        raise ValueError(f"plan_chunks: the buckets must be positive batch sizes, got {list(buckets)}")
+    n = int(n)
+    if n < 0:
+        raise ValueError("plan_chunks: a request has no negative number of rows")
+    out, at = [], 0
+    while n - at > sizes[-1]:
+        out.append((at, sizes[-1], sizes[-1]))
+        at += sizes[-1]
+    if n - at > 0:
+        out.append((at, n - at, next(b for b in sizes if b >= n - at)))
+    return out
+
+
+def fold_batch_norms(arrays: Dict[str, "torch.Tensor"], epsilon: Optional[float] = None) -> dict:
+    """{<scope>/gamma: (scale, shift)} of every BatchNorm among the named arrays of a model (<scope>/gamma, beta, moving_mean,
+    moving_variance): nn.fold_batch_norm on each, computed once when an export is compiled.  Pure."""
+    from . import nn
+    eps = nn.BN_EPSILON if epsilon is None else float(epsilon)
+    out = {}
+    for name in arrays:
+        if name.endswith("/gamma"):
+            scope = name[:-len("gamma")]
+            parts = [arrays.get(scope + k) for k in ("beta", "moving_mean", "moving_variance")]
+            if all(p is not None for p in parts):
+                out[name] = tuple(t.contiguous() for t in nn.fold_batch_norm(arrays[name], *parts, eps))
+    return out
+
+
+def _columns_by_key(params: dict) -> dict:
+    """feature key -> the CategoricalColumn / NumericColumn behind it, from every column (list) among a model's params"""
+    from .feature_column import CategoricalColumn, NumericColumn
+    found: dict = {}
+
+    def visit(o):
+        if isinstance(o, (list, tuple)):
+            for v in o:
+                visit(v)
+            return
+        base = getattr(o, "categorical_column", o)
+        for c in getattr(base, "keys", None) or [base]:                  # (a crossed column: its two key columns)
+            if isinstance(c, (CategoricalColumn, NumericColumn)):
+                found.setdefault(c.key, c)
+    for v in params.values():
+        visit(v)
+    return found
+
+
+class _Bucket:
+    """One captured PREDICT graph: its static input span (ids, then floats: the staging layout), the feature views over it, the
+    static outputs, and the serving plan whose BatchNorm folds the captured tower reads."""
+    __slots__ = ("rows", "span", "features", "graph", "out", "tower", "plan")
+
+
 class ServingModel:
     """The serving side of an export: model_fn + params (the code) + an export directory (the variables and the
-    receiver's feature spec).  predict(serialized tf.train.Example protos) -> {prediction key: array [n, ...]}."""
+    receiver's feature spec).
+
+        predict(serialized tf.train.Example protos) -> {prediction key: array [n, ...]}     Python decode, eager model_fn
+        serve(protos)                                -> the same dict                        native decode (recalgo_examples_*),
+                                                                                             then the compiled graph of the
+                                                                                             request's bucket — or, without
+                                                                                             compile(), the eager model_fn
+        compile(batch_sizes)                         captures the PREDICT graph once per bucket size"""
+
+    DECODE_THREADS = 4            # recalgo_examples_decode's `threads` for requests of 256 rows and more (never the host's core count)
 
     def __init__(self, model_fn, params: dict, export_dir: str, device=None):
         from .estimator import Estimator, RunConfig
@@ -160,15 +230,234 @@ class ServingModel:
         self.estimator = Estimator(model_fn, params, RunConfig(device=device))
         self._variables = dict(np.load(os.path.join(export_dir, "variables.npz")))
         self._loaded = False
+        self._decoder = None
+        self._learned_bags: set = set()       # keys not declared as sequences that a request showed to hold several values
+        self._buckets: Dict[int, _Bucket] = {}
+        self.graphs_dropped_by: Optional[str] = None     # the feature whose several values made serve() drop the compiled graphs
+
+    @property
+    def compiled_buckets(self) -> List[int]:
+        """The bucket sizes serve() has a captured graph for right now: empty before compile(), and again after a request
+        turned a column into a bag (`graphs_dropped_by` names it; a process that watches this sees the downgrade)."""
+        return sorted(self._buckets)
+
+    def tower_buckets(self) -> List[int]:
+        """the buckets whose captured graph holds the fused tower's launch"""
+        return sorted(size for size, b in self._buckets.items() if b.tower)
 
     def predict(self, serialized_examples: Sequence[bytes]) -> Dict[str, np.ndarray]:
         from .estimator import ModeKeys
         est = self.estimator
         features = self.receiver(serialized_examples)
         features, _ = est._to_device(features, None)
-        if not self._loaded:
-            est._build(features, None, ModeKeys.PREDICT)
-            est.load_variables(self._variables)
-            self._loaded, self._variables = True, None
+        self._ensure_loaded(features)
         spec = est._call_model_fn(features, None, ModeKeys.PREDICT)
         return {k: v.detach().cpu().numpy() for k, v in spec.predictions.items()}
+
+    def _ensure_loaded(self, features) -> None:
+        from .estimator import ModeKeys
+        if not self._loaded:
+            self.estimator._build(features, None, ModeKeys.PREDICT)
+            self.estimator.load_variables(self._variables)
+            self._loaded, self._variables = True, None
+
+    # ---- the native decoder: what the receiver's feature spec asks for, described by the model's own columns -------------------
+    def _layout(self):
+        """-> (single-valued id keys, bag keys, float keys [(key, shape, n, default)]), each in sorted key order"""
+        from .feature_column import CategoricalColumn
+        cols = _columns_by_key(self.estimator.params)
+        ids, bags, floats = [], [], []
+        for key in sorted(self.feature_spec):
+            sp = self.feature_spec[key]
+            if sp[0] == "fixed":
+                floats.append((key, tuple(sp[2]), int(np.prod(sp[2])), sp[3]))
+                continue
+            col = cols.get(key)
+            if not isinstance(col, CategoricalColumn) or not col.vocabulary_file:
+                raise NotImplementedError(f"serve: the native decoder needs a vocabulary-file column for feature {key!r} "
+                                          "(predict() decodes anything the receiver's spec describes)")
+            (bags if (col.is_sequence or key in self._learned_bags) else ids).append((key, col))
+        return ids, bags, floats
+
+    def ragged_keys(self) -> List[str]:
+        """The features that reach the model as a Ragged (bags, histories): declared sequences, and keys a request showed to
+        hold several values.  A model with any is served eagerly: compile() refuses it."""
+        return [k for k, _ in self._layout()[1]]
+
+    def _open_decoder(self):
+        from .io import native
+        if self._decoder is None:
+            ids, bags, floats = self._layout()
+            dec = native.ExampleDecoder([(k, c.vocabulary_file) for k, c in ids], [(k, c.vocabulary_file) for k, c in bags],
+                                        [(k, n, d) for k, _, n, d in floats])
+            self._decoder = (dec, ids, bags, floats)
+        return self._decoder
+
+    @staticmethod
+    def _span_bytes(rows: int, F: int, NF: int):
+        """the staging / static-input layout of `rows` rows: [ids int64 [rows, F] | pad to 16 bytes | floats float32 [rows, NF]]"""
+        id_bytes = (rows * F * 8 + 15) // 16 * 16
+        return id_bytes, id_bytes + max(rows * NF * 4, 16)
+
+    def _views(self, span, rows: int):
+        """the feature dict over a uint8 span of that layout (host or device): id columns of one matrix, float blocks of another"""
+        import torch
+        _, ids, _, floats = self._open_decoder()
+        F, NF = len(ids), sum(n for _, _, n, _ in floats)
+        id_bytes, _ = self._span_bytes(rows, F, NF)
+        feats = {}
+        if F:
+            mat = span[:rows * F * 8].view(torch.int64).view(rows, F)
+            feats.update({k: mat[:, j] for j, (k, _) in enumerate(ids)})
+        if NF:
+            fmat = span[id_bytes:id_bytes + rows * NF * 4].view(torch.float32).view(rows, NF)
+            off = 0
+            for k, shape, n, _ in floats:
+                feats[k] = fmat[:, off:off + n].view((rows,) + shape)
+                off += n
+        return feats
+
+    def _decode_to(self, records, rows: int, dst=None):
+        """Decodes `records` (at most `rows`) into pinned staging of the `rows`-row layout — the rows past the request padded with
+        id -1 / 0.0 — and moves it with ONE copy: into `dst` (a bucket's static span), or to a new device span.
+        -> (device span, {bag key: (offsets, values)})"""
+        import torch
+        from .io.native import SeveralValues
+        est = self.estimator
+        while True:
+            dec, ids, bags, floats = self._open_decoder()
+            F, NF, n = len(ids), sum(k[2] for k in floats), len(records)
+            id_bytes, total = self._span_bytes(rows, F, NF)
+            got = {}
+
+            def fill(buf, dec=dec, F=F, NF=NF, n=n, id_bytes=id_bytes):
+                host = buf.numpy()
+                mat = host[:rows * F * 8].view(np.int64).reshape(rows, F)
+                fmat = host[id_bytes:id_bytes + rows * NF * 4].view(np.float32).reshape(rows, NF)
+                got["bags"] = dec.decode(records, ids=mat[:n], floats=fmat[:n], threads=self.DECODE_THREADS if n >= 256 else 0)[2]
+                mat[n:] = -1
+                fmat[n:] = 0.0
+            try:
+                if est.device.type != "cuda":
+                    buf = torch.empty(total, dtype=torch.uint8)
+                    fill(buf)
+                    return buf, got["bags"]
+                return est._h2d(fill, (total,), torch.uint8, dst=dst), got["bags"]
+            except SeveralValues as e:
+                # a column that is not declared a sequence holds several values: from now on it is decoded as a bag, and a
+                # model with a bag is not served from captured graphs (compile() says so)
+                if e.key is None or e.key in self._learned_bags:
+                    raise
+                import warnings
+                self._learned_bags.add(e.key)
+                self._decoder = None
+                if self._buckets:
+                    warnings.warn(f"serve: feature {e.key!r} holds several values in a record; the compiled graphs are dropped "
+                                  "and requests are served eagerly")
+                    self._buckets, self.graphs_dropped_by = {}, e.key
+                dst = None
+
+    def _ragged_features(self, bags, n: int):
+        """{key: Ragged | dense ids} of the decoded bags, as CategoricalColumn.ids presents a parsed request: a column that is not
+        a sequence and holds at most one value per row in THIS request is a dense [n] id vector (-1 where it has none)."""
+        import torch
+        from .feature_column import Ragged
+        dev, out = self.estimator.device, {}
+        cols = {k: c for k, c in self._open_decoder()[2]}
+        for key, (offsets, values) in bags.items():
+            lens = np.diff(offsets)
+            if not cols[key].is_sequence and n > 0 and int(lens.max()) <= 1:
+                dense = np.full(n, -1, dtype=np.int64)
+                dense[lens == 1] = values
+                out[key] = torch.from_numpy(dense).to(dev)
+            else:
+                out[key] = Ragged(torch.from_numpy(np.ascontiguousarray(values)).to(dev), torch.from_numpy(offsets.copy()).to(dev))
+        return out
+
+    # ---- serving ----------------------------------------------------------------------------------------------------------------
+    def serve(self, serialized_examples: Sequence[bytes]) -> Dict[str, np.ndarray]:
+        """predict()'s contract on the native decoder: the compiled graph of the request's bucket when compile() has run (a
+        request larger than the largest bucket in chunks), the eager PREDICT model_fn otherwise."""
+        import torch
+        from .estimator import ModeKeys
+        records = list(serialized_examples)
+        n = len(records)
+        if self._buckets and n > 0:
+            parts = []
+            for at, rows, size in plan_chunks(n, list(self._buckets)):
+                if not self._buckets:             # (a request that turned a column into a bag dropped the graphs)
+                    break
+                b = self._buckets[size]
+                self._decode_to(records[at:at + rows], size, dst=b.span)
+                if not self._buckets:
+                    break
+                b.graph.replay()
+                parts.append({k: v[:rows].cpu().numpy() for k, v in b.out.items()})
+            else:
+                return {k: (np.concatenate([p[k] for p in parts]) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        with torch.no_grad():
+            span, bags = self._decode_to(records, n)
+            features = self._views(span, n)
+            features.update(self._ragged_features(bags, n))
+            self._ensure_loaded(features)
+            spec = self.estimator._call_model_fn(features, None, ModeKeys.PREDICT)
+        return {k: v.detach().cpu().numpy() for k, v in spec.predictions.items()}
+
+    def compile(self, batch_sizes: Sequence[int] = (1, 16, 64, 256, 1024, 4096), warmup: int = 2) -> "ServingModel":
+        """Captures the PREDICT model_fn once per bucket size into a torch.cuda.CUDAGraph over private static inputs (one stream,
+        no forked branch; warm-up on a side stream, then capture_error_mode="thread_local", as estimator.GraphedTrainStep).
+        Under the capture the VariableStore's serving switch is on: buckets of at most nn.SERVE_TOWER_MAX_ROWS rows run their
+        hidden stack as ONE launch with the BatchNorms folded (nn.LazyTower); the folds are computed here, once.
+        A model whose decoded features contain a Ragged is not compiled: NotImplementedError names the keys; serve() still
+        serves it (native decode, eager model_fn)."""
+        import torch
+        from . import nn
+        from .estimator import ModeKeys
+        est = self.estimator
+        sizes = sorted({int(b) for b in batch_sizes})
+        if not sizes or sizes[0] < 1:
+            raise ValueError(f"compile: batch_sizes must be positive, got {list(batch_sizes)}")
+        ragged = self.ragged_keys()
+        if ragged:
+            raise NotImplementedError("compile: the decoded features " + ", ".join(ragged) + " are ragged (bags / histories); graphs "
+                                      "over fixed-capacity ragged buffers are not built yet — serve() serves this model eagerly")
+        if est.device.type != "cuda":
+            raise RuntimeError("compile: captured graphs need a HIP device")
+        _, ids, _, floats = self._open_decoder()
+        F, NF = len(ids), sum(k[2] for k in floats)
+        folds = None
+        buckets: Dict[int, _Bucket] = {}
+        with torch.no_grad():
+            for size in sizes:
+                b = _Bucket()
+                b.rows = size
+                b.span = torch.zeros(self._span_bytes(size, F, NF)[1], dtype=torch.uint8, device=est.device)
+                b.features = self._views(b.span, size)
+                if F:
+                    b.span[:size * F * 8].view(torch.int64).fill_(-1)          # (a bucket of padding rows: id -1, 0.0)
+                self._ensure_loaded(b.features)
+                if folds is None:
+                    folds = fold_batch_norms(est.store.named_arrays())
+                plan = nn.ServingPlan(nn.SERVE_TOWER_MAX_ROWS, folds, nn.BN_EPSILON)
+
+                def run(b=b, plan=plan):
+                    est.store.serving = plan
+                    try:
+                        return dict(est._call_model_fn(b.features, None, ModeKeys.PREDICT).predictions)
+                    finally:
+                        est.store.serving = None
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    for _ in range(max(int(warmup), 1)):
+                        run()
+                torch.cuda.current_stream().wait_stream(side)
+                torch.cuda.synchronize()
+                b.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(b.graph, capture_error_mode="thread_local"):
+                    b.out = run()
+                b.tower = plan.tower_launches > 0          # (whether the captured graph holds the fused tower's launch)
+                b.plan = plan                     # (the captured launches read the folds: they live as long as the graph)
+                buckets[size] = b
+        self._buckets = buckets
+        return self

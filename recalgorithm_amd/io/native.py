@@ -74,6 +74,86 @@ class Vocabulary:
         return int(load().recalgo_vocab_lookup(self.h, key, len(key)))
 
 
+class SeveralValues(ValueError):
+    """recalgo_examples_decode answered -2: `key`, declared single-valued, holds several values in some record."""
+
+    def __init__(self, message: str):
+        super().__init__(message)
+        pre, suf = "feature ", " holds more than one value in a record"
+        self.key = message[len(pre):len(message) - len(suf)] if message.startswith(pre) and message.endswith(suf) else None
+
+
+class ExampleDecoder:
+    """recalgo_examples_* of include/recalgo_host.h: serialized tf.train.Example protos that are already in memory (a serving
+    request) -> ids int64 [n, len(id_keys)], floats float32 [n, sum n], and per bag key (offsets int64 [n + 1], values int64).
+    id_keys / bag_keys: [(feature key, vocabulary file)], single-valued / multi-valued; float_keys: [(key, n, default | None)].
+    `decode(records, ids=, floats=)` writes into caller-owned arrays (e.g. views of pinned staging) when given."""
+
+    def __init__(self, id_keys, bag_keys, float_keys):
+        lib = load()
+        self.id_keys, self.bag_keys, self.float_keys = list(id_keys), list(bag_keys), list(float_keys)
+        self._vocabs = [Vocabulary.get(path) for _, path in self.id_keys + self.bag_keys]        # (kept alive with the decoder)
+        F, G, NF = len(self.id_keys), len(self.bag_keys), len(self.float_keys)
+        self.n_floats = sum(int(n) for _, n, _ in self.float_keys)
+        chars = lambda keys: (ctypes.c_char_p * max(len(keys), 1))(*[k.encode() for k in keys])
+        self.h = lib.recalgo_examples_open(
+            F, chars([k for k, _ in self.id_keys]), (c_void_p * max(F, 1))(*[v.h for v in self._vocabs[:F]]),
+            G, chars([k for k, _ in self.bag_keys]), (c_void_p * max(G, 1))(*[v.h for v in self._vocabs[F:]]),
+            NF, chars([k for k, _, _ in self.float_keys]), (ctypes.c_int32 * max(NF, 1))(*[int(n) for _, n, _ in self.float_keys]),
+            (ctypes.c_float * max(NF, 1))(*[float(d or 0.0) for _, _, d in self.float_keys]),
+            (ctypes.c_int32 * max(NF, 1))(*[int(d is not None) for _, _, d in self.float_keys]))
+        if not self.h:
+            raise ValueError("recalgo_examples_open refused the feature descriptions")
+        self._bag_cap = 0
+
+    def close(self):
+        if self.h:
+            load().recalgo_examples_close(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001   (interpreter shutdown: the library may be gone)
+            pass
+
+    def decode(self, records, ids: Optional[np.ndarray] = None, floats: Optional[np.ndarray] = None, threads: int = 0,
+               bag_cap: Optional[int] = None):
+        """-> (ids [n, F], floats [n, NF], {bag key: (offsets [n + 1], values [nnz])}).  Raises ValueError for a record that
+        does not parse or a required float that is missing, SeveralValues for an id key that is a bag."""
+        lib = load()
+        n, F, G, NF = len(records), len(self.id_keys), len(self.bag_keys), self.n_floats
+        bufs = [r if isinstance(r, bytes) else bytes(r) for r in records]
+        ptrs = (ctypes.c_char_p * max(n, 1))(*bufs)
+        lens = (ctypes.c_uint64 * max(n, 1))(*[len(b) for b in bufs])
+        if ids is None:
+            ids = np.empty((n, F), dtype=np.int64)
+        if floats is None:
+            floats = np.empty((n, NF), dtype=np.float32)
+        for a, shape, dt in ((ids, (n, F), np.int64), (floats, (n, NF), np.float32)):
+            if a.shape != shape or a.dtype != dt or not a.flags["C_CONTIGUOUS"]:
+                raise ValueError(f"ExampleDecoder.decode: the output array must be C-contiguous {np.dtype(dt).name} {shape}")
+        offsets = np.zeros((max(G, 1), n + 1), dtype=np.int64)
+        cap = int(self._bag_cap if bag_cap is None else bag_cap)
+        while True:
+            values = np.empty(max(cap, 1), dtype=np.int64)
+            rc = int(lib.recalgo_examples_decode(self.h, ptrs, lens, n, ids.ctypes.data_as(c_void_p), floats.ctypes.data_as(c_void_p),
+                                                 offsets.ctypes.data_as(c_void_p), values.ctypes.data_as(c_void_p), cap, int(threads)))
+            if rc < 0:
+                msg = lib.recalgo_examples_error(self.h).decode()
+                raise SeveralValues(msg) if rc == -2 else ValueError(msg)
+            if rc <= cap or bag_cap is not None:
+                break
+            cap = self._bag_cap = rc               # (remembered: the next request of this size decodes once)
+        self.last_needed = rc
+        bags, base = {}, 0
+        for g, (key, _) in enumerate(self.bag_keys):
+            total = int(offsets[g, n])
+            bags[key] = (offsets[g], values[base:base + total] if rc <= cap else None)
+            base += total
+        return ids, floats, bags
+
+
 class PackedBatch(dict):
     """A decoded feature batch whose single-valued id features are column views of ONE contiguous [B, F] int64 matrix,
     columns in SORTED key order (the order feature_column.input_layer consumes them in): `packed_ids = (matrix, keys)`.

@@ -266,7 +266,96 @@ class LazyDense:
 
 
 def _resolved(t):
-    return t.materialize() if isinstance(t, LazyDense) else t
+    return t.materialize() if isinstance(t, (LazyDense, LazyTower)) else t
+
+
+# ServingModel.compile's switch (VariableStore.serving) routes the hidden stack of a PREDICT graph into ONE launch (ops.serve_tower)
+# for request buckets of at most this many rows: the largest measured bucket at which the compiled graph with the fused tower
+# is no slower than the compiled graph on the per-layer kernels (profiles/serving_bench.json, DESIGN.md §5 "Serving").
+SERVE_TOWER_MAX_ROWS = 4096
+# ...and only where the tower folds at least one BatchNorm.  A plain dense(relu) stack (DCN's) is three launches of the dense
+# engine, which the same measurement has FASTER than the tower at every size (0.044 against 0.058 ms of device time per request
+# at n = 1): such a stack is collected all the same — whether a BatchNorm follows is known only at the end — and then runs
+# on the per-layer kernels, the launches it would have had without the switch.  True: plain stacks take the tower too (tests, the bench).
+SERVE_TOWER_PLAIN_STACKS = False
+
+
+class ServingPlan:
+    """What ServingModel.compile hangs on VariableStore.serving while it captures a bucket: the row limit of the fused tower
+    for this bucket and the BatchNorm folds, computed once per export: {<scope>/gamma: (scale, shift)} at `epsilon`.
+    `tower_launches` counts the ops.serve_tower launches made under this plan (warm-up calls and the capture)."""
+
+    def __init__(self, max_rows: int, folds: dict, epsilon: float):
+        self.max_rows, self.folds, self.epsilon = int(max_rows), folds, float(epsilon)
+        self.tower_launches = 0
+
+
+class LazyTower:
+    """Consecutive `dense(relu) -> [dropout = identity] -> [batch_normalization(training=False)]` layers of a PREDICT graph under
+    the serving switch, not evaluated yet: whatever consumes the stack (the one-unit head, a concat) gets it from ONE launch
+    (ops.serve_tower, include/recalgo_serve.h) instead of one or two launches per layer.  LazyDense is the precedent.
+    A tower is a value: a layer or a fold added gives a NEW tower over the same input and the same first layers, so a model_fn
+    that keeps a hidden layer's output beside the next layer's holds two different stacks, each evaluated when used."""
+
+    def __init__(self, x: torch.Tensor, layers=(), plan=None):
+        self.x, self.plan = x, plan
+        self.layers = tuple(layers)           # ((kernel Variable, bias Variable | None, scale | None, shift | None), ..)
+        self._out = None
+
+    @property
+    def shape(self):
+        return (self.x.shape[0], int(self.layers[-1][0].data.shape[1]))
+
+    def dim(self):
+        return 2
+
+    @property
+    def is_cuda(self):
+        return True
+
+    def units(self):
+        return [int(ly[0].data.shape[1]) for ly in self.layers]
+
+    def with_layer(self, kernel: Variable, bias: Optional[Variable]) -> "LazyTower":
+        return LazyTower(self.x, self.layers + ((kernel, bias, None, None),), self.plan)
+
+    def with_fold(self, scale: torch.Tensor, shift: torch.Tensor) -> "LazyTower":
+        """the tower whose last layer's epilogue applies a BatchNorm's (scale, shift)"""
+        kernel, bias, _, _ = self.layers[-1]
+        return LazyTower(self.x, self.layers[:-1] + ((kernel, bias, scale, shift),), self.plan)
+
+    def materialize(self) -> torch.Tensor:
+        if self._out is None:
+            from . import ops
+            if SERVE_TOWER_PLAIN_STACKS or any(ly[2] is not None for ly in self.layers):
+                self._out = ops.serve_tower(self.x, [(k.data, None if b is None else b.data, sc, sh, True) for k, b, sc, sh in self.layers])
+                if self.plan is not None:
+                    self.plan.tower_launches += 1
+            else:                             # no BatchNorm to fold: the layers as `dense` runs them
+                out, store = self.x, current_store()
+                for kernel, bias, _, _ in self.layers:
+                    out = _DenseFn.apply(store.anchor, out, kernel, bias, True, 0.0, None, None, ReluSource(), None)
+                self._out = out
+        return self._out
+
+
+def _serving_tower(store, x, units: int):
+    """The LazyTower a relu layer of `units` columns over x extends (an empty one over a plain tensor), or None: the serving
+    switch is on (a PREDICT capture of ServingModel.compile), the bucket is small enough, and the kernel serves the stack
+    with this layer added."""
+    plan = getattr(store, "serving", None)
+    if plan is None or store.building or torch.is_grad_enabled():
+        return None
+    from . import ops
+    if isinstance(x, LazyTower):
+        if x._out is None:
+            ok = len(x.layers) < ops.SERVE_MAX_LAYERS and ops.serve_tower_supported(x.x.shape[1], x.units() + [units])
+            return x if ok else None
+        x = x._out                            # (already evaluated for another consumer: a new tower starts at its output)
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
+            and 1 <= x.shape[0] <= plan.max_rows and x.data_ptr() % 4 == 0 and ops.serve_tower_supported(x.shape[1], [units])):
+        return None
+    return LazyTower(x, (), plan)
 
 
 class LazyConcat:
@@ -350,7 +439,7 @@ class LazyLogit:
 
 def concat(values, axis: int = -1):
     """tf.concat along the last axis; lazy (see LazyConcat) when every value is a 2-D device tensor."""
-    values = list(values)
+    values = [t.materialize() if isinstance(t, LazyTower) else t for t in values]
     if axis in (-1, values[0].dim() - 1) and len(values) <= 4 and all(t.dim() == 2 and t.is_cuda for t in values):
         return LazyConcat(values)
     return torch.cat([_resolved(t) for t in values], dim=axis)
@@ -390,6 +479,11 @@ def dense(x, units, activation: Optional[str] = None,
         bias = store.get_variable("bias", (units,), zeros) if use_bias else None
     if activation not in (None, "relu"):
         raise ValueError(f"unsupported activation {activation}")
+    if getattr(store, "serving", None) is not None or isinstance(x, LazyTower):
+        tower = _serving_tower(store, x, units) if (activation == "relu" and input_l2 == 0.0 and not bn_stats and drop is None) else None
+        if tower is not None:                 # a PREDICT capture of ServingModel.compile: the layer joins the one-launch tower
+            return tower.with_layer(kernel, bias)
+        x = _resolved(x)
     parts = x.parts if isinstance(x, LazyConcat) else [x]
     if units == 1 and activation is None:
         from . import ops
@@ -713,8 +807,19 @@ class _BatchNormInferFn(Function):
         return g * scale, None, None
 
 
+BN_EPSILON = 1e-3        # tf.layers.batch_normalization's default, which every model_fn here leaves alone
+
+
+def fold_batch_norm(gamma: torch.Tensor, beta: torch.Tensor, moving_mean: torch.Tensor, moving_variance: torch.Tensor,
+                    epsilon: float = BN_EPSILON):
+    """BatchNorm inference as one multiply-add per column -> (scale, shift): y = x * scale + shift with
+    scale = gamma * rsqrt(moving_variance + epsilon), shift = beta - moving_mean * scale.  Pure: any dtype, any device."""
+    scale = torch.rsqrt(moving_variance + epsilon) * gamma
+    return scale, beta - moving_mean * scale
+
+
 def batch_normalization(x: torch.Tensor, training: bool = False,
-                        momentum: float = 0.99, epsilon: float = 1e-3,
+                        momentum: float = 0.99, epsilon: float = BN_EPSILON,
                         name: Optional[str] = None) -> torch.Tensor:
     """tf.layers.batch_normalization on (B, C)."""
     store = current_store()
@@ -725,12 +830,17 @@ def batch_normalization(x: torch.Tensor, training: bool = False,
         beta = store.get_variable("beta", (C,), zeros)
         mmean = store.get_variable("moving_mean", (C,), zeros, trainable=False)
         mvar = store.get_variable("moving_variance", (C,), ones, trainable=False)
+    if isinstance(x, LazyTower):
+        plan = getattr(store, "serving", None)
+        fold = plan.folds.get(gamma.name) if (plan is not None and not training and plan.epsilon == epsilon) else None
+        if fold is not None and x._out is None and x.layers[-1][2] is None:
+            return x.with_fold(*fold)         # the last layer's epilogue applies it
+        x = x.materialize()
     if training:
         # (batch moments left behind by the producing dense layer's epilogue, see dense(bn_stats=))
         pre = getattr(x, "_recalgo_bn_partials", None) if (x.dim() == 2 and x.is_contiguous()) else None
         return _attach_link(_BatchNormTrainFn.apply(store.anchor, x, gamma, beta, mmean, mvar, momentum, epsilon, pre))
-    inv = torch.rsqrt(mvar.data + epsilon) * gamma.data
-    return _BatchNormInferFn.apply(x, inv, beta.data - mmean.data * inv)
+    return _BatchNormInferFn.apply(x, *fold_batch_norm(gamma.data, beta.data, mmean.data, mvar.data, epsilon))
 
 
 class _DenseActBNFn(Function):

@@ -2783,3 +2783,54 @@ def dien_evolve(h: torch.Tensor, target: torch.Tensor, lengths: torch.Tensor, w_
         raise ValueError("dien_evolve: lengths are required")
     tensors = [None if isinstance(p, Variable) else p for p in params]
     return _DienEvolveFn.apply(anchor, h, target, _dien_lengths(lengths, B, "dien_evolve"), DIEN_MODES[mode], params, *tensors)
+
+
+# =============================================================================================
+# Serving (csrc/serve.hip, include/recalgo_serve.h): the inference tower of a small request, one launch
+# =============================================================================================
+_CS = _lib.SERVING_HEADERS["recalgo_serve.h"].constants       # the RECALGO_SERVE_* #defines of include/recalgo_serve.h
+SERVE_MAX_LAYERS, SERVE_MAX_IN, SERVE_MAX_UNITS = (_CS["RECALGO_SERVE_MAX_LAYERS"], _CS["RECALGO_SERVE_MAX_IN"],
+                                                   _CS["RECALGO_SERVE_MAX_UNITS"])
+
+
+def serve_tower_supported(K0: int, units) -> bool:
+    units = [int(u) for u in units]
+    return bool(_lib_().recalgo_serve_tower_supported(int(K0), (ctypes.c_int * max(len(units), 1))(*units), len(units)))
+
+
+def serve_tower(x: torch.Tensor, layers, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """include/recalgo_serve.h recalgo_serve_tower_fwd: h <- fmaf(relu?(h W + b), scale, shift) layer after layer, one launch.
+    x [B, K0] fp32 contiguous; layers: [(W [K, units], b [units] | None, scale [units] | None, shift [units] | None, relu)].
+    Inference only (no autograd node).  Shapes the kernel does not serve: ValueError — there is no fallback here; the caller
+    (nn.LazyTower) asks serve_tower_supported first and runs the per-layer kernels otherwise."""
+    if x.dim() != 2 or x.shape[0] == 0:
+        raise ValueError("serve_tower: x must be a non-empty [B, K0] matrix")
+    _chk(x, torch.float32, "serve_tower: x")
+    B, K = int(x.shape[0]), int(x.shape[1])
+    units, relu_bits = [], 0
+    for l, (w, b, scale, shift, relu) in enumerate(layers):
+        if w.dim() != 2 or int(w.shape[0]) != (units[-1] if units else K):
+            raise ValueError(f"serve_tower: layer {l}'s kernel is {tuple(w.shape)}, its input has {units[-1] if units else K} columns")
+        n = int(w.shape[1])
+        for t, name in ((w, "kernel"), (b, "bias"), (scale, "scale"), (shift, "shift")):
+            if t is not None:
+                _chk(t, torch.float32, f"serve_tower: layer {l} {name}")
+                if t.device != x.device or (t is not w and tuple(t.shape) != (n,)):
+                    raise ValueError(f"serve_tower: layer {l} {name} must be a [{n}] tensor on {x.device}")
+        if (scale is None) != (shift is None):
+            raise ValueError(f"serve_tower: layer {l} has a scale without a shift (or the reverse)")
+        units.append(n)
+        relu_bits |= int(bool(relu)) << l
+    if not serve_tower_supported(K, units):
+        raise ValueError(f"serve_tower: the kernel serves 1 .. {SERVE_MAX_LAYERS} layers, 1 <= K0 <= {SERVE_MAX_IN} and widths of "
+                         f"16 .. {SERVE_MAX_UNITS} that are multiples of 16; got K0={K} units={units}")
+    if out is None:
+        out = torch.empty(B, units[-1], device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (B, units[-1]) or out.device != x.device:
+        raise ValueError("serve_tower: out must be [B, units[-1]] on x's device")
+    else:
+        _chk(out, torch.float32, "serve_tower: out")
+    tables = [_ptr_array([ly[i] for ly in layers]) for i in range(4)]
+    _lib_().recalgo_serve_tower_fwd(_p(x), *tables, (ctypes.c_int * len(units))(*units), len(units), relu_bits, B, K, _p(out),
+                                    _stream(x))
+    return out

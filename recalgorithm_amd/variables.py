@@ -104,6 +104,9 @@ class VariableStore:
         self.opt_state = None            # device-side Adam step counter / lr_t (estimator.py)
         self._drop_calls = 0             # training-mode dropout calls of the current model_fn invocation (nn.dropout)
         self._rb_cache: Dict[tuple, torch.Tensor] = {}
+        # the serving switch, off by default: only export.ServingModel.compile sets it (an nn.ServingPlan), around the PREDICT
+        # model_fn calls it captures; nn.dense / nn.batch_normalization then collect the hidden stack into an nn.LazyTower
+        self.serving = None
 
     def row_base_tensor(self, arena: "EmbeddingArena", table_names: Sequence[str]) -> torch.Tensor:
         """int64 device tensor of the first arena row of each named table (cached)."""
