@@ -1,0 +1,146 @@
+// The streaming metrics of one EVAL batch in ONE launch (include/recalgo_metrics.h): per slot an AUC histogram
+//     hist[label > 0.5][#{j : p > th[j]}] += 1
+// or an accuracy count, plus the loss accumulator.  The host turns the histograms into tp / fp / fn / tn once, at the end of the
+// evaluation; per batch nothing comes back.  A latency chain, not a throughput kernel (4096 rows x 6 slots: 24 workgroups):
+//   * grid (row chunks, slots); a workgroup owns kRows consecutive rows of one slot;
+//   * AUC: the thresholds and a zeroed 2 x (N + 1) histogram in LDS, one binary search per row over the LDS copy (the predicate
+//     p > th[j] is monotone in j for an ascending array, false everywhere for a NaN), one 32-bit LDS atomic per row, then one
+//     64-bit global atomic per non-empty bin;
+//   * accuracy: a sum over each wave, one LDS atomic per wave, one global atomic per workgroup;
+//   * integer additions only, so the counts are the same bits in whatever order the workgroups arrive; plain vector stores and
+//     atomics from C++; the loss is added by one thread of one workgroup (launches on a stream are ordered).
+#include "common.h"
+#include "../../include/recalgo_metrics.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kRows = 1024;                               // rows of one workgroup
+constexpr int kMaxSlots = RECALGO_METRICS_MAX_SLOTS;
+constexpr int kMaxN = RECALGO_METRICS_MAX_THRESHOLDS;
+
+struct Slot {
+    const float* labels;
+    const float* predictions;
+    const float* thresholds;
+    int kind, N, label_stride, prediction_stride;
+    long long first_word;                                 // of the slot's counters in the state buffer
+};
+struct MetricsArgs {
+    Slot slot[kMaxSlots];
+    const float* loss;
+    unsigned long long* state;
+    int n;
+};
+
+__global__ __launch_bounds__(kThreads) void metrics_update_kernel(MetricsArgs P) {
+    __shared__ float th[kMaxN];
+    __shared__ unsigned hist[2 * (kMaxN + 1)];
+    const Slot& S = P.slot[blockIdx.y];
+    const int tid = (int)threadIdx.x;
+    const int r0 = (int)blockIdx.x * kRows;
+    const int rows = min(kRows, P.n - r0);                // (r0 < n: the grid is cdiv(n, kRows) chunks)
+    unsigned long long* const out = P.state + S.first_word;
+
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0 && P.loss != nullptr) {
+        double* const sum = reinterpret_cast<double*>(P.state);
+        *sum = *sum + (double)*P.loss;
+        P.state[1] = P.state[1] + 1ull;
+    }
+
+    if (S.kind == RECALGO_METRICS_ACCURACY) {
+        if (tid == 0) hist[0] = 0u;
+        __syncthreads();
+        unsigned mine = 0;
+        for (int k = tid; k < rows; k += kThreads) {
+            const size_t i = (size_t)(r0 + k);
+            mine += S.labels[i * S.label_stride] == S.predictions[i * S.prediction_stride] ? 1u : 0u;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+        if ((tid & 63) == 0 && mine) atomicAdd(&hist[0], mine);
+        __syncthreads();
+        if (tid == 0) {
+            if (hist[0]) atomicAdd(&out[0], (unsigned long long)hist[0]);
+            if (blockIdx.x == 0) atomicAdd(&out[1], (unsigned long long)P.n);
+        }
+        return;
+    }
+
+    const int N = S.N, bins = 2 * (N + 1);
+    for (int j = tid; j < N; j += kThreads) th[j] = S.thresholds[j];
+    for (int b = tid; b < bins; b += kThreads) hist[b] = 0u;
+    __syncthreads();
+    for (int k = tid; k < rows; k += kThreads) {
+        const size_t i = (size_t)(r0 + k);
+        const float p = S.predictions[i * S.prediction_stride];
+        const int y = S.labels[i * S.label_stride] > 0.5f ? 1 : 0;
+        int lo = 0, hi = N;                               // th[j] < p for j < lo, !(p > th[j]) for j >= hi
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (p > th[mid]) lo = mid + 1;
+            else hi = mid;
+        }
+        atomicAdd(&hist[y * (N + 1) + lo], 1u);
+    }
+    __syncthreads();
+    for (int b = tid; b < bins; b += kThreads) {
+        const unsigned c = hist[b];
+        if (c) atomicAdd(&out[b], (unsigned long long)c);
+    }
+}
+
+bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// words of a slot's counters; 0: a slot the kernel does not serve
+long long slot_words(const recalgo_metrics_slot_t& s) {
+    if (s.kind == RECALGO_METRICS_ACCURACY) return 2;
+    if (s.kind != RECALGO_METRICS_AUC || s.num_thresholds < 2 || s.num_thresholds > kMaxN) return 0;
+    return 2ll * (s.num_thresholds + 1);
+}
+
+}  // namespace
+
+RECALGO_EXPORT int recalgo_metrics_abi_version(void) { return RECALGO_METRICS_ABI_VERSION; }
+
+RECALGO_EXPORT int64_t recalgo_metrics_state_bytes(const recalgo_metrics_slot_t* slots, int n_slots) {
+    if (!slots || n_slots < 1 || n_slots > kMaxSlots) return 0;
+    long long words = 2;
+    for (int s = 0; s < n_slots; ++s) {
+        const long long w = slot_words(slots[s]);
+        if (!w) return 0;
+        words += w;
+    }
+    return (int64_t)(words * 8);
+}
+
+RECALGO_EXPORT int recalgo_metrics_update(const recalgo_metrics_slot_t* slots, int n_slots, const float* loss, int n, void* state,
+                                          recalgo_stream_t stream) {
+    RECALGO_REQUIRE(n >= 1 && slots && state && n_slots >= 1 && n_slots <= kMaxSlots);
+    RECALGO_REQUIRE(aligned_to(state, 8) && aligned_to(loss, 4));
+    MetricsArgs P = {};
+    long long word = 2;
+    for (int s = 0; s < n_slots; ++s) {
+        const recalgo_metrics_slot_t& in = slots[s];
+        const long long w = slot_words(in);
+        RECALGO_REQUIRE(w && in.labels && in.predictions && in.label_stride >= 1 && in.prediction_stride >= 1);
+        RECALGO_REQUIRE(aligned_to(in.labels, 4) && aligned_to(in.predictions, 4));
+        const bool auc = in.kind == RECALGO_METRICS_AUC;
+        RECALGO_REQUIRE(!auc || (in.thresholds && aligned_to(in.thresholds, 4)));
+        Slot& S = P.slot[s];
+        S.labels = in.labels;
+        S.predictions = in.predictions;
+        S.thresholds = auc ? in.thresholds : nullptr;
+        S.kind = in.kind;
+        S.N = auc ? in.num_thresholds : 0;
+        S.label_stride = in.label_stride;
+        S.prediction_stride = in.prediction_stride;
+        S.first_word = word;
+        word += w;
+    }
+    P.loss = loss;
+    P.state = static_cast<unsigned long long*>(state);
+    P.n = n;
+    hipLaunchKernelGGL(metrics_update_kernel, dim3(cdiv(n, kRows), n_slots), dim3(kThreads), 0, as_stream(stream), P);
+    RECALGO_RETURN_LAST();
+}

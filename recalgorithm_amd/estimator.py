@@ -37,9 +37,12 @@ class EstimatorSpec:
 
 class RunConfig:
     def __init__(self, model_dir=None, save_checkpoints_steps=None, device=None, seed=42,
-                 use_hip_graph=True, **_ignored):
+                 use_hip_graph=True, device_metrics=True, **_ignored):
         self.model_dir, self.save_checkpoints_steps = model_dir, save_checkpoints_steps
         self.device, self.seed, self.use_hip_graph = device, seed, use_hip_graph
+        # evaluate(): the metrics and the loss sum are accumulated on the device, one launch per batch and one copy at the end
+        # (EvalAccumulator); False: the host loop over Metric.update(), which also serves whatever the kernel does not
+        self.device_metrics = device_metrics
 
 
 class TrainSpec:
@@ -353,6 +356,95 @@ class metrics:  # namespace mirror of tf.metrics
     def auc(labels, predictions, num_thresholds=200):
         m = AUCMetric(labels, predictions, num_thresholds)
         return (m, m)
+
+
+class EvalAccumulator:
+    """The metrics of one evaluate() call, accumulated on the device: one recalgo_metrics_update launch per batch
+    (ops.metrics_update: an integer histogram per AUC metric, two counters per accuracy metric, the loss sum), nothing read back
+    until finish(), which makes ONE device-to-host copy of the state buffer and fills the first batch's Metric objects from the
+    counts; their own result() then produces the values, so the trapezoid and the epsilons stay in AUCMetric.
+
+    Exact: a prediction's bin is #{j : p > th[j]}, the very comparisons AUCMetric.update makes, so
+    tp[j] = sum over bin > j of hist[1][bin] is the count update() would have added up, as an integer (float64 holds it exactly
+    below 2**53); the loss sum is the same sequence of double additions as `loss_sum += float(spec.loss)`.
+
+    Serves AUCMetric and AccuracyMetric over fp32 tensors on the HIP device with a fp32 scalar loss there (`of` returns None for
+    any other spec: the caller keeps the host loop)."""
+
+    def __init__(self, spec: EstimatorSpec, device):
+        self.device = torch.device(device)
+        self.keys, self.metrics, self._th, self._layout = [], {}, {}, None
+        slots = self._slots(spec, first=True)
+        _, self.first, words = ops.metrics_slot_table(slots)
+        self.state = torch.zeros(words, dtype=torch.int64, device=spec.loss.device)
+
+    @classmethod
+    def of(cls, spec: EstimatorSpec, device) -> Optional["EvalAccumulator"]:
+        return cls(spec, device) if cls.serves(spec, device) else None
+
+    @staticmethod
+    def serves(spec: EstimatorSpec, device) -> bool:
+        def on_device(t):
+            return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() > 0
+                    and _same_device(t.device, device))
+        metric_ops = spec.eval_metric_ops or {}
+        if not (0 < len(metric_ops) <= ops.METRICS_MAX_SLOTS) or not on_device(spec.loss) or spec.loss.numel() != 1:
+            return False
+        n = None
+        for m, _ in metric_ops.values():
+            if type(m) not in (AUCMetric, AccuracyMetric) or not (on_device(m.labels) and on_device(m.predictions)):
+                return False
+            n = m.labels.numel() if n is None else n
+            if m.labels.numel() != n or m.predictions.numel() != n or ops.metrics_element_stride(m.labels) is None \
+                    or ops.metrics_element_stride(m.predictions) is None:
+                return False
+            if type(m) is AUCMetric and not (2 <= m.n <= ops.METRICS_MAX_THRESHOLDS and m.th.numel() == m.n):
+                return False
+        return True
+
+    def _slots(self, spec: EstimatorSpec, first: bool = False):
+        metric_ops = spec.eval_metric_ops or {}
+        layout = [(k, type(m), getattr(m, "n", None)) for k, (m, _) in metric_ops.items()]
+        if first:
+            self._layout = layout
+            for k, (m, _) in metric_ops.items():
+                self.keys.append(k)
+                self.metrics[k] = m
+                if type(m) is AUCMetric:       # the thresholds as the metric states them, on the device once
+                    self._th[k] = m.th.to(device=m.predictions.device, dtype=torch.float32).contiguous()
+        elif layout != self._layout or not self.serves(spec, self.device):
+            raise ValueError("evaluate(device_metrics=True): a batch's eval_metric_ops differ from the first batch's "
+                             f"({[k for k, _, _ in layout]} against {self.keys}), or are not fp32 tensors on {self.device}")
+        return [("auc", m.labels, m.predictions, self._th[k]) if type(m) is AUCMetric else ("accuracy", m.labels, m.predictions)
+                for k, (m, _) in metric_ops.items()]
+
+    def add(self, spec: EstimatorSpec) -> None:
+        """One launch: the batch's metrics and loss into the state buffer.  Capturable (no read-back, no allocation)."""
+        ops.metrics_update(self._slots(spec), spec.loss.detach(), self.state)
+
+    @staticmethod
+    def fill_auc(m: "AUCMetric", hist: torch.Tensor) -> None:
+        """hist [2, N + 1] integer counts of (label > 0.5, #{j : p > th[j]}) -> m.tp / fp / fn / tn, as update() accumulates them"""
+        hist = hist.to(torch.int64).reshape(2, m.n + 1)
+        above = hist.flip(1).cumsum(1).flip(1)[:, 1:]             # above[y][j] = sum over bin > j of hist[y][bin]
+        total = hist.sum(1, keepdim=True)
+        m.fp, m.tp = above.to(torch.float64).unbind(0)
+        m.tn, m.fn = (total - above).to(torch.float64).unbind(0)
+
+    @staticmethod
+    def fill_accuracy(m: "AccuracyMetric", correct: int, total: int) -> None:
+        m.correct, m.total = float(correct), float(total)
+
+    def finish(self):
+        """-> ({key: filled Metric}, loss sum, batches) after ONE device-to-host copy"""
+        host = self.state.cpu()
+        for k, first in zip(self.keys, self.first):
+            m = self.metrics[k]
+            if type(m) is AUCMetric:
+                self.fill_auc(m, host[first:first + 2 * (m.n + 1)])
+            else:
+                self.fill_accuracy(m, int(host[first]), int(host[first + 1]))
+        return self.metrics, float(host[:1].view(torch.float64)), int(host[1])
 
 
 # --------------------------------------------------------------------------------------------
@@ -876,9 +968,72 @@ class Estimator:
 
     @torch.no_grad()
     def evaluate(self, input_fn, steps=None) -> Dict[str, float]:
+        """RunConfig(device_metrics=True) on a HIP device: metrics and loss are accumulated by one launch per batch and read
+        once at the end (_evaluate_on_device); otherwise, and for a spec whose metrics that launch does not serve, the host
+        loop over Metric.update()."""
+        if getattr(self.config, "device_metrics", False) and self.device.type == "cuda":
+            return self._evaluate_on_device(iter(input_fn()), steps)
+        return self._evaluate_on_host(input_fn(), steps)
+
+    def _evaluate_on_device(self, batches, steps) -> Dict[str, float]:
+        """No host synchronisation inside the loop.  With config.use_hip_graph the EVAL step — model_fn under no_grad plus the
+        metrics launch, one stream — is captured on the third fixed-shape batch and replayed from then on (GraphedTrainStep's
+        static inputs and one-copy load); a batch of another shape (the last partial one) and every ragged batch run the same
+        step eagerly into the same accumulator.  The graph lives for this call only."""
+        acc, graphed, n = None, None, 0
+
+        def step(features, labels):
+            spec = self._call_model_fn(features, labels, ModeKeys.EVAL)
+            acc.add(spec)
+            return spec.loss
+
+        for i, (features, labels) in enumerate(batches):
+            if steps is not None and i >= steps:
+                break
+            pb = self._packed_host_batch(features, labels) if graphed is not None else None
+            if pb is not None:
+                host = (features, labels)
+                try:
+                    self.feed_step(graphed, features, labels, pb)     # (host batch -> the graph's input span, one copy)
+                    n += 1
+                    continue
+                except BatchShapeMismatch:       # last partial batch: eager step
+                    features, labels = self._to_device(*host)
+            else:
+                features, labels = self._to_device(features, labels)
+                self._build(features, labels, ModeKeys.EVAL)
+            if acc is None:
+                spec = self._call_model_fn(features, labels, ModeKeys.EVAL)
+                acc = EvalAccumulator.of(spec, self.device)
+                if acc is None:                  # metrics the launch does not serve: the host loop, from this batch on
+                    import itertools
+                    return self._evaluate_on_host(itertools.chain([(features, labels)], batches), None if steps is None else steps - i)
+                acc.add(spec)
+            elif pb is None and self.config.use_hip_graph and _static_batch(features) and n >= 2:
+                try:
+                    if graphed is None:
+                        graphed = GraphedTrainStep(step, features, labels, warmup=0)
+                        graphed()
+                    else:
+                        graphed(features, labels)
+                except BatchShapeMismatch:
+                    step(features, labels)
+            else:
+                step(features, labels)
+            n += 1
+        del graphed
+        if acc is None:
+            return self._evaluate_on_host((), steps)
+        agg, loss_sum, nb = acc.finish()
+        out = {k: m.result() for k, m in agg.items()}
+        out["loss"] = loss_sum / max(nb, 1)
+        out["global_step"] = self.global_step
+        return out
+
+    def _evaluate_on_host(self, batches, steps) -> Dict[str, float]:
         agg: Dict[str, Metric] = {}
         loss_sum, nb = 0.0, 0
-        for i, (features, labels) in enumerate(input_fn()):
+        for i, (features, labels) in enumerate(batches):
             if steps is not None and i >= steps:
                 break
             features, labels = self._to_device(features, labels)

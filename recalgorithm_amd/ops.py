@@ -2834,3 +2834,66 @@ def serve_tower(x: torch.Tensor, layers, out: Optional[torch.Tensor] = None) -> 
     _lib_().recalgo_serve_tower_fwd(_p(x), *tables, (ctypes.c_int * len(units))(*units), len(units), relu_bits, B, K, _p(out),
                                     _stream(x))
     return out
+
+
+# =============================================================================================
+# Evaluation (csrc/metrics.hip, include/recalgo_metrics.h): every streaming metric of an EVAL batch and the loss sum, one launch
+# =============================================================================================
+_MH = _lib.SERVING_HEADERS["recalgo_metrics.h"]
+_CM = _MH.constants                                            # the RECALGO_METRICS_* #defines of include/recalgo_metrics.h
+_MetricsSlot = _MH.structs["recalgo_metrics_slot_t"]
+METRICS_MAX_SLOTS, METRICS_MAX_THRESHOLDS = _CM["RECALGO_METRICS_MAX_SLOTS"], _CM["RECALGO_METRICS_MAX_THRESHOLDS"]
+METRICS_KINDS = {"auc": _CM["RECALGO_METRICS_AUC"], "accuracy": _CM["RECALGO_METRICS_ACCURACY"]}
+
+
+def metrics_element_stride(t: torch.Tensor) -> Optional[int]:
+    """The element stride at which the kernel walks t's numel() values in order, None when there is no single one: a contiguous
+    tensor (1), or one whose values lie along one dimension (a [B, 1] column view of a [B, T] matrix: T)."""
+    long_dims = [int(st) for d, st in zip(t.shape, t.stride()) if d > 1]
+    if not long_dims:
+        return 1
+    if len(long_dims) == 1:
+        return long_dims[0] if long_dims[0] >= 1 else None
+    return 1 if t.is_contiguous() else None
+
+
+def metrics_slot_table(slots):
+    """slots: [("auc", labels, predictions, thresholds) | ("accuracy", labels, predictions)] -> (the ctypes table of
+    recalgo_metrics_slot_t, word offset of each slot's counters in the state buffer, the buffer's size in 64-bit words)."""
+    table = (_MetricsSlot * max(len(slots), 1))()
+    first, word = [], 2
+    for i, (kind, labels, predictions, *th) in enumerate(slots):
+        s = table[i]
+        s.kind = METRICS_KINDS[kind]
+        s.labels, s.predictions = labels.data_ptr(), predictions.data_ptr()
+        s.label_stride, s.prediction_stride = metrics_element_stride(labels) or 0, metrics_element_stride(predictions) or 0
+        if kind == "auc":
+            s.thresholds, s.num_thresholds = th[0].data_ptr(), int(th[0].numel())
+        first.append(word)
+        word += 2 * (s.num_thresholds + 1) if kind == "auc" else 2
+    nbytes = int(_lib_().recalgo_metrics_state_bytes(table, len(slots)))
+    if nbytes != 8 * word:
+        raise ValueError(f"metrics: 1 .. {METRICS_MAX_SLOTS} slots, an AUC slot with 2 .. {METRICS_MAX_THRESHOLDS} thresholds")
+    return table, first, word
+
+
+def metrics_update(slots, loss: Optional[torch.Tensor], state: torch.Tensor) -> None:
+    """include/recalgo_metrics.h recalgo_metrics_update: one launch adds a batch to `state` (int64 words, laid out as
+    metrics_slot_table says, zeroed by the caller before the first batch) — per AUC slot hist[labels > 0.5][#{j : p > th[j]}],
+    per accuracy slot (labels == predictions).sum() and the row count, and `loss` (fp32 scalar on the device, or None) into the
+    double loss sum with one more batch counted.  Every tensor is fp32 on state's device; labels and predictions of a slot have the
+    same number of elements, the same in every slot, at one element stride each (metrics_element_stride)."""
+    n = int(slots[0][1].numel()) if slots else 0
+    for kind, labels, predictions, *th in slots:
+        for t, name in ((labels, "labels"), (predictions, "predictions")) + (((th[0], "thresholds"),) if kind == "auc" else ()):
+            if t.dtype != torch.float32 or t.device != state.device:
+                raise TypeError(f"metrics_update: {kind} {name} must be float32 on {state.device}")
+        if labels.numel() != n or predictions.numel() != n or metrics_element_stride(labels) is None \
+                or metrics_element_stride(predictions) is None or (kind == "auc" and not th[0].is_contiguous()):
+            raise ValueError(f"metrics_update: {kind} labels and predictions must hold the batch's {n} values at one element stride")
+    table, _, words = metrics_slot_table(slots)
+    if state.dtype != torch.int64 or not state.is_contiguous() or state.numel() != words:
+        raise ValueError(f"metrics_update: state must be a contiguous int64 tensor of {words} words")
+    if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != state.device):
+        raise TypeError(f"metrics_update: loss must be one float32 value on {state.device}")
+    _lib_().recalgo_metrics_update(table, len(slots), _p(loss), n, _p(state), _stream(state))
