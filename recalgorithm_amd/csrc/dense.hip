@@ -38,6 +38,7 @@
 #include "act.h"
 #include "tile_v2.h"
 #include "dropout.h"
+#include "slab_sum.h"
 
 namespace {
 
@@ -742,16 +743,8 @@ __global__ __launch_bounds__(kThreads) void dense_bwd_rider_kernel(DgradArgs D, 
 // (Tried instead: letting the last-arriving workgroup of each tile do the sum inside the wgrad kernel, with the
 // agent-scope release / ticket / acquire hand-off — correct, but the per-workgroup L2 write-back made the
 // [4096 x 256 x 128] wgrad 56 us instead of 18 + 7; the partials of one launch stay cheap only across a kernel boundary.)
-constexpr int kMaxSplitJobs = 32;
-struct SplitJob {
-    const float* partials;
-    float* out0;
-    float* out1;
-    unsigned long long slab, n0, n;
-    int S, vec;                // vec: 1 float4 per thread, 0 one float per thread, 2 "tall" (S >> n): 16 columns x 16 row
-                               //      groups per workgroup (a thread walking hundreds of partial rows alone is latency bound)
-    unsigned first_block;      // blocks [first_block, next job's first_block) belong to this job
-};
+using recalgo_slabs::kMaxSplitJobs;
+using recalgo_slabs::SplitJob;
 struct SplitJobs {
     SplitJob job[kMaxSplitJobs];
     int n_jobs;
@@ -768,56 +761,21 @@ __global__ __launch_bounds__(256) void dense_sum_slabs_kernel(SplitJobs J) {
         if (k < J.n_jobs && blockIdx.x >= J.job[k].first_block) j = k;
     const SplitJob& jb = J.job[j];
     const size_t t = (size_t)(blockIdx.x - jb.first_block) * 256 + threadIdx.x;
+    // (the three summation bodies: slab_sum.h, shared with the optimizer's sum-and-step launch)
     if (jb.vec == 2) {
         __shared__ float sh[16][17];
-        const unsigned cl = threadIdx.x & 15, rg = threadIdx.x >> 4;
-        const size_t c = (size_t)(blockIdx.x - jb.first_block) * 16 + cl;
-        float acc = 0.f;
-        if (c < jb.n) {
-            // the partial rows of a column are independent loads: eight in flight per thread, added in row order (a loop of
-            // load -> wait -> add over the 512 partial rows of the loss tail was most of this launch: ~13 us in the step)
-            const float* col = jb.partials + c;
-            int r = rg;
-            for (; r + 16 * 7 < jb.S; r += 16 * 8) {
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = col[(size_t)(r + 16 * u) * jb.slab];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) acc += v[u];
-            }
-            for (; r < jb.S; r += 16) acc += col[(size_t)r * jb.slab];
-        }
-        sh[rg][cl] = acc;
-        __syncthreads();
-        if (rg == 0 && c < jb.n) {
-            float tt = 0.f;
-#pragma unroll
-            for (int g = 0; g < 16; ++g) tt += sh[g][cl];
-            jb.out0[c] = tt;
-        }
+        const size_t tile = blockIdx.x - jb.first_block, c = tile * 16 + (threadIdx.x & 15);
+        const float tt = recalgo_slabs::sum_tall(jb, tile, sh);
+        if ((threadIdx.x >> 4) == 0 && c < jb.n) jb.out0[c] = tt;
         return;
     }
     if (jb.vec) {
         const size_t i = t * 4;
         if (i >= jb.n) return;
-        // the slab loads are independent: four in flight per thread, added in slab order (the sum's order is fixed)
-        const float* base = jb.partials + i;
-        float4 acc = *reinterpret_cast<const float4*>(base);
-        int s = 1;
-        for (; s + 4 <= jb.S; s += 4) {
-            const float4 a0 = *reinterpret_cast<const float4*>(base + (size_t)s * jb.slab);
-            const float4 a1 = *reinterpret_cast<const float4*>(base + (size_t)(s + 1) * jb.slab);
-            const float4 a2 = *reinterpret_cast<const float4*>(base + (size_t)(s + 2) * jb.slab);
-            const float4 a3 = *reinterpret_cast<const float4*>(base + (size_t)(s + 3) * jb.slab);
-            acc = f4_add(f4_add(f4_add(f4_add(acc, a0), a1), a2), a3);
-        }
-        for (; s < jb.S; ++s) acc = f4_add(acc, *reinterpret_cast<const float4*>(base + (size_t)s * jb.slab));
-        *reinterpret_cast<float4*>(i < jb.n0 ? jb.out0 + i : jb.out1 + (i - jb.n0)) = acc;
+        *reinterpret_cast<float4*>(recalgo_slabs::job_target(jb, i)) = recalgo_slabs::sum_slabs4(jb, i);
     } else {
         if (t >= jb.n) return;
-        float acc = jb.partials[t];
-        for (int s = 1; s < jb.S; ++s) acc += jb.partials[(size_t)s * jb.slab + t];
-        *(t < jb.n0 ? jb.out0 + t : jb.out1 + (t - jb.n0)) = acc;
+        *recalgo_slabs::job_target(jb, t) = recalgo_slabs::sum_slabs1(jb, t);
     }
 }
 
@@ -953,6 +911,16 @@ static SplitJob make_split_job(const float* ws, int S, int K, int N, float* dw, 
     jb.vec = (jb.n0 % 4 == 0 && N % 4 == 0 && aligned16(dw) && (dbias == nullptr || aligned16(dbias)) && aligned16(ws)) ? 1 : 0;
     jb.first_block = first_block;
     *blocks = (unsigned)cdiv((int64_t)(jb.vec ? (jb.n + 3) / 4 : jb.n), 256);
+    return jb;
+}
+
+static SplitJob make_colsum_job(const recalgo_colsum_t& c, unsigned first_block, unsigned* blocks) {
+    SplitJob jb;
+    jb.partials = c.partials; jb.out0 = c.out; jb.out1 = nullptr; jb.S = c.rows;
+    jb.slab = (unsigned long long)c.row_stride; jb.n0 = jb.n = (unsigned long long)c.n;
+    jb.vec = 2;
+    jb.first_block = first_block;
+    *blocks = (unsigned)cdiv((int64_t)jb.n, 16);
     return jb;
 }
 
@@ -1145,13 +1113,9 @@ RECALGO_EXPORT int recalgo_dense_bwd_weights_reduce(const recalgo_dense_split_t*
     for (int i = 0; i < n_sums; ++i) {                       // plain column sums of partial rows (the loss tail's)
         const recalgo_colsum_t& c = sums[i];
         RECALGO_REQUIRE(c.partials != nullptr && c.out != nullptr && c.rows >= 1 && c.n >= 1 && c.row_stride >= c.n);
-        SplitJob jb;
-        jb.partials = c.partials; jb.out0 = c.out; jb.out1 = nullptr; jb.S = c.rows;
-        jb.slab = (unsigned long long)c.row_stride; jb.n0 = jb.n = (unsigned long long)c.n;
-        jb.vec = 2;
-        jb.first_block = blocks;
-        blocks += (unsigned)cdiv((int64_t)jb.n, 16);
-        J.job[J.n_jobs++] = jb;
+        unsigned nb = 0;
+        J.job[J.n_jobs++] = make_colsum_job(c, blocks, &nb);
+        blocks += nb;
         if (J.n_jobs == kMaxSplitJobs) {
             int rc = launch_split_jobs(J, blocks, st);
             if (rc) return rc;
@@ -1178,4 +1142,34 @@ RECALGO_EXPORT int recalgo_dense_bwd_weights_reduce(const recalgo_dense_split_t*
         }
     }
     return launch_split_jobs(J, blocks, st);
+}
+
+// the same jobs in the same block layout for a launch that hosts them (slab_sum.h; tail.hip's sum-and-step launch)
+int recalgo_build_split_jobs(const recalgo_dense_split_t* jobs, int n_jobs, const recalgo_colsum_t* sums, int n_sums,
+                             SplitJob* out, int cap, int* n_out, unsigned* blocks_out) {
+    RECALGO_REQUIRE(n_jobs >= 0 && (n_jobs == 0 || jobs != nullptr) && n_sums >= 0 && (n_sums == 0 || sums != nullptr));
+    int n = 0;
+    unsigned blocks = 0;
+    for (int i = 0; i < n_sums; ++i) {
+        const recalgo_colsum_t& c = sums[i];
+        RECALGO_REQUIRE(c.partials != nullptr && c.out != nullptr && c.rows >= 1 && c.n >= 1 && c.row_stride >= c.n);
+        if (n == cap) return -1;
+        unsigned nb = 0;
+        out[n++] = make_colsum_job(c, blocks, &nb);
+        blocks += nb;
+    }
+    for (int i = 0; i < n_jobs; ++i) {
+        const recalgo_dense_split_t& d = jobs[i];
+        RECALGO_REQUIRE(d.M > 0 && d.K > 0 && d.N > 0 && d.dw != nullptr);
+        const int S = wgrad_splits(d.M, d.K, d.N);
+        if (S <= 1) continue;                               // nothing was deferred for this shape: dw holds the gradient
+        RECALGO_REQUIRE(d.workspace != nullptr);
+        if (n == cap) return -1;
+        unsigned nb = 0;
+        out[n++] = make_split_job(static_cast<const float*>(d.workspace), S, d.K, d.N, d.dw, d.dbias, blocks, &nb);
+        blocks += nb;
+    }
+    *n_out = n;
+    *blocks_out = blocks;
+    return 0;
 }

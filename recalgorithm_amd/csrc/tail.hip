@@ -1,7 +1,13 @@
 // Loss tail (a14), TF1 Adam (a15), DIN activations (a12) — small streaming kernels, gfx950.
+#include <algorithm>
+#include <utility>
+#include <vector>
+
 #include "deferred.h"
 #include "act.h"
 #include "plan_scan.h"
+#include "slab_sum.h"
+#include "../../include/recalgo_sumstep.h"
 #include "sigmoid_ce.h"
 
 namespace {
@@ -386,105 +392,96 @@ struct AdamStepArgs {
     unsigned scan_first;      // blocks [scan_first, scan_first + n_scans) are those workgroups
 };
 
-__global__ __launch_bounds__(256) void adam_tf1_step_kernel(AdamStepArgs A) {
-    __shared__ float s_lr_t;
-    if (blockIdx.x >= A.scan_first) {                          // (workgroup-uniform)
-        __shared__ unsigned scan_sh[8];
-        recalgo_plan::scan_block(A.scan[blockIdx.x - A.scan_first], scan_sh);
-        return;
+// float4 words [lo4, hi4) of the flat dense buffer, by workgroup `blk` of `nblk`
+__device__ __forceinline__ void adam_dense_words(const AdamStepArgs& A, long long lo4, long long hi4, unsigned blk, unsigned nblk,
+                                                 float lr_t, float b1, float b2, float eps) {
+    const long long stride = (long long)nblk * 256;
+    float4* p4 = reinterpret_cast<float4*>(A.p);
+    float4* g4 = reinterpret_cast<float4*>(A.g);
+    float4* m4 = reinterpret_cast<float4*>(A.m);
+    float4* v4 = reinterpret_cast<float4*>(A.v);
+    for (long long i = lo4 + (long long)blk * 256 + threadIdx.x; i < hi4; i += stride) {
+        float4 gg = g4[i], mm = m4[i], vv = v4[i];
+        const bool inert = gg.x == 0.f && gg.y == 0.f && gg.z == 0.f && gg.w == 0.f && mm.x == 0.f && mm.y == 0.f &&
+                           mm.z == 0.f && mm.w == 0.f && vv.x == 0.f && vv.y == 0.f && vv.z == 0.f && vv.w == 0.f;
+        if (inert) continue;                       // exact: the update of an all-zero word is the identity
+        float4 pp = p4[i];
+        adam1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps);
+        adam1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps);
+        adam1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps);
+        adam1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps);
+        p4[i] = pp; m4[i] = mm; v4[i] = vv;
+        if (A.zero_grad && (gg.x != 0.f || gg.y != 0.f || gg.z != 0.f || gg.w != 0.f)) g4[i] = f4_zero();
     }
-    const long long t = A.step[0] + (A.advance ? 1 : 0);
-    if (threadIdx.x == 0) {
-        const double td = (double)t;
-        s_lr_t = (float)((double)A.lr * sqrt(1.0 - pow((double)A.b2, td)) / (1.0 - pow((double)A.b1, td)));
-    }
-    __syncthreads();
-    const float lr_t = s_lr_t, b1 = A.b1, b2 = A.b2, eps = A.eps;
-    if (blockIdx.x < A.dense_blocks) {
-        const long long n4 = A.n / 4;
-        const long long stride = (long long)A.dense_blocks * 256;
-        float4* p4 = reinterpret_cast<float4*>(A.p);
-        float4* g4 = reinterpret_cast<float4*>(A.g);
-        float4* m4 = reinterpret_cast<float4*>(A.m);
-        float4* v4 = reinterpret_cast<float4*>(A.v);
-        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-            float4 gg = g4[i], mm = m4[i], vv = v4[i];
-            const bool inert = gg.x == 0.f && gg.y == 0.f && gg.z == 0.f && gg.w == 0.f && mm.x == 0.f && mm.y == 0.f &&
-                               mm.z == 0.f && mm.w == 0.f && vv.x == 0.f && vv.y == 0.f && vv.z == 0.f && vv.w == 0.f;
-            if (inert) continue;                       // exact: the update of an all-zero word is the identity
-            float4 pp = p4[i];
+}
+// one element outside the float4 words (the n % 4 tail)
+__device__ __forceinline__ void adam_dense_element(const AdamStepArgs& A, long long i, float lr_t, float b1, float b2, float eps) {
+    float pp = A.p[i], gg = A.g[i], mm = A.m[i], vv = A.v[i];
+    adam1(pp, gg, mm, vv, lr_t, b1, b2, eps);
+    A.p[i] = pp; A.m[i] = mm; A.v[i] = vv;
+    if (A.zero_grad) A.g[i] = 0.f;
+}
+
+// the live rows of the arena that workgroup `bid` of the launch belongs to (A.n_arenas > 0, bid >= A.dense_blocks)
+__device__ __forceinline__ void adam_arena_block(const AdamStepArgs& A, unsigned bid, float lr_t, float b1, float b2, float eps) {
+    int a = 0;
+#pragma unroll
+    for (int k = 1; k < kAdamMaxArenas; ++k)
+        if (k < A.n_arenas && bid >= A.ar[k].first_block) a = k;
+    AdamArena R = A.ar[0];                       // select by value (a dynamic index into the kernel arguments
+#pragma unroll                                       // would go through scratch)
+    for (int k = 1; k < kAdamMaxArenas; ++k)
+        if (a == k) R = A.ar[k];
+    const unsigned blk = bid - R.first_block;
+    const long long stride = (long long)R.n_blocks * 256;
+    const int K = R.K;
+    if ((K & 3) == 0) {
+        const int K4 = K >> 2;
+        const long long total4 = (long long)R.count[0] * K4;
+        float4* p4 = reinterpret_cast<float4*>(R.p);
+        float4* g4 = reinterpret_cast<float4*>(R.g);
+        float4* m4 = reinterpret_cast<float4*>(R.m);
+        float4* v4 = reinterpret_cast<float4*>(R.v);
+        const int sh = R.k4_shift;
+        for (long long tt = (long long)blk * 256 + threadIdx.x; tt < total4; tt += stride) {
+            const long long r = sh >= 0 ? tt >> sh : tt / K4;
+            const long long i = (long long)R.list[r] * K4 + (tt - r * K4);
+            float4 gg = g4[i];
+            const bool nz = gg.x != 0.f || gg.y != 0.f || gg.z != 0.f || gg.w != 0.f;
+            if (R.lazy) {
+                // tf.contrib.opt.LazyAdamOptimizer (the reference's DIEN, dien.py:328): only the rows of this step's
+                // IndexedSlices move — here: rows with a non-zero gradient (the K4 lanes of a row vote)
+                int any = nz;
+                if (sh > 0)
+                    for (int o = 1; o < K4; o <<= 1) any |= __shfl_xor(any, o, 64);
+                if (!any) continue;
+            }
+            float4 mm = m4[i], vv = v4[i], pp = p4[i];
             adam1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps);
             adam1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps);
             adam1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps);
             adam1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps);
             p4[i] = pp; m4[i] = mm; v4[i] = vv;
-            if (A.zero_grad && (gg.x != 0.f || gg.y != 0.f || gg.z != 0.f || gg.w != 0.f)) g4[i] = f4_zero();
+            if (A.zero_grad && nz) g4[i] = f4_zero();
         }
-        if (blockIdx.x == 0 && threadIdx.x < (unsigned)(A.n - n4 * 4)) {
-            const long long i = n4 * 4 + threadIdx.x;
-            float pp = A.p[i], gg = A.g[i], mm = A.m[i], vv = A.v[i];
+    } else {
+        const long long total = (long long)R.count[0] * K;
+        for (long long tt = (long long)blk * 256 + threadIdx.x; tt < total; tt += stride) {
+            const long long r = tt / K;
+            const long long i = (long long)R.list[r] * K + (tt - r * K);
+            float gg = R.g[i];
+            const bool nz = gg != 0.f;
+            if (R.lazy && !nz) continue;                 // (element-wise vote for widths that are not 4 * 2^n)
+            float mm = R.m[i], vv = R.v[i], pp = R.p[i];
             adam1(pp, gg, mm, vv, lr_t, b1, b2, eps);
-            A.p[i] = pp; A.m[i] = mm; A.v[i] = vv;
-            if (A.zero_grad) A.g[i] = 0.f;
-        }
-    } else if (A.n_arenas > 0) {                     // (n == 0 and no arena: the one workgroup only takes its ticket —
-        int a = 0;                                   //  ar[0] is then a padding descriptor with no count to read)
-#pragma unroll
-        for (int k = 1; k < kAdamMaxArenas; ++k)
-            if (k < A.n_arenas && blockIdx.x >= A.ar[k].first_block) a = k;
-        AdamArena R = A.ar[0];                       // select by value (a dynamic index into the kernel arguments
-#pragma unroll                                       // would go through scratch)
-        for (int k = 1; k < kAdamMaxArenas; ++k)
-            if (a == k) R = A.ar[k];
-        const unsigned blk = blockIdx.x - R.first_block;
-        const long long stride = (long long)R.n_blocks * 256;
-        const int K = R.K;
-        if ((K & 3) == 0) {
-            const int K4 = K >> 2;
-            const long long total4 = (long long)R.count[0] * K4;
-            float4* p4 = reinterpret_cast<float4*>(R.p);
-            float4* g4 = reinterpret_cast<float4*>(R.g);
-            float4* m4 = reinterpret_cast<float4*>(R.m);
-            float4* v4 = reinterpret_cast<float4*>(R.v);
-            const int sh = R.k4_shift;
-            for (long long tt = (long long)blk * 256 + threadIdx.x; tt < total4; tt += stride) {
-                const long long r = sh >= 0 ? tt >> sh : tt / K4;
-                const long long i = (long long)R.list[r] * K4 + (tt - r * K4);
-                float4 gg = g4[i];
-                const bool nz = gg.x != 0.f || gg.y != 0.f || gg.z != 0.f || gg.w != 0.f;
-                if (R.lazy) {
-                    // tf.contrib.opt.LazyAdamOptimizer (the reference's DIEN, dien.py:328): only the rows of this step's
-                    // IndexedSlices move — here: rows with a non-zero gradient (the K4 lanes of a row vote)
-                    int any = nz;
-                    if (sh > 0)
-                        for (int o = 1; o < K4; o <<= 1) any |= __shfl_xor(any, o, 64);
-                    if (!any) continue;
-                }
-                float4 mm = m4[i], vv = v4[i], pp = p4[i];
-                adam1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps);
-                adam1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps);
-                adam1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps);
-                adam1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps);
-                p4[i] = pp; m4[i] = mm; v4[i] = vv;
-                if (A.zero_grad && nz) g4[i] = f4_zero();
-            }
-        } else {
-            const long long total = (long long)R.count[0] * K;
-            for (long long tt = (long long)blk * 256 + threadIdx.x; tt < total; tt += stride) {
-                const long long r = tt / K;
-                const long long i = (long long)R.list[r] * K + (tt - r * K);
-                float gg = R.g[i];
-                const bool nz = gg != 0.f;
-                if (R.lazy && !nz) continue;                 // (element-wise vote for widths that are not 4 * 2^n)
-                float mm = R.m[i], vv = R.v[i], pp = R.p[i];
-                adam1(pp, gg, mm, vv, lr_t, b1, b2, eps);
-                R.p[i] = pp; R.m[i] = mm; R.v[i] = vv;
-                if (A.zero_grad && nz) R.g[i] = 0.f;
-            }
+            R.p[i] = pp; R.m[i] = mm; R.v[i] = vv;
+            if (A.zero_grad && nz) R.g[i] = 0.f;
         }
     }
-    if (!A.advance) return;
-    // the last workgroup to arrive publishes the new step count
+}
+
+// the last workgroup to arrive publishes the new step count (every workgroup in front of scan_first, once, at its end)
+__device__ __forceinline__ void adam_publish_step(const AdamStepArgs& A, long long t) {
     __syncthreads();
     if (threadIdx.x == 0) {
         const int arrived = __hip_atomic_fetch_add(A.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -493,6 +490,198 @@ __global__ __launch_bounds__(256) void adam_tf1_step_kernel(AdamStepArgs A) {
             A.step[0] = t;
         }
     }
+}
+
+__device__ __forceinline__ float adam_lr_t_value(const AdamStepArgs& A, long long t) {
+    const double td = (double)t;
+    return (float)((double)A.lr * sqrt(1.0 - pow((double)A.b2, td)) / (1.0 - pow((double)A.b1, td)));
+}
+// lr_t of step t, derived by every workgroup itself (two pow and a sqrt in double); s_lr_t: one float of LDS
+__device__ __forceinline__ float adam_lr_t(const AdamStepArgs& A, long long t, float* s_lr_t) {
+    if (threadIdx.x == 0) *s_lr_t = adam_lr_t_value(A, t);
+    __syncthreads();
+    return *s_lr_t;
+}
+
+__global__ __launch_bounds__(256) void adam_tf1_step_kernel(AdamStepArgs A) {
+    __shared__ float s_lr_t;
+    if (blockIdx.x >= A.scan_first) {                          // (workgroup-uniform)
+        __shared__ unsigned scan_sh[8];
+        recalgo_plan::scan_block(A.scan[blockIdx.x - A.scan_first], scan_sh);
+        return;
+    }
+    const long long t = A.step[0] + (A.advance ? 1 : 0);
+    const float lr_t = adam_lr_t(A, t, &s_lr_t), b1 = A.b1, b2 = A.b2, eps = A.eps;
+    if (blockIdx.x < A.dense_blocks) {
+        const long long n4 = A.n / 4;
+        adam_dense_words(A, 0, n4, blockIdx.x, A.dense_blocks, lr_t, b1, b2, eps);
+        if (blockIdx.x == 0 && threadIdx.x < (unsigned)(A.n - n4 * 4)) adam_dense_element(A, n4 * 4 + threadIdx.x, lr_t, b1, b2, eps);
+    } else if (A.n_arenas > 0) {                     // (n == 0 and no arena: the one workgroup only takes its ticket —
+        adam_arena_block(A, blockIdx.x, lr_t, b1, b2, eps);      //  ar[0] is then a padding descriptor with no count to read)
+    }
+    if (A.advance) adam_publish_step(A, t);
+}
+
+// ---------------------------------------------------------------------------------------
+// The step's deferred sums AND the optimizer launch above in one: a weight gradient that the backward pass left as split slabs or
+// partial rows is summed (slab_sum.h: the order of dense_sum_slabs_kernel) by the thread that then updates the parameter — the sum
+// launch wrote it to the flat gradient buffer only for this launch to read it back once, a kernel boundary later.
+// Workgroups: [the jobs' (first_block, the layout of the sum launch) | "rest": the intervals of the flat buffer no job writes,
+// their gradient read from the buffer as above | arenas | plan scans].  A job whose output lies outside the flat buffer (the loss
+// value) is only summed.  p, m, v of a job's element are requested before its slabs, so that all the loads are in flight together.
+// ---------------------------------------------------------------------------------------
+constexpr int kSumStepMaxJobs = recalgo_slabs::kMaxSplitJobs;
+constexpr int kSumStepMaxRest = 2 * kSumStepMaxJobs + 1;     // (the complement of <= 2 outputs per job)
+struct SumStepArgs {
+    AdamStepArgs A;                // A.dense_blocks = job_blocks + rest_blocks
+    recalgo_slabs::SplitJob job[kSumStepMaxJobs];
+    int n_jobs, n_rest;
+    unsigned job_blocks, rest_blocks;
+    unsigned lr_block;             // the workgroup behind the plan scans that leaves the next step's lr_t (no ticket buffer: none)
+    long long rest_lo[kSumStepMaxRest], rest_hi[kSumStepMaxRest];     // element intervals [lo, hi) of the flat buffer
+};
+static_assert(sizeof(SumStepArgs) <= 4096, "passed by value: the kernel-argument segment");
+
+// what the optimizer launch does with one summed element e of the flat buffer / one float4 word e4 (p, m, v loaded by the caller)
+__device__ __forceinline__ void sum_step_finish1(const AdamStepArgs& A, size_t e, float gg, float pp, float mm, float vv, float lr_t) {
+    if (!(gg == 0.f && mm == 0.f && vv == 0.f)) {
+        adam1(pp, gg, mm, vv, lr_t, A.b1, A.b2, A.eps);
+        A.p[e] = pp; A.m[e] = mm; A.v[e] = vv;
+    }
+    A.g[e] = (A.zero_grad && gg != 0.f) ? 0.f : gg;
+}
+__device__ __forceinline__ void sum_step_finish4(const AdamStepArgs& A, size_t e4, float4 gg, float4 pp, float4 mm, float4 vv, float lr_t) {
+    const float b1 = A.b1, b2 = A.b2, eps = A.eps;
+    const bool nz = gg.x != 0.f || gg.y != 0.f || gg.z != 0.f || gg.w != 0.f;
+    const bool inert = !nz && mm.x == 0.f && mm.y == 0.f && mm.z == 0.f && mm.w == 0.f && vv.x == 0.f && vv.y == 0.f &&
+                       vv.z == 0.f && vv.w == 0.f;
+    if (!inert) {
+        adam1(pp.x, gg.x, mm.x, vv.x, lr_t, b1, b2, eps);
+        adam1(pp.y, gg.y, mm.y, vv.y, lr_t, b1, b2, eps);
+        adam1(pp.z, gg.z, mm.z, vv.z, lr_t, b1, b2, eps);
+        adam1(pp.w, gg.w, mm.w, vv.w, lr_t, b1, b2, eps);
+        reinterpret_cast<float4*>(A.p)[e4] = pp;
+        reinterpret_cast<float4*>(A.m)[e4] = mm;
+        reinterpret_cast<float4*>(A.v)[e4] = vv;
+    }
+    reinterpret_cast<float4*>(A.g)[e4] = (A.zero_grad && nz) ? f4_zero() : gg;   // (what sum + step leave: the sum, or zero_grad's zeros)
+}
+
+// The arrival ticket of this launch, sharded: its several hundred workgroups end within a microsecond of each other, and one
+// word takes an atomic every ~12 ns (all of them on one ticket made the launch 15.3 us, the sum of the two it replaces 14.2).
+// A workgroup arrives at shard blockIdx % 8 (a word on a line of its own); the last of a shard re-arms it and arrives at the top
+// word, the last there re-arms that and publishes the step count.
+constexpr int kTicketShards = 8;
+constexpr int kTicketStride = 64;                                    // ints between two words: 256 bytes
+constexpr int kTicketInts = kTicketStride * (kTicketShards + 3);      // (recalgo_adam_tf1_sum_step_workspace_bytes)
+// Behind the ticket words, two slots {t, lr, b1, b2 -> lr_t}: lr_t costs two pow and a sqrt in double behind the load of the
+// counter (~2.5 us in front of a workgroup's first slab load).  One extra workgroup of the launch of step t leaves lr_t of step
+// t + 1 in slot (t + 1) & 1 (nobody reads that slot in this launch); the workgroups of the next launch find it there, compare the
+// whole key, and compute lr_t themselves where it does not match (the first step, a counter set from outside).
+struct LrSlot { int t_lo, t_hi, lr, b1, b2, lr_t; };
+__device__ __forceinline__ int* lr_slot(const AdamStepArgs& A, int k) { return A.ticket + (kTicketShards + 1 + k) * kTicketStride; }
+__device__ __forceinline__ void sum_step_publish(const AdamStepArgs& A, long long t) {
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned total = A.scan_first, s = blockIdx.x % kTicketShards;         // (the scan workgroups take no ticket)
+        const unsigned in_shard = (total - s + kTicketShards - 1) / kTicketShards;   // workgroups b < total with b % 8 == s
+        int* shard = A.ticket + (1 + s) * kTicketStride;
+        if (__hip_atomic_fetch_add(shard, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)in_shard - 1) {
+            __hip_atomic_store(shard, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned shards = total < (unsigned)kTicketShards ? total : (unsigned)kTicketShards;
+            if (__hip_atomic_fetch_add(A.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)shards - 1) {
+                __hip_atomic_store(A.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                A.step[0] = t;
+            }
+        }
+    }
+}
+
+// (the name ends in adam_tf1_step_kernel: bench.in_step_table counts a profile's steps by the launches of that name)
+__global__ __launch_bounds__(256) void sums_adam_tf1_step_kernel(SumStepArgs K) {
+    const AdamStepArgs& A = K.A;
+    __shared__ float s_lr_t;
+    if (blockIdx.x >= A.scan_first && blockIdx.x != K.lr_block) {     // (workgroup-uniform, as every branch on blockIdx below)
+        __shared__ unsigned scan_sh[8];
+        recalgo_plan::scan_block(A.scan[blockIdx.x - A.scan_first], scan_sh);
+        return;
+    }
+    if (blockIdx.x == K.lr_block) {                            // lr_t of the NEXT step (see LrSlot)
+        if (threadIdx.x == 0) {
+            const long long tn = A.step[0] + (A.advance ? 2 : 1);
+            int* o = lr_slot(A, (int)(tn & 1));
+            o[0] = (int)tn; o[1] = (int)(tn >> 32); o[2] = __float_as_int(A.lr); o[3] = __float_as_int(A.b1);
+            o[4] = __float_as_int(A.b2); o[5] = __float_as_int(adam_lr_t_value(A, tn));
+        }
+        return;
+    }
+    // (both slots are requested with the counter: no load depends on another)
+    LrSlot c0{}, c1{};
+    if (A.ticket != nullptr) {
+        const int* a = lr_slot(A, 0);
+        const int* b = lr_slot(A, 1);
+        c0 = LrSlot{a[0], a[1], a[2], a[3], a[4], a[5]};
+        c1 = LrSlot{b[0], b[1], b[2], b[3], b[4], b[5]};
+    }
+    const long long t = A.step[0] + (A.advance ? 1 : 0);
+    const LrSlot c = (t & 1) ? c1 : c0;
+    const bool cached = A.ticket != nullptr && c.t_lo == (int)t && c.t_hi == (int)(t >> 32) && c.lr == __float_as_int(A.lr) &&
+                        c.b1 == __float_as_int(A.b1) && c.b2 == __float_as_int(A.b2);           // (uniform over the whole grid)
+    const float lr_t = cached ? __int_as_float(c.lr_t) : adam_lr_t(A, t, &s_lr_t);
+    if (blockIdx.x < K.job_blocks) {
+        int j = 0;
+#pragma unroll
+        for (int k = 1; k < kSumStepMaxJobs; ++k)
+            if (k < K.n_jobs && blockIdx.x >= K.job[k].first_block) j = k;
+        const recalgo_slabs::SplitJob& jb = K.job[j];
+        const size_t blk = blockIdx.x - jb.first_block;
+        const unsigned long long flat_bytes = (unsigned long long)A.n * sizeof(float);
+        if (jb.vec == 2) {
+            __shared__ float sh[16][17];
+            const size_t c = blk * 16 + (threadIdx.x & 15);
+            const bool writer = (threadIdx.x >> 4) == 0 && c < jb.n;
+            // (byte offset into the flat gradient buffer; an output outside it wraps to a large number)
+            const unsigned long long off = (unsigned long long)(reinterpret_cast<uintptr_t>(jb.out0 + c) - reinterpret_cast<uintptr_t>(A.g));
+            const bool flat = writer && off < flat_bytes;
+            const size_t e = (size_t)(off / sizeof(float));
+            float pp = 0.f, mm = 0.f, vv = 0.f;
+            if (flat) { pp = A.p[e]; mm = A.m[e]; vv = A.v[e]; }
+            const float gg = recalgo_slabs::sum_tall(jb, blk, sh);
+            if (flat) sum_step_finish1(A, e, gg, pp, mm, vv, lr_t);
+            else if (writer) jb.out0[c] = gg;
+        } else if (jb.vec) {
+            const size_t i = (blk * 256 + threadIdx.x) * 4;
+            if (i < jb.n) {
+                const size_t e4 = (size_t)(recalgo_slabs::job_target(jb, i) - A.g) / 4;
+                const float4 pp = reinterpret_cast<const float4*>(A.p)[e4], mm = reinterpret_cast<const float4*>(A.m)[e4],
+                             vv = reinterpret_cast<const float4*>(A.v)[e4];
+                sum_step_finish4(A, e4, recalgo_slabs::sum_slabs4(jb, i), pp, mm, vv, lr_t);
+            }
+        } else {
+            const size_t i = blk * 256 + threadIdx.x;
+            if (i < jb.n) {
+                const size_t e = (size_t)(recalgo_slabs::job_target(jb, i) - A.g);
+                const float pp = A.p[e], mm = A.m[e], vv = A.v[e];
+                sum_step_finish1(A, e, recalgo_slabs::sum_slabs1(jb, i), pp, mm, vv, lr_t);
+            }
+        }
+    } else if (blockIdx.x < A.dense_blocks) {
+        const unsigned blk = blockIdx.x - K.job_blocks;
+        for (int k = 0; k < K.n_rest; ++k) {
+            const long long lo = K.rest_lo[k], hi = K.rest_hi[k];
+            const long long lo4 = (lo + 3) >> 2, hi4 = hi >> 2;
+            if (lo4 < hi4) adam_dense_words(A, lo4, hi4, blk, K.rest_blocks, lr_t, A.b1, A.b2, A.eps);
+            if (blk == 0 && threadIdx.x < 8) {
+                // the elements in front of the first whole word (threads 0-2) and behind the last (threads 4-6)
+                const long long head_end = lo4 * 4 < hi ? lo4 * 4 : hi, tail_lo = hi4 * 4 > head_end ? hi4 * 4 : head_end;
+                const long long i = threadIdx.x < 4 ? lo + threadIdx.x : tail_lo + (threadIdx.x - 4);
+                if (i < (threadIdx.x < 4 ? head_end : hi)) adam_dense_element(A, i, lr_t, A.b1, A.b2, A.eps);
+            }
+        }
+    } else if (A.n_arenas > 0) {
+        adam_arena_block(A, blockIdx.x, lr_t, A.b1, A.b2, A.eps);
+    }
+    if (A.advance) sum_step_publish(A, t);
 }
 
 __global__ void adam_advance_kernel(int64_t* step, float lr, float b1, float b2, float* lr_t) {
@@ -858,20 +1047,17 @@ RECALGO_EXPORT int recalgo_adam_tf1_step(float* p, float* g, float* m, float* v,
                                        zero_grad, nullptr, 0, stream);
 }
 
-RECALGO_EXPORT int recalgo_adam_tf1_step_plans(float* p, float* g, float* m, float* v, int64_t n,
-                                               const recalgo_adam_arena_t* arenas, int n_arenas, int64_t* step_dev,
-                                               int* ticket_dev, int advance, float lr, float beta1, float beta2, float eps,
-                                               int zero_grad, const recalgo_plan_scan_t* scans, int n_scans,
-                                               recalgo_stream_t stream) {
+// The launch's arguments but for the dense workgroups (A.dense_blocks: set by the caller, who launches A.scan_first + n_scans
+// workgroups) -> 0 or hipErrorInvalidValue
+static int fill_adam_step_args(AdamStepArgs& A, float* p, float* g, float* m, float* v, int64_t n, const recalgo_adam_arena_t* arenas,
+                               int n_arenas, int64_t* step_dev, int* ticket_dev, int advance, float lr, float beta1, float beta2,
+                               float eps, int zero_grad, const recalgo_plan_scan_t* scans, int n_scans) {
     RECALGO_REQUIRE(n >= 0 && n_arenas >= 0 && n_arenas <= kAdamMaxArenas && step_dev != nullptr);
     RECALGO_REQUIRE(n_scans >= 0 && n_scans <= kAdamMaxArenas && (n_scans == 0 || scans != nullptr));
     RECALGO_REQUIRE(!advance || ticket_dev != nullptr);
     RECALGO_REQUIRE(n == 0 || (p && g && m && v && aligned16(p, g, m, v)));
     RECALGO_REQUIRE(n_arenas == 0 || arenas != nullptr);
-    AdamStepArgs A;
     A.p = p; A.g = g; A.m = m; A.v = v; A.n = n;
-    const int64_t want = (n / 4 + 255) / 256;
-    A.dense_blocks = n == 0 ? 0u : (unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
     unsigned blocks = A.dense_blocks;
     A.n_arenas = 0;
     for (int i = 0; i < n_arenas; ++i) {
@@ -908,7 +1094,106 @@ RECALGO_EXPORT int recalgo_adam_tf1_step_plans(float* p, float* g, float* m, flo
         A.scan[i] = recalgo_plan::Scan{c.total, c.offs, static_cast<uint4*>(c.sched), c.counter_shift, c.nb_log2};
     }
     for (int i = n_scans; i < kAdamMaxArenas; ++i) A.scan[i] = recalgo_plan::Scan{nullptr, nullptr, nullptr, 0, 8};
-    blocks += (unsigned)n_scans;
-    hipLaunchKernelGGL(adam_tf1_step_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), A);
+    return 0;
+}
+
+RECALGO_EXPORT int recalgo_adam_tf1_step_plans(float* p, float* g, float* m, float* v, int64_t n,
+                                               const recalgo_adam_arena_t* arenas, int n_arenas, int64_t* step_dev,
+                                               int* ticket_dev, int advance, float lr, float beta1, float beta2, float eps,
+                                               int zero_grad, const recalgo_plan_scan_t* scans, int n_scans,
+                                               recalgo_stream_t stream) {
+    RECALGO_REQUIRE(n >= 0);
+    AdamStepArgs A;
+    const int64_t want = (n / 4 + 255) / 256;
+    A.dense_blocks = n == 0 ? 0u : (unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+    const int rc = fill_adam_step_args(A, p, g, m, v, n, arenas, n_arenas, step_dev, ticket_dev, advance, lr, beta1, beta2, eps,
+                                       zero_grad, scans, n_scans);
+    if (rc) return rc;
+    hipLaunchKernelGGL(adam_tf1_step_kernel, dim3(A.scan_first + (unsigned)n_scans), dim3(256), 0, as_stream(stream), A);
+    RECALGO_RETURN_LAST();
+}
+
+// The job table of the sum-and-step launch and the intervals of the flat buffer no job writes -> 1, or 0 where the launch cannot
+// serve the jobs (recalgo_adam_tf1_sum_step_supported)
+static int build_sum_step(SumStepArgs& K, const float* g, int64_t n, const recalgo_dense_split_t* jobs, int n_jobs,
+                          const recalgo_colsum_t* sums, int n_sums, const recalgo_colsum_t* side_sums, int n_side_sums) {
+    if (n < 0 || n_jobs < 0 || n_sums < 0 || n_side_sums < 0 || (n_jobs && !jobs) || (n_sums && !sums) || (n_side_sums && !side_sums))
+        return 0;
+    if (n > 0 && (g == nullptr || !aligned16(g))) return 0;
+    std::vector<recalgo_colsum_t> cs(sums, sums + n_sums);
+    cs.insert(cs.end(), side_sums, side_sums + n_side_sums);
+    unsigned blocks = 0;
+    if (recalgo_build_split_jobs(jobs, n_jobs, cs.data(), (int)cs.size(), K.job, kSumStepMaxJobs, &K.n_jobs, &blocks) != 0) return 0;
+    K.job_blocks = blocks;
+    const uintptr_t g0 = reinterpret_cast<uintptr_t>(g), g1 = g0 + (uintptr_t)n * sizeof(float);
+    std::vector<std::pair<int64_t, int64_t>> outs;               // [lo, hi) in elements of the flat buffer
+    for (int j = 0; j < K.n_jobs; ++j) {
+        const recalgo_slabs::SplitJob& jb = K.job[j];
+        const bool side = jb.vec == 2 && j >= n_sums;            // (the column sums come first, in the caller's order)
+        const std::pair<const float*, unsigned long long> o[2] = {{jb.out0, jb.n0}, {jb.out1, jb.n - jb.n0}};
+        for (int h = 0; h < 2; ++h) {
+            if (o[h].second == 0) continue;
+            const uintptr_t a = reinterpret_cast<uintptr_t>(o[h].first), b = a + (uintptr_t)o[h].second * sizeof(float);
+            if (side) {
+                if (a < g1 && b > g0) return 0;                    // a value that is no gradient, inside the gradient buffer
+                continue;
+            }
+            if (a < g0 || b > g1 || (a - g0) % sizeof(float) != 0) return 0;
+            // (the float4 path's outputs are 16-byte aligned, as is g: make_split_job)
+            outs.emplace_back((int64_t)((a - g0) / sizeof(float)), (int64_t)((b - g0) / sizeof(float)));
+        }
+    }
+    std::sort(outs.begin(), outs.end());
+    K.n_rest = 0;
+    int64_t at = 0, rest = 0;
+    auto gap = [&](int64_t lo, int64_t hi) {
+        if (lo >= hi) return;
+        K.rest_lo[K.n_rest] = lo; K.rest_hi[K.n_rest] = hi;
+        ++K.n_rest;
+        rest += hi - lo;
+    };
+    for (const auto& o : outs) {
+        if (o.first < at) return 0;                                // two outputs overlap
+        gap(at, o.first);
+        at = o.second;
+    }
+    gap(at, n);
+    const int64_t want = (rest / 4 + 255) / 256;
+    K.rest_blocks = rest == 0 ? 0u : (unsigned)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
+    return 1;
+}
+
+RECALGO_EXPORT int64_t recalgo_adam_tf1_sum_step_workspace_bytes(void) { return (int64_t)kTicketInts * (int64_t)sizeof(int); }
+
+// (include/recalgo_sumstep.h declares the descriptor arrays of recalgo.h as const void*: that header stands alone)
+RECALGO_EXPORT int recalgo_sumstep_abi_version(void) { return RECALGO_SUMSTEP_ABI_VERSION; }
+
+RECALGO_EXPORT int recalgo_adam_tf1_sum_step_supported(const float* g, int64_t n, const void* jobs, int n_jobs, const void* sums,
+                                                       int n_sums, const void* side_sums, int n_side_sums) {
+    SumStepArgs K;
+    return build_sum_step(K, g, n, static_cast<const recalgo_dense_split_t*>(jobs), n_jobs, static_cast<const recalgo_colsum_t*>(sums),
+                          n_sums, static_cast<const recalgo_colsum_t*>(side_sums), n_side_sums);
+}
+
+RECALGO_EXPORT int recalgo_adam_tf1_sum_step(float* p, float* g, float* m, float* v, int64_t n, const void* arenas_, int n_arenas,
+                                             int64_t* step_dev, int* ticket_dev, int advance, float lr, float beta1, float beta2,
+                                             float eps, int zero_grad, const void* scans_, int n_scans, const void* jobs, int n_jobs,
+                                             const void* sums, int n_sums, const void* side_sums, int n_side_sums,
+                                             recalgo_stream_t stream) {
+    const recalgo_adam_arena_t* arenas = static_cast<const recalgo_adam_arena_t*>(arenas_);
+    const recalgo_plan_scan_t* scans = static_cast<const recalgo_plan_scan_t*>(scans_);
+    SumStepArgs K;
+    RECALGO_REQUIRE(build_sum_step(K, g, n, static_cast<const recalgo_dense_split_t*>(jobs), n_jobs,
+                                   static_cast<const recalgo_colsum_t*>(sums), n_sums, static_cast<const recalgo_colsum_t*>(side_sums),
+                                   n_side_sums));
+    for (int j = K.n_jobs; j < kSumStepMaxJobs; ++j) K.job[j] = recalgo_slabs::SplitJob{nullptr, nullptr, nullptr, 0, 0, 0, 0, 0, 0xffffffffu};
+    for (int k = K.n_rest; k < kSumStepMaxRest; ++k) K.rest_lo[k] = K.rest_hi[k] = 0;
+    K.A.dense_blocks = K.job_blocks + K.rest_blocks;
+    const int rc = fill_adam_step_args(K.A, p, g, m, v, n, arenas, n_arenas, step_dev, ticket_dev, advance, lr, beta1, beta2, eps,
+                                       zero_grad, scans, n_scans);
+    if (rc) return rc;
+    K.lr_block = ticket_dev != nullptr ? K.A.scan_first + (unsigned)n_scans : 0xffffffffu;
+    hipLaunchKernelGGL(sums_adam_tf1_step_kernel, dim3(K.A.scan_first + (unsigned)n_scans + (ticket_dev != nullptr ? 1u : 0u)), dim3(256),
+                       0, as_stream(stream), K);
     RECALGO_RETURN_LAST();
 }

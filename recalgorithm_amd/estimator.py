@@ -100,6 +100,25 @@ class AdamOptimizer:
         owned.sort(key=sparse.has_companions)     # (an arena whose lookups ride on another arena's plan comes after it)
         arenas = [ar for ar in arenas if not sparse.has_work(ar)]
         fused = all(ar.tracks_live_rows for ar in arenas) and len(arenas) <= 4 and store.device.type == "cuda"
+        # The deferred sums INSIDE the optimizer launch (ops.adam_tf1_sum_step_) where nothing has to happen between the two:
+        # no all-reduce of the summed gradients (grad_hook), no other optimizer consuming them (before_update), no parked
+        # l2 term to add to them.  The launch advances the counter itself (arrival ticket: a device int beside the counter,
+        # never created inside a graph capture — the capture's warm-up steps ran eagerly).
+        if fused and ops.sum_step_enabled and grad_hook is None and before_update is None and not ops._parked_l2:
+            if "ticket" not in st and not torch.cuda.is_current_stream_capturing():
+                st["ticket"] = torch.zeros(ops.sum_step_ticket_ints(), dtype=torch.int32, device=store.device)
+            if "ticket" in st:
+                dense, colsums = ops.take_dense_splits()
+                scans = [r for r in (sparse.plan_scan_record(ar, self.lazy_embeddings) for ar in owned[:4]) if r is not None]
+                if not ops.adam_tf1_sum_step_(store.flat, store.flat_grad, store.flat_m, store.flat_v, arenas, st["step"],
+                                              st["ticket"], self.lr, self.beta1, self.beta2, self.eps, dense, colsums,
+                                              lazy=self.lazy_embeddings, plan_scans=scans):
+                    ops._launch_dense_splits(dense, colsums, st["step"])         # refused: the two launches
+                    ops.adam_tf1_step_(store.flat, store.flat_grad, store.flat_m, store.flat_v, arenas, st["step"], None,
+                                       self.lr, self.beta1, self.beta2, self.eps, lazy=self.lazy_embeddings, plan_scans=scans)
+                for ar in owned:
+                    sparse.apply(ar, self.lazy_embeddings, st["step"], self.lr, self.beta1, self.beta2, self.eps)
+                return
         # parked gradients: deferred weight-gradient split sums (+ the step counter, advanced by the same launch),
         # l2-regulariser contributions (PNN weight_regularizer)
         nn.apply_parked_grads(step_dev=st["step"] if fused else None)

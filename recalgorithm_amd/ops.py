@@ -1497,21 +1497,37 @@ def flush_dense_splits(step_dev: Optional[torch.Tensor] = None) -> None:
     """Finish every deferred sum of the step in ONE launch: the weight-gradient split reductions of `dense`, the column
     sums the loss tail left behind, and (`step_dev`, the optimizer's int64 step counter) the step increment — the
     optimizer kernel that follows then only reads the counter."""
+    _launch_dense_splits(*take_dense_splits(), step_dev)
+
+
+def take_dense_splits():
+    """The hand-over form of flush_dense_splits: everything it does but the launch -> (the _dense_pending entries, the
+    _colsum_pending entries) of the step, for a launch that hosts the sums (adam_tf1_sum_step_) or, where that one refuses,
+    for _launch_dense_splits."""
     launch_wgrad_rider()
     _dlogit_partials.clear()                 # (keyed by an address: no entry may outlive its step's deferred-sum launch)
-    if not _dense_pending and not _colsum_pending and step_dev is None:
-        return
-    jobs = (_DenseSplit * max(len(_dense_pending), 1))()
-    for i, (M, K, N, ws, dw, dbias) in enumerate(_dense_pending):
-        jobs[i] = _DenseSplit(M, K, N, ws.data_ptr(), dw.data_ptr(), 0 if dbias is None else dbias.data_ptr())
-    sums = (_ColSum * max(len(_colsum_pending), 1))()
-    for i, (part, off, rows, stride, n, out) in enumerate(_colsum_pending):
-        sums[i] = _ColSum(part.data_ptr() + 4 * off, out.data_ptr(), rows, stride, n)
-    dev_t = _dense_pending[0][4] if _dense_pending else (_colsum_pending[0][0] if _colsum_pending else step_dev)
-    nj, ns = len(_dense_pending), len(_colsum_pending)
+    dense, colsums = list(_dense_pending), list(_colsum_pending)
     _dense_pending.clear()
     _colsum_pending.clear()
-    _lib_().recalgo_dense_bwd_weights_reduce(jobs, nj, sums, ns, _p(step_dev), _stream(dev_t))
+    return dense, colsums
+
+
+def _split_job_arrays(dense, colsums):
+    jobs = (_DenseSplit * max(len(dense), 1))()
+    for i, (M, K, N, ws, dw, dbias) in enumerate(dense):
+        jobs[i] = _DenseSplit(M, K, N, ws.data_ptr(), dw.data_ptr(), 0 if dbias is None else dbias.data_ptr())
+    sums = (_ColSum * max(len(colsums), 1))()
+    for i, (part, off, rows, stride, n, out) in enumerate(colsums):
+        sums[i] = _ColSum(part.data_ptr() + 4 * off, out.data_ptr(), rows, stride, n)
+    return jobs, sums
+
+
+def _launch_dense_splits(dense, colsums, step_dev: Optional[torch.Tensor]) -> None:
+    if not dense and not colsums and step_dev is None:
+        return
+    jobs, sums = _split_job_arrays(dense, colsums)
+    dev_t = dense[0][4] if dense else (colsums[0][0] if colsums else step_dev)
+    _lib_().recalgo_dense_bwd_weights_reduce(jobs, len(dense), sums, len(colsums), _p(step_dev), _stream(dev_t))
 
 
 def mlp_width_supported(C: int) -> bool:
@@ -2414,6 +2430,50 @@ def adam_tf1_step_(flat, flat_grad, flat_m, flat_v, arenas, step_dev: torch.Tens
         lib.recalgo_adam_tf1_step_plans(_p(flat) if n else None, _p(flat_grad) if n else None, _p(flat_m) if n else None,
                                         _p(flat_v) if n else None, n, arr, len(chunk), _p(step_dev), _p(ticket_dev), int(advance),
                                         lr, beta1, beta2, eps, int(zero_grad), scans, len(plan_scans), _stream(step_dev))
+
+
+# The step's deferred sums inside the optimizer launch (recalgo_adam_tf1_sum_step): off -> the two launches, always
+sum_step_enabled = True
+sum_step_stats = {"fused": 0, "refused": 0}       # optimizer steps that ran as the one launch / that the entry refused
+
+
+def sum_step_ticket_ints() -> int:
+    """Length of the zeroed int32 tensor the launch keeps its arrival ticket in (adam_tf1_sum_step_'s ticket_dev)."""
+    return int(_lib_().recalgo_adam_tf1_sum_step_workspace_bytes()) // 4
+
+
+def adam_tf1_sum_step_(flat, flat_grad, flat_m, flat_v, arenas, step_dev: torch.Tensor, ticket_dev: torch.Tensor, lr: float,
+                       beta1: float, beta2: float, eps: float, dense, colsums, lazy: bool = False, plan_scans=()) -> bool:
+    """flush_dense_splits(step_dev) + adam_tf1_step_(.., zero_grad=True) as ONE launch (include/recalgo_sumstep.h
+    recalgo_adam_tf1_sum_step), bit-identical to the two.  dense, colsums: take_dense_splits().  -> False, nothing launched,
+    where the entry cannot serve the jobs (the caller runs the two launches)."""
+    lib = _lib_()
+    n = 0 if flat is None else flat.numel()
+    if len(arenas) > 4:
+        return False
+    g0 = flat_grad.data_ptr() if n else 0
+    g1 = g0 + 4 * n
+    # a column sum whose output is no part of the flat gradient buffer (the loss value) is only summed
+    side = [c for c in colsums if c[5].data_ptr() + 4 * c[4] <= g0 or c[5].data_ptr() >= g1]
+    grads = [c for c in colsums if not any(c is e for e in side)]
+    jobs, sums = _split_job_arrays(dense, grads)
+    _, side_sums = _split_job_arrays((), side)
+    gp = _p(flat_grad) if n else None
+    if not lib.recalgo_adam_tf1_sum_step_supported(gp, n, jobs, len(dense), sums, len(grads), side_sums, len(side)):
+        sum_step_stats["refused"] += 1
+        return False
+    arr = (_AdamArena * max(len(arenas), 1))()
+    for j, a in enumerate(arenas):
+        _, lst, cnt = a.live_state()
+        rows, K = a.weight.shape
+        arr[j] = _AdamArena(a.weight.data_ptr(), a.grad.data_ptr(), a.m.data_ptr(), a.v.data_ptr(), lst.data_ptr(),
+                            cnt.data_ptr(), rows, K, int(lazy))
+    scans = (type(plan_scans[0]) * len(plan_scans))(*plan_scans) if plan_scans else None
+    lib.recalgo_adam_tf1_sum_step(_p(flat) if n else None, gp, _p(flat_m) if n else None, _p(flat_v) if n else None, n, arr,
+                                  len(arenas), _p(step_dev), _p(ticket_dev), 1, lr, beta1, beta2, eps, 1, scans, len(plan_scans),
+                                  jobs, len(dense), sums, len(grads), side_sums, len(side), _stream(step_dev))
+    sum_step_stats["fused"] += 1
+    return True
 
 
 # =============================================================================================
