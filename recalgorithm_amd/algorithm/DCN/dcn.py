@@ -18,6 +18,7 @@ from ... import flags, nn, ops
 from ...estimator import (Estimator, EvalSpec, ModeKeys, RunConfig, TrainSpec, train_and_evaluate)
 from ...model_tail import finish_model_fn
 from ...variables import variable_scope
+from .. import _common as common
 from ..utils import eval_input_fn, parse_example, train_input_fn
 from .cross_layer import cross_network
 
@@ -36,6 +37,7 @@ flags.DEFINE_integer("batch_size", 1024, "Training batch size")
 flags.DEFINE_float("learning_rate", 0.005, "Learning rate")
 flags.DEFINE_string("hidden_units", "512,256,128", "Comma-separated list of number of units in each hidden layer")
 flags.DEFINE_integer("num_cross_layer", 1, "Number of cross layers")
+common.define_ragged_capacity_flag()
 FLAGS = flags.FLAGS
 
 DENSE_FEATURES = [  # dcn.py:59-76 (list order; input_layer sorts by name)
@@ -79,6 +81,9 @@ def example_parser(serialized_example):
     features = parse_example(serialized_example, spec)
     read_comment = features.pop("read_comment")
     return features, {"read_comment": read_comment}
+
+
+example_parser.columns_getter = lambda: (total_feature_columns, label_feature_columns)   # native decoder hook
 
 
 def dcn_model_fn(features, labels, mode, params):
@@ -130,7 +135,8 @@ def main(unused_argv):
     print(params)
     estimator = Estimator(model_fn=dcn_model_fn, params=params,
                           config=RunConfig(model_dir=FLAGS.model_dir,
-                                           save_checkpoints_steps=FLAGS.save_checkpoints_steps))
+                                           save_checkpoints_steps=FLAGS.save_checkpoints_steps,
+                                           ragged_capacity=common.ragged_capacity_from_flags()))
     train_spec = TrainSpec(
         input_fn=lambda: train_input_fn(filepath=FLAGS.train_data, example_parser=example_parser,
                                         batch_size=FLAGS.batch_size, num_epochs=FLAGS.num_epochs,

@@ -29,6 +29,8 @@ flags.DEFINE_string("activation", "dice", "Dense layer activation, supported str
 flags.DEFINE_boolean("mini_batch_aware_regularization", True, "Whether to use mini_batch_aware_regularization")
 flags.DEFINE_float("l2_lambda", 0.2, "Coefficient when using mini_batch_aware_regularization")
 flags.DEFINE_boolean("use_softmax", False, "Whether to use softmax on attention score")
+flags.DEFINE_integer("sequence_max_length", 0, "Pad the history to this many steps (static shapes: with --ragged_capacity the "
+                     "training step can be captured); 0 = the longest history of the batch, as the reference")
 FLAGS = flags.FLAGS
 
 
@@ -131,6 +133,7 @@ def main(unused_argv):
         "mini_batch_aware_regularization": FLAGS.mini_batch_aware_regularization,
         "l2_lambda": FLAGS.l2_lambda,
         "use_softmax": FLAGS.use_softmax,
+        "sequence_max_length": FLAGS.sequence_max_length or None,
     }
     common.run_estimator(din_model_fn, params, example_parser)
 

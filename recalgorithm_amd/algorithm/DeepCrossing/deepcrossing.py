@@ -22,7 +22,7 @@ from .. import _common as common
 from .residual_unit import residual_unit  # noqa: F401  (the reference's import; the model_fn runs the units as one stack)
 
 # flags: deepcrossing.py:20-37
-common.define_common_flags()
+common.define_common_flags(ragged_capacity=False)         # (this script keeps exactly the reference's flag list)
 flags.DEFINE_integer("residual_internal_dim", 128, "Residual module internal dimension")
 flags.DEFINE_integer("residual_network_num", 1, "Numbers of residual networks")
 FLAGS = flags.FLAGS

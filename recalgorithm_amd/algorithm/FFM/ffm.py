@@ -48,9 +48,11 @@ example_parser = common.make_example_parser(lambda: (total_feature_columns, labe
 
 def _distinct_bags(x: Ragged) -> Ragged:
     """utils.py:49-64 `to_sparse_tensor` of a multi-hot row: its DISTINCT valid ids, ascending."""
+    fc.data_dependent("FFM: the distinct ids of a bag (_distinct_bags) have a data-dependent count")
     vals, offs = x.values, x.offsets
     B = offs.numel() - 1
     bag = torch.repeat_interleave(torch.arange(B, device=vals.device), offs[1:] - offs[:-1])
+    vals = vals[:bag.numel()]                                    # (a padded Ragged: the -1 tail belongs to no bag)
     ok = vals >= 0
     key = bag[ok] * (int(vals.max().item()) + 2 if vals.numel() else 1) + vals[ok]
     uniq = torch.unique(key)                                     # sorted

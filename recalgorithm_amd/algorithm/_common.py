@@ -26,7 +26,24 @@ DENSE_FEATURES = [  # list order of dcn.py:59-76; fc.input_layer sorts by name
 ]
 
 
-def define_common_flags(batch_size=1024, learning_rate=0.005):
+def define_ragged_capacity_flag():
+    """--ragged_capacity (not a reference flag): RunConfig(ragged_capacity=), see ragged_capacity_from_flags"""
+    flags.DEFINE_integer("ragged_capacity", 0, "Values per example that a bag or history buffer holds, so that training and "
+                         "evaluation steps over them are captured into a graph (0: off, such batches run eagerly; -1: auto, "
+                         "1.25 x the largest batch of the warm-up steps)")
+
+
+def ragged_capacity_from_flags():
+    """--ragged_capacity as RunConfig takes it: 0 (or a script without the flag) -> None, -1 -> "auto", n -> n"""
+    n = int(getattr(FLAGS, "ragged_capacity", 0) or 0)
+    if n < -1:
+        raise ValueError(f"--ragged_capacity={n}: expected 0 (off), -1 (auto) or a number of values per example")
+    return None if n == 0 else "auto" if n == -1 else n
+
+
+def define_common_flags(batch_size=1024, learning_rate=0.005, ragged_capacity=True):
+    if ragged_capacity:                      # (False: a script whose flag list is exactly the reference's)
+        define_ragged_capacity_flag()
     flags.DEFINE_string("model_dir", "./model_dir", "Directory where model parameters, graph, etc are saved")
     flags.DEFINE_string("output_dir", "./output_dir", "Directory where pb file are saved")
     flags.DEFINE_string("train_data", "../../dataset/wechat_algo_data1/tfrecord/train.tfrecord", "Path to the train data")
@@ -113,7 +130,8 @@ def run_estimator(model_fn, params, example_parser, predictions_writer=None):
     print(params)
     estimator = Estimator(model_fn=model_fn, params=params,
                           config=RunConfig(model_dir=FLAGS.model_dir,
-                                           save_checkpoints_steps=FLAGS.save_checkpoints_steps))
+                                           save_checkpoints_steps=FLAGS.save_checkpoints_steps,
+                                           ragged_capacity=ragged_capacity_from_flags()))
     train_spec = TrainSpec(
         input_fn=lambda: train_input_fn(filepath=FLAGS.train_data, example_parser=example_parser,
                                         batch_size=FLAGS.batch_size, num_epochs=FLAGS.num_epochs,

@@ -35,11 +35,64 @@ class EstimatorSpec:
         self.export_outputs, self.training_hooks = export_outputs, training_hooks
 
 
+# --------------------------------------------------------------------------------------------
+# the capacity of a padded Ragged (RunConfig(ragged_capacity=), ServingModel.compile(ragged_capacity=))
+# --------------------------------------------------------------------------------------------
+RAGGED_AUTO_MARGIN = (5, 4)      # "auto": 1.25 x the largest nnz seen ...
+RAGGED_AUTO_ROUND = 1024         # ... rounded up to a multiple of this many values
+
+
+def check_ragged_capacity(policy):
+    """None | int >= 1 | {key: int >= 1} | "auto", or ValueError"""
+    ok = policy is None or policy == "auto" or (isinstance(policy, int) and not isinstance(policy, bool) and policy >= 1) or \
+        (isinstance(policy, dict) and all(isinstance(v, int) and not isinstance(v, bool) and v >= 1 for v in policy.values()))
+    if not ok:
+        raise ValueError(f"ragged_capacity = {policy!r}: expected None, an int >= 1 (values per example), a dict key -> int >= 1, "
+                         "or 'auto'")
+    return dict(policy) if isinstance(policy, dict) else policy
+
+
+def ragged_auto_capacity(max_nnz: int) -> int:
+    """ceil(1.25 * max_nnz / 1024) * 1024, in integers"""
+    num, den = RAGGED_AUTO_MARGIN
+    return (num * int(max_nnz) + den * RAGGED_AUTO_ROUND - 1) // (den * RAGGED_AUTO_ROUND) * RAGGED_AUTO_ROUND
+
+
+def ragged_capacity_for(policy, key: str, rows: int, max_nnz: Optional[int] = None) -> Optional[int]:
+    """The length of the padded `values` of `key` in a batch of `rows` examples, or None when the policy gives none (None; a
+    dict without the key; "auto" before any batch was seen: max_nnz None)."""
+    if isinstance(policy, dict):
+        policy = policy.get(key)
+    if policy is None:
+        return None
+    if policy == "auto":
+        return None if max_nnz is None else ragged_auto_capacity(max_nnz)
+    return int(policy) * int(rows)
+
+
+def ragged_overflows(nnz: int, capacity: Optional[int]) -> bool:
+    """A batch with more values than the capacity is never truncated: it takes the eager route."""
+    return capacity is None or int(nnz) > int(capacity)
+
+
+def dense_as_ragged(ids: torch.Tensor):
+    """A [B] / [B, 1] id vector as the Ragged it stands for: B bags of one value each (an id of -1: a bag without a valid value,
+    which looks up the same zero row)."""
+    from .feature_column import Ragged
+    ids = ids.reshape(-1)
+    return Ragged(ids.contiguous(), torch.arange(ids.numel() + 1, dtype=torch.int64, device=ids.device))
+
+
 class RunConfig:
     def __init__(self, model_dir=None, save_checkpoints_steps=None, device=None, seed=42,
-                 use_hip_graph=True, device_metrics=True, **_ignored):
+                 use_hip_graph=True, device_metrics=True, ragged_capacity=None, **_ignored):
         self.model_dir, self.save_checkpoints_steps = model_dir, save_checkpoints_steps
         self.device, self.seed, self.use_hip_graph = device, seed, use_hip_graph
+        # bags and histories (feature_column.Ragged) in buffers of fixed capacity, so that a step over them is captured:
+        # None (the default): a ragged batch runs eagerly; an int: values per example, for every ragged key; a dict: key ->
+        # values per example; "auto": per key, 1.25 x the largest nnz of the eager warm-up batches, rounded up to 1024 values.
+        # A batch that does not fit is never truncated: it runs eagerly (Estimator.ragged_overflows)
+        self.ragged_capacity = check_ragged_capacity(ragged_capacity)
         # evaluate(): the metrics and the loss sum are accumulated on the device, one launch per batch and one copy at the end
         # (EvalAccumulator); False: the host loop over Metric.update(), which also serves whatever the kernel does not
         self.device_metrics = device_metrics
@@ -579,6 +632,10 @@ class GraphedTrainStep:
     on the current stream) into a hipGraph over static input buffers; `__call__` copies the new
     batch into the static buffers and replays.  Shapes must not change between calls."""
 
+    # True (set by an Estimator with RunConfig(ragged_capacity=)): the static `values` of a Ragged is a buffer of fixed capacity,
+    # and load() accepts the unpadded values of a device-resident batch that fit it
+    pad_values = False
+
     def __init__(self, step_fn: Callable, features, labels, warmup: int = 3):
         self.step_fn = step_fn
         # PRIVATE static input buffers: clones of the first batch (storage-preserving: the 26 id columns of one [B, F]
@@ -629,8 +686,13 @@ class GraphedTrainStep:
             raise BatchShapeMismatch("graphed step: the input structure changed")
         spans = self._static_spans()
         groups = {}
+        pads = []
         for i, ((k0, dst), (k1, src)) in enumerate(zip(self._static, new)):
             if k0 != k1 or dst.shape != src.shape:
+                if (self.pad_values and k0 == k1 and k1.endswith(".values") and src.dim() == 1 and src.numel() <= dst.numel()
+                        and src.dtype == dst.dtype == torch.int64 and src.device == dst.device and src.is_cuda):
+                    pads.append((dst, src))      # (an unpadded device Ragged that fits the static buffer: see below)
+                    continue
                 raise BatchShapeMismatch(f"graphed step: input {k1} changed shape/structure")
             if dst.dtype == src.dtype and dst.stride() == src.stride() and src.device == dst.device:
                 # (same shape, strides and dtype: the source covers a byte span of the same length as the destination's)
@@ -660,6 +722,10 @@ class GraphedTrainStep:
             singles.extend(i for i, _ in items)
         for i in singles:                        # (after every span copy: a per-tensor copy is never overwritten by one)
             self._static[i][1].copy_(new[i][1], non_blocking=True)
+        for dst, src in pads:
+            # the values of a device-resident Ragged go into the static buffer of fixed capacity and the -1 tail is written
+            # by the same launch (recalgo_ragged_pad)
+            ops.ragged_pad(src.contiguous(), dst.numel(), out=dst)
 
     def _static_spans(self):
         """Per static input: (storage pointer, first byte, end byte, element size) — computed once: the per-step path of a
@@ -725,9 +791,80 @@ class Estimator:
         self.loss_grad_scale = None   # 1/world under data parallelism (parallel.attach_data_parallel)
         self._seed_grad, self._seed_value = None, None
         self._pinned = {}                # (shape, dtype) -> ring of pinned staging buffers (_h2d)
+        # RunConfig(ragged_capacity=): see _fit_ragged
+        self.ragged_overflows = 0        # batches that did not fit their capacity and ran eagerly, unpadded
+        self.capture_refused = None      # why no step of this model is captured over ragged inputs (store.data_dependent)
+        self.graph_replays = 0           # steps (train and evaluate) that were one replay of a captured graph
+        self._ragged_keys = set()        # keys that have arrived as a Ragged ...
+        self._ragged_frozen = False      # ... before the first capture
+        self._ragged_seen = {}           # key -> largest nnz of the eager warm-up batches ("auto")
+        self._ragged_caps = {}           # key -> the capacity "auto" settled on when the warm-up ended
 
     # -- plumbing -------------------------------------------------------------------------
     _STAGING_RING = 8
+
+    def _fit_ragged(self, features, warm: bool, loading: bool = False):
+        """RunConfig(ragged_capacity=...): -> (features with every Ragged padded to its capacity, True), or (features as they
+        came, False) for a batch that must run eagerly: one whose nnz exceeds the capacity of any key (never truncated;
+        counted in ragged_overflows), or one with a ragged key the policy gives no capacity.
+        A key that has arrived as a Ragged before and now comes as a dense [B] id vector (no row of the batch holds two values)
+        is presented as B bags of one value.  Host values are padded while the pinned staging buffer is filled; device values
+        by one launch — or, `loading` (the batch goes into a captured step's static buffers next), not at all: GraphedTrainStep.load
+        pads them straight into the static buffer.  `warm`: the eager warm-up steps, which "auto" takes its capacity from."""
+        from .feature_column import Ragged, pad_ragged
+        policy = self.config.ragged_capacity
+        if policy is None or self.capture_refused is not None or not isinstance(features, dict):
+            return features, policy is None
+        if not self._ragged_frozen:          # (until a step is captured: afterwards the padded keys are those of the capture)
+            self._ragged_keys |= {k for k, v in features.items() if isinstance(v, Ragged)}
+        if not self._ragged_keys and not any(isinstance(v, Ragged) for v in features.values()):
+            return features, True
+        out, fits = dict(features), True
+        for k in sorted(set(self._ragged_keys) | {k for k, v in features.items() if isinstance(v, Ragged)}):
+            v = features.get(k)
+            if isinstance(v, torch.Tensor) and v.dtype == torch.int64 and (v.dim() == 1 or (v.dim() == 2 and v.shape[1] == 1)):
+                v = dense_as_ragged(v)
+            if not isinstance(v, Ragged):
+                continue
+            nnz, rows = int(v.values.numel()), int(v.offsets.numel()) - 1
+            if policy == "auto":
+                if warm and k not in self._ragged_caps:
+                    self._ragged_seen[k] = max(self._ragged_seen.get(k, 0), nnz)
+                    cap = ragged_auto_capacity(self._ragged_seen[k])
+                else:
+                    if k not in self._ragged_caps and k in self._ragged_seen:
+                        self._ragged_caps[k] = ragged_auto_capacity(self._ragged_seen[k])
+                    cap = self._ragged_caps.get(k)
+            else:
+                cap = ragged_capacity_for(policy, k, rows)
+            if ragged_overflows(nnz, cap):
+                fits = False
+                continue
+            if v.values.device.type == "cpu" and self.device.type == "cuda":
+                def fill(buf, vals=v.values, n=nnz):
+                    if n:
+                        _host_copy(buf[:n], vals.contiguous())
+                    buf[n:].fill_(-1)
+                out[k] = Ragged(self._h2d(fill, (cap,), torch.int64), v.offsets)
+            elif loading and v.values.is_cuda:
+                out[k] = v
+            else:
+                out[k] = pad_ragged(v, cap)
+        if not fits:
+            self.ragged_overflows += 1
+            return features, False
+        return out, True
+
+    def _capturable(self, features, fits: bool) -> bool:
+        """May a step over this batch be captured (or replayed)?  Without a ragged capacity: a batch of dense tensors only."""
+        if self.config.ragged_capacity is None:
+            return _static_batch(features)
+        if not fits:
+            return False
+        if self.capture_refused is None and getattr(self.store, "data_dependent", None):
+            self.capture_refused = self.store.data_dependent
+        from .feature_column import Ragged
+        return self.capture_refused is None and all(isinstance(v, (torch.Tensor, Ragged)) for v in features.values())
 
     def _h2d(self, fill, shape, dtype, dst: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Host -> device through a small ring of PERSISTENT pinned staging buffers (one ring per dtype, buffers grow to
@@ -943,27 +1080,37 @@ class Estimator:
                 break
             loss = None
             pb = self._packed_host_batch(features, labels) if graphed is not None else None
+            fits = True
             if pb is not None:
                 host = (features, labels)
                 try:
                     loss = self.feed_step(graphed, features, labels, pb)     # (host batch -> the graph's input span, one copy)
+                    self.graph_replays += 1
                 except BatchShapeMismatch:       # last partial batch: eager step
                     features, labels = self._to_device(*host)
                     loss = self.train_step(features, labels)
             else:
+                # (ragged_capacity: every Ragged padded to its capacity, the eager warm-up steps included)
+                features, fits = self._fit_ragged(features, warm=n < 2, loading=graphed is not None)
                 features, labels = self._to_device(features, labels)
                 self._build(features, labels, ModeKeys.TRAIN)
             # the first two steps run eagerly (they also warm the allocator and hipBLASLt);
             # from the third fixed-shape batch on, the step is one hipGraph replay
             if loss is not None:
                 pass
-            elif self.config.use_hip_graph and _static_batch(features) and n >= 2:
+            elif self.config.use_hip_graph and n >= 2 and self._capturable(features, fits):
                 try:
                     if graphed is None:
                         graphed = GraphedTrainStep(self.train_step, features, labels, warmup=0)
+                        graphed.pad_values = self.config.ragged_capacity is not None
+                        self._ragged_frozen = True
                         loss = graphed()
+                        if log_every and self._ragged_keys:
+                            print(f"[recalgo] step {self.global_step + 1}: training step captured over ragged inputs of fixed "
+                                  f"capacity ({', '.join(sorted(self._ragged_keys))})", flush=True)
                     else:
                         loss = graphed(features, labels)
+                        self.graph_replays += 1
                 except BatchShapeMismatch:       # last partial batch: eager step
                     loss = self.train_step(features, labels)
             else:
@@ -997,8 +1144,9 @@ class Estimator:
     def _evaluate_on_device(self, batches, steps) -> Dict[str, float]:
         """No host synchronisation inside the loop.  With config.use_hip_graph the EVAL step — model_fn under no_grad plus the
         metrics launch, one stream — is captured on the third fixed-shape batch and replayed from then on (GraphedTrainStep's
-        static inputs and one-copy load); a batch of another shape (the last partial one) and every ragged batch run the same
-        step eagerly into the same accumulator.  The graph lives for this call only."""
+        static inputs and one-copy load); a batch of another shape (the last partial one) and, without config.ragged_capacity,
+        every ragged batch run the same step eagerly into the same accumulator; with a capacity every Ragged is padded to it
+        first (_fit_ragged) and only a batch that overflows runs eagerly.  The graph lives for this call only."""
         acc, graphed, n = None, None, 0
 
         def step(features, labels):
@@ -1010,15 +1158,18 @@ class Estimator:
             if steps is not None and i >= steps:
                 break
             pb = self._packed_host_batch(features, labels) if graphed is not None else None
+            fits = True
             if pb is not None:
                 host = (features, labels)
                 try:
                     self.feed_step(graphed, features, labels, pb)     # (host batch -> the graph's input span, one copy)
+                    self.graph_replays += 1
                     n += 1
                     continue
                 except BatchShapeMismatch:       # last partial batch: eager step
                     features, labels = self._to_device(*host)
             else:
+                features, fits = self._fit_ragged(features, warm=n < 2, loading=graphed is not None)
                 features, labels = self._to_device(features, labels)
                 self._build(features, labels, ModeKeys.EVAL)
             if acc is None:
@@ -1028,13 +1179,16 @@ class Estimator:
                     import itertools
                     return self._evaluate_on_host(itertools.chain([(features, labels)], batches), None if steps is None else steps - i)
                 acc.add(spec)
-            elif pb is None and self.config.use_hip_graph and _static_batch(features) and n >= 2:
+            elif pb is None and self.config.use_hip_graph and n >= 2 and self._capturable(features, fits):
                 try:
                     if graphed is None:
                         graphed = GraphedTrainStep(step, features, labels, warmup=0)
+                        graphed.pad_values = self.config.ragged_capacity is not None
+                        self._ragged_frozen = True
                         graphed()
                     else:
                         graphed(features, labels)
+                        self.graph_replays += 1
                 except BatchShapeMismatch:
                     step(features, labels)
             else:

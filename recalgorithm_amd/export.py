@@ -202,10 +202,43 @@ def _columns_by_key(params: dict) -> dict:
     return found
 
 
+def ragged_span_layout(rows: int, F: int, NF: int, caps):
+    """The staging / static-input layout of a bucket of `rows` rows whose model has bags or histories: the dense layout of
+    ServingModel._span_bytes(rows, F, NF), then for every (key, values per row) of `caps`, in that order,
+        offsets int64 [rows + 1] | values int64 [rows * cap]
+    each piece starting on a 16-byte boundary.  -> ({key: (byte offset of offsets, byte offset of values, rows * cap)}, bytes)"""
+    up = lambda n: (int(n) + 15) // 16 * 16
+    at = up(ServingModel._span_bytes(rows, F, NF)[1])
+    pieces = {}
+    for key, cap in caps:
+        off_at = at
+        val_at = off_at + up((rows + 1) * 8)
+        at = val_at + up(max(rows * int(cap), 1) * 8)
+        pieces[key] = (off_at, val_at, rows * int(cap))
+    return pieces, at
+
+
+def _fill_ragged_pieces(host, pieces, bags, rows: int, n: int) -> bool:
+    """Writes the decoded bags of an n-row request into the pieces of a `rows`-row span (numpy uint8 `host`): offsets, the rows
+    past the request as empty bags; values, then -1 up to the capacity.  A bag that does not fit is NOT truncated: every piece
+    is written as empty bags and False is returned."""
+    fits = all(int(bags[key][0][n]) <= cap for key, (_, _, cap) in pieces.items())
+    for key, (off_at, val_at, cap) in pieces.items():
+        offsets, values = bags[key]
+        o = host[off_at:off_at + (rows + 1) * 8].view(np.int64)
+        v = host[val_at:val_at + cap * 8].view(np.int64)
+        nnz = int(offsets[n]) if fits else 0
+        o[:n + 1] = offsets[:n + 1] if fits else 0
+        o[n + 1:] = nnz
+        v[:nnz] = values[:nnz]
+        v[nnz:] = -1
+    return fits
+
+
 class _Bucket:
-    """One captured PREDICT graph: its static input span (ids, then floats: the staging layout), the feature views over it, the
-    static outputs, and the serving plan whose BatchNorm folds the captured tower reads."""
-    __slots__ = ("rows", "span", "features", "graph", "out", "tower", "plan")
+    """One captured PREDICT graph: its static input span (ids, then floats, then the ragged pieces: the staging layout), the
+    feature views over it, the static outputs, and the serving plan whose BatchNorm folds the captured tower reads."""
+    __slots__ = ("rows", "span", "features", "graph", "out", "tower", "plan", "caps")
 
 
 class ServingModel:
@@ -234,6 +267,9 @@ class ServingModel:
         self._learned_bags: set = set()       # keys not declared as sequences that a request showed to hold several values
         self._buckets: Dict[int, _Bucket] = {}
         self.graphs_dropped_by: Optional[str] = None     # the feature whose several values made serve() drop the compiled graphs
+        self.ragged_overflows = 0             # chunks whose decoded bags exceeded their bucket's capacity: served eagerly
+        self._compiled_with: Optional[dict] = None       # compile()'s arguments
+        self._recompile = False               # a request showed a new bag that the compiled ragged capacity serves
 
     @property
     def compiled_buckets(self) -> List[int]:
@@ -281,7 +317,7 @@ class ServingModel:
 
     def ragged_keys(self) -> List[str]:
         """The features that reach the model as a Ragged (bags, histories): declared sequences, and keys a request showed to
-        hold several values.  A model with any is served eagerly: compile() refuses it."""
+        hold several values.  A model with any is compiled only with compile(ragged_capacity=); without it, it is served eagerly."""
         return [k for k, _ in self._layout()[1]]
 
     def _open_decoder(self):
@@ -299,8 +335,9 @@ class ServingModel:
         id_bytes = (rows * F * 8 + 15) // 16 * 16
         return id_bytes, id_bytes + max(rows * NF * 4, 16)
 
-    def _views(self, span, rows: int):
-        """the feature dict over a uint8 span of that layout (host or device): id columns of one matrix, float blocks of another"""
+    def _views(self, span, rows: int, caps=None):
+        """the feature dict over a uint8 span of that layout (host or device): id columns of one matrix, float blocks of another;
+        `caps` (ragged_span_layout): a Ragged of fixed capacity per bag / history key"""
         import torch
         _, ids, _, floats = self._open_decoder()
         F, NF = len(ids), sum(n for _, _, n, _ in floats)
@@ -315,12 +352,18 @@ class ServingModel:
             for k, shape, n, _ in floats:
                 feats[k] = fmat[:, off:off + n].view((rows,) + shape)
                 off += n
+        if caps:
+            from .feature_column import Ragged
+            for k, (off_at, val_at, cap) in ragged_span_layout(rows, F, NF, caps)[0].items():
+                feats[k] = Ragged(span[val_at:val_at + cap * 8].view(torch.int64), span[off_at:off_at + (rows + 1) * 8].view(torch.int64))
         return feats
 
-    def _decode_to(self, records, rows: int, dst=None):
+    def _decode_to(self, records, rows: int, dst=None, caps=None):
         """Decodes `records` (at most `rows`) into pinned staging of the `rows`-row layout — the rows past the request padded with
         id -1 / 0.0 — and moves it with ONE copy: into `dst` (a bucket's static span), or to a new device span.
-        -> (device span, {bag key: (offsets, values)})"""
+        -> (device span, {bag key: (offsets, values)})
+        `caps` (a bucket compiled with a ragged capacity): the bags go into the span's ragged pieces too, the rows past the
+        request as empty bags; a bag that does not fit leaves them empty and the returned dict holds "__overflow__": True."""
         import torch
         from .io.native import SeveralValues
         est = self.estimator
@@ -328,15 +371,20 @@ class ServingModel:
             dec, ids, bags, floats = self._open_decoder()
             F, NF, n = len(ids), sum(k[2] for k in floats), len(records)
             id_bytes, total = self._span_bytes(rows, F, NF)
+            pieces = None
+            if caps:
+                pieces, total = ragged_span_layout(rows, F, NF, caps)
             got = {}
 
-            def fill(buf, dec=dec, F=F, NF=NF, n=n, id_bytes=id_bytes):
+            def fill(buf, dec=dec, F=F, NF=NF, n=n, id_bytes=id_bytes, pieces=pieces):
                 host = buf.numpy()
                 mat = host[:rows * F * 8].view(np.int64).reshape(rows, F)
                 fmat = host[id_bytes:id_bytes + rows * NF * 4].view(np.float32).reshape(rows, NF)
                 got["bags"] = dec.decode(records, ids=mat[:n], floats=fmat[:n], threads=self.DECODE_THREADS if n >= 256 else 0)[2]
                 mat[n:] = -1
                 fmat[n:] = 0.0
+                if pieces and not _fill_ragged_pieces(host, pieces, got["bags"], rows, n):
+                    got["bags"] = dict(got["bags"], __overflow__=True)
             try:
                 if est.device.type != "cuda":
                     buf = torch.empty(total, dtype=torch.uint8)
@@ -351,7 +399,11 @@ class ServingModel:
                 import warnings
                 self._learned_bags.add(e.key)
                 self._decoder = None
-                if self._buckets:
+                cap = (self._compiled_with or {}).get("ragged_capacity")
+                if self._buckets and cap is not None and (not isinstance(cap, dict) or e.key in cap):
+                    # compiled with a ragged capacity that serves this key: serve() captures the buckets again, the key a bag
+                    self._buckets, self._recompile = {}, True
+                elif self._buckets:
                     warnings.warn(f"serve: feature {e.key!r} holds several values in a record; the compiled graphs are dropped "
                                   "and requests are served eagerly")
                     self._buckets, self.graphs_dropped_by = {}, e.key
@@ -378,23 +430,47 @@ class ServingModel:
     def serve(self, serialized_examples: Sequence[bytes]) -> Dict[str, np.ndarray]:
         """predict()'s contract on the native decoder: the compiled graph of the request's bucket when compile() has run (a
         request larger than the largest bucket in chunks), the eager PREDICT model_fn otherwise."""
-        import torch
-        from .estimator import ModeKeys
         records = list(serialized_examples)
         n = len(records)
-        if self._buckets and n > 0:
-            parts = []
-            for at, rows, size in plan_chunks(n, list(self._buckets)):
-                if not self._buckets:             # (a request that turned a column into a bag dropped the graphs)
-                    break
-                b = self._buckets[size]
-                self._decode_to(records[at:at + rows], size, dst=b.span)
-                if not self._buckets:
-                    break
-                b.graph.replay()
-                parts.append({k: v[:rows].cpu().numpy() for k, v in b.out.items()})
-            else:
-                return {k: (np.concatenate([p[k] for p in parts]) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+        while n > 0:
+            if self._recompile:
+                # a column showed several values for the first time and compile() was given a capacity that serves it: the
+                # buckets are captured again with the column as a bag (once per such column, not per request)
+                self._recompile = False
+                self.compile(**self._compiled_with)
+            if not self._buckets:
+                break
+            out = self._serve_compiled(records)
+            if out is not None:
+                return out
+            if not self._recompile:
+                break
+        return self._serve_eager(records)
+
+    def _serve_compiled(self, records):
+        """the request through the captured graphs, or None when decoding it dropped them"""
+        parts = []
+        for at, rows, size in plan_chunks(len(records), list(self._buckets)):
+            if not self._buckets:                 # (a request that turned a column into a bag dropped the graphs)
+                return None
+            b = self._buckets[size]
+            _, bags = self._decode_to(records[at:at + rows], size, dst=b.span, caps=b.caps)
+            if not self._buckets:
+                return None
+            if bags.get("__overflow__"):
+                # a bag larger than the bucket's capacity is never truncated: this chunk runs eagerly (the same kernels)
+                self.ragged_overflows += 1
+                parts.append(self._serve_eager(records[at:at + rows]))
+                continue
+            b.graph.replay()
+            parts.append({k: v[:rows].cpu().numpy() for k, v in b.out.items()})
+        return {k: (np.concatenate([p[k] for p in parts]) if len(parts) > 1 else parts[0][k]) for k in parts[0]}
+
+    def _serve_eager(self, records) -> Dict[str, np.ndarray]:
+        """native decode, then the eager PREDICT model_fn"""
+        import torch
+        from .estimator import ModeKeys
+        n = len(records)
         with torch.no_grad():
             span, bags = self._decode_to(records, n)
             features = self._views(span, n)
@@ -403,13 +479,41 @@ class ServingModel:
             spec = self.estimator._call_model_fn(features, None, ModeKeys.PREDICT)
         return {k: v.detach().cpu().numpy() for k, v in spec.predictions.items()}
 
-    def compile(self, batch_sizes: Sequence[int] = (1, 16, 64, 256, 1024, 4096), warmup: int = 2) -> "ServingModel":
+    def _ragged_caps(self, ragged_capacity):
+        """[(bag / history key, values per row)] in decoder order for compile(ragged_capacity=): an int for every key, or a dict
+        that names each.  A history additionally needs a static number of steps: NotImplementedError names the parameter."""
+        from .estimator import check_ragged_capacity
+        policy = check_ragged_capacity(ragged_capacity)
+        if policy == "auto":
+            raise ValueError("compile: ragged_capacity is an int or a dict of values per row (serving sees no warm-up batches "
+                             "to size 'auto' from)")
+        _, _, bags, _ = self._open_decoder()
+        params = self.estimator.params
+        if any(c.is_sequence for _, c in bags):
+            static_T = params.get("static_sequence_length") if "static_sequence_length" in params else params.get("sequence_max_length")
+            if not static_T:
+                name = "static_sequence_length" if "static_sequence_length" in params else "sequence_max_length"
+                raise NotImplementedError(f"compile: a model with a history needs a static number of steps: set params[{name!r}] "
+                                          "(sequence_max_length: DIN, DIEN; static_sequence_length: BST)")
+        caps = []
+        for key, _ in bags:
+            cap = policy.get(key) if isinstance(policy, dict) else policy
+            if cap is None:
+                raise ValueError(f"compile: ragged_capacity names no capacity for the ragged feature {key!r}")
+            caps.append((key, int(cap)))
+        return caps
+
+    def compile(self, batch_sizes: Sequence[int] = (1, 16, 64, 256, 1024, 4096), warmup: int = 2,
+                ragged_capacity=None) -> "ServingModel":
         """Captures the PREDICT model_fn once per bucket size into a torch.cuda.CUDAGraph over private static inputs (one stream,
         no forked branch; warm-up on a side stream, then capture_error_mode="thread_local", as estimator.GraphedTrainStep).
         Under the capture the VariableStore's serving switch is on: buckets of at most nn.SERVE_TOWER_MAX_ROWS rows run their
         hidden stack as ONE launch with the BatchNorms folded (nn.LazyTower); the folds are computed here, once.
-        A model whose decoded features contain a Ragged is not compiled: NotImplementedError names the keys; serve() still
-        serves it (native decode, eager model_fn)."""
+        A model whose decoded features contain a Ragged (a bag, a history) is compiled only with `ragged_capacity`, values per row
+        as an int or a dict key -> int: a bucket's span then holds offsets [rows + 1] and values [rows * capacity] per such key
+        (ragged_span_layout), and a chunk whose bags do not fit is served eagerly (ragged_overflows).  Without it
+        NotImplementedError names the keys; serve() still serves the model (native decode, eager model_fn).  A model whose
+        launches depend on the request's data even then (a history without a static length) is refused the same way."""
         import torch
         from . import nn
         from .estimator import ModeKeys
@@ -418,9 +522,11 @@ class ServingModel:
         if not sizes or sizes[0] < 1:
             raise ValueError(f"compile: batch_sizes must be positive, got {list(batch_sizes)}")
         ragged = self.ragged_keys()
-        if ragged:
-            raise NotImplementedError("compile: the decoded features " + ", ".join(ragged) + " are ragged (bags / histories); graphs "
-                                      "over fixed-capacity ragged buffers are not built yet — serve() serves this model eagerly")
+        if ragged and ragged_capacity is None:
+            raise NotImplementedError("compile: the decoded features " + ", ".join(ragged) + " are ragged (bags / histories); pass "
+                                      "ragged_capacity= (values per row) to capture graphs over fixed-capacity buffers — serve() "
+                                      "serves this model eagerly")
+        caps = self._ragged_caps(ragged_capacity)
         if est.device.type != "cuda":
             raise RuntimeError("compile: captured graphs need a HIP device")
         _, ids, _, floats = self._open_decoder()
@@ -430,12 +536,16 @@ class ServingModel:
         with torch.no_grad():
             for size in sizes:
                 b = _Bucket()
-                b.rows = size
-                b.span = torch.zeros(self._span_bytes(size, F, NF)[1], dtype=torch.uint8, device=est.device)
-                b.features = self._views(b.span, size)
+                b.rows, b.caps = size, caps
+                total = ragged_span_layout(size, F, NF, caps)[1] if caps else self._span_bytes(size, F, NF)[1]
+                b.span = torch.zeros(total, dtype=torch.uint8, device=est.device)
+                b.features = self._views(b.span, size, caps)
                 if F:
                     b.span[:size * F * 8].view(torch.int64).fill_(-1)          # (a bucket of padding rows: id -1, 0.0)
+                for k, _ in caps or ():
+                    b.features[k].values.fill_(-1)                            # (... and empty bags: offsets 0, values -1)
                 self._ensure_loaded(b.features)
+                est.store.data_dependent = None
                 if folds is None:
                     folds = fold_batch_norms(est.store.named_arrays())
                 plan = nn.ServingPlan(nn.SERVE_TOWER_MAX_ROWS, folds, nn.BN_EPSILON)
@@ -453,6 +563,8 @@ class ServingModel:
                         run()
                 torch.cuda.current_stream().wait_stream(side)
                 torch.cuda.synchronize()
+                if caps and est.store.data_dependent:    # (said by the warm-up runs: never found out inside a capture)
+                    raise NotImplementedError(f"compile: the model is not capturable over ragged inputs: {est.store.data_dependent}")
                 b.graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(b.graph, capture_error_mode="thread_local"):
                     b.out = run()
@@ -460,4 +572,5 @@ class ServingModel:
                 b.plan = plan                     # (the captured launches read the folds: they live as long as the graph)
                 buckets[size] = b
         self._buckets = buckets
+        self._compiled_with = dict(batch_sizes=tuple(sizes), warmup=warmup, ragged_capacity=ragged_capacity)
         return self

@@ -24,6 +24,40 @@ from . import ops, sparse
 from .variables import EmbeddingArena, current_store, truncated_normal
 
 Ragged = namedtuple("Ragged", ["values", "offsets"])   # int64 [nnz], int64 [B+1]
+# A Ragged PADDED to a capacity (pad_ragged) keeps shapes fixed from batch to batch, so that a step over bags and histories
+# can be captured:
+#     values   has exactly `capacity` entries; those from offsets[-1] on are -1
+#     offsets  unchanged: [B+1], offsets[-1] = nnz <= capacity
+# Every consumer reads `values` through `offsets` (or treats an id < 0 as "no row"), so a padded Ragged gives the same result
+# as the unpadded one — on the device the same bits.  A consumer whose shapes depend on the data cannot be captured either
+# way; it says so through `data_dependent(reason)` and the Estimator keeps such a model eager.
+
+
+def pad_ragged(r: Ragged, capacity: int) -> Ragged:
+    """`r` with `values` padded with -1 to exactly `capacity` entries (host: a copy; device: one launch, no synchronisation).
+    A Ragged that already has that many values is returned as it is.  Never truncates: more than `capacity` values raise."""
+    capacity = int(capacity)
+    vals = r.values
+    if vals.numel() == capacity:
+        return r
+    if vals.device.type == "cpu":
+        nnz = int(r.offsets[-1]) if r.offsets.numel() else 0
+        if nnz > capacity:
+            raise ValueError(f"pad_ragged: {nnz} values do not fit a capacity of {capacity}")
+        out = torch.full((capacity,), -1, dtype=torch.int64)
+        out[:nnz] = vals[:nnz]
+        return Ragged(out, r.offsets)
+    if vals.numel() > capacity:                # (offsets[-1] is not read back on the device: the buffer itself has to fit)
+        raise ValueError(f"pad_ragged: {vals.numel()} values do not fit a capacity of {capacity}")
+    return Ragged(ops.ragged_pad(vals.contiguous(), capacity), r.offsets)
+
+
+def data_dependent(reason: str) -> None:
+    """Called by a consumer of a Ragged whose shapes or launches depend on the batch's data: the current store keeps the first
+    reason, and the Estimator does not capture a step of such a model (Estimator.capture_refused)."""
+    store = current_store()
+    if getattr(store, "data_dependent", None) is None:
+        store.data_dependent = reason
 
 _VOCAB_CACHE: Dict[str, Dict[bytes, int]] = {}
 
@@ -360,10 +394,12 @@ def input_layer(features, feature_columns, _layer_name: Optional[str] = None) ->
             V = c.categorical_column.num_buckets
             mh = torch.zeros(B, V, device=dev)
             if isinstance(ids, Ragged):
+                data_dependent(f"input_layer: the multi-hot of {c.name} is built from a Ragged")
                 lens = ids.offsets[1:] - ids.offsets[:-1]
                 rows = torch.repeat_interleave(torch.arange(B, device=dev), lens)
-                ok = ids.values >= 0
-                mh.index_put_((rows[ok], ids.values[ok]), torch.ones(int(ok.sum()), device=dev), accumulate=True)
+                vals = ids.values[:rows.numel()]             # (a padded Ragged: the -1 tail belongs to no row)
+                ok = vals >= 0
+                mh.index_put_((rows[ok], vals[ok]), torch.ones(int(ok.sum()), device=dev), accumulate=True)
             else:
                 ok = ids >= 0
                 mh[torch.arange(B, device=dev)[ok], ids[ok]] = 1.0
@@ -446,8 +482,12 @@ def sequence_input_layer(features, feature_columns, max_length: Optional[int] = 
             B = ids.numel()
             ids = Ragged(ids.contiguous(), _unit_offsets(B, dev))
             T = 1
+        elif max_length:
+            T = max_length
         else:
-            T = max_length or max(int((ids.offsets[1:] - ids.offsets[:-1]).max().item()), 1)
+            data_dependent("sequence_input_layer: max_length is None (a static T: params['sequence_max_length']; BST: "
+                           "params['static_sequence_length'])")
+            T = max(int((ids.offsets[1:] - ids.offsets[:-1]).max().item()), 1)
         o, l = ops.sequence_gather(store, ids.values, ids.offsets, ar, tname, T)
         outs.append(o)
         lens = l

@@ -138,6 +138,9 @@ def _staged(arena, rows: torch.Tensor, store=None):
     if sd is None:
         return None
     from . import parallel
+    if store is not None and getattr(store, "data_dependent", None) is None and rows.dim() == 1:
+        # (a bag or a history looked up in a row-sharded arena: the exchange plan is made from the batch's rows)
+        store.data_dependent = "a row-sharded arena stages a ragged lookup's rows per batch (ops._staged)"
     plan = sd.plan(rows)
     return plan, parallel.StagedArena(plan, arena, store, torch.is_grad_enabled()), plan.staged_ids(rows, rows.shape)
 
@@ -302,17 +305,53 @@ class _BagMeanFn(Function):
         rb, vocab = arena.tables[table_name]
         g = g.contiguous()
         if ctx.src is not None:
-            # bag of every entry = the number of bag ends at or before it (what repeat_interleave(arange(B), lens) lists, without
-            # its host synchronisation: a step with a bag lookup captures into a hipGraph)
-            bag = torch.searchsorted(offsets[1:], torch.arange(values.numel(), device=values.device), right=True).clamp_(max=B - 1)
-            cnt = torch.zeros(B, device=values.device).index_add_(0, bag, (values >= 0).float()).clamp_(min=1.0)
-            ctx.src.set_grad(g[bag] / cnt[bag].unsqueeze(1))
+            # one request per bag entry: its gradient row g[bag] / count, one launch, the bag found on the device (no host
+            # synchronisation: a step with a bag lookup captures into a hipGraph)
+            ctx.src.set_grad(bag_mean_grad_rows(values, offsets, g))
             return None, None, None, None, None, None
         gt = arena.grad[rb:rb + vocab]
         _lib_().recalgo_embedding_bag_mean_bwd(
             _p(values), _p(offsets), _p(g), B, arena.K, arena.K, 0, _p(gt), _live(arena, rb), _stream(offsets))
         _flush(arena)
         return None, None, None, None, None, None
+
+
+def bag_mean_grad_rows(values: torch.Tensor, offsets: torch.Tensor, g: torch.Tensor, g_col: int = 0, K: Optional[int] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """rows [len(values), K]: rows[j] = g[bag of j, g_col : g_col + K] / (valid values of that bag) for an entry j below
+    offsets[-1] with values[j] >= 0, zeros for every other row — OOV entries and the -1 tail of a padded Ragged
+    (recalgo_bag_mean_grad_rows, include/recalgo_ragged.h).  g: [B, >= g_col + K] fp32 with a contiguous last dimension."""
+    _chk(values, torch.int64, "values")
+    _chk(offsets, torch.int64, "offsets")
+    B = offsets.numel() - 1
+    if g.dtype != torch.float32 or g.dim() != 2 or g.shape[0] != B or (g.shape[1] > 1 and g.stride(1) != 1):
+        raise ValueError(f"bag_mean_grad_rows: g must be fp32 [B = {B}, C] with a contiguous last dimension, got {tuple(g.shape)} {g.dtype}")
+    K = g.shape[1] - g_col if K is None else int(K)
+    stride = int(g.stride(0)) if B > 1 else int(g.shape[1])
+    rows = torch.empty(values.numel(), K, device=values.device, dtype=torch.float32) if out is None else out
+    if out is not None:
+        _chk(out, torch.float32, "out")
+        if tuple(out.shape) != (values.numel(), K):
+            raise ValueError("bag_mean_grad_rows: out must be [len(values), K]")
+    _lib_().recalgo_bag_mean_grad_rows(_p(values), _p(offsets), B, values.numel(), _p(g), stride, int(g_col), K, _p(rows),
+                                       _stream(offsets))
+    return rows
+
+
+def ragged_pad(values: torch.Tensor, capacity: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [capacity]: `values` followed by -1 up to the capacity, one launch (recalgo_ragged_pad); `out`: an existing
+    buffer of that size — a captured step's static `values`."""
+    _chk(values, torch.int64, "values")
+    n, capacity = values.numel(), int(capacity)
+    if n > capacity:
+        raise ValueError(f"ragged_pad: {n} values do not fit a capacity of {capacity}")
+    dst = torch.empty(capacity, device=values.device, dtype=torch.int64) if out is None else out
+    if out is not None:
+        _chk(out, torch.int64, "out")
+        if out.numel() != capacity or out.device != values.device:
+            raise ValueError("ragged_pad: out must hold exactly `capacity` int64 values on the device of `values`")
+    _lib_().recalgo_ragged_pad(_p(values) if n else None, n, _p(dst), capacity, _stream(dst))
+    return dst
 
 
 def embedding_bag_mean(store, values, offsets, arena, table_name) -> torch.Tensor:

@@ -102,6 +102,9 @@ class VariableStore:
         self.building = False
         self.shared_tables: Dict[tuple, str] = {}
         self.opt_state = None            # device-side Adam step counter / lr_t (estimator.py)
+        # why a step of this model cannot be captured over ragged inputs: set by a consumer of a Ragged whose shapes or launches
+        # depend on the data (feature_column.sequence_input_layer without max_length, ..); the Estimator reads it and stays eager
+        self.data_dependent: Optional[str] = None
         self._drop_calls = 0             # training-mode dropout calls of the current model_fn invocation (nn.dropout)
         self._rb_cache: Dict[tuple, torch.Tensor] = {}
         # the serving switch, off by default: only export.ServingModel.compile sets it (an nn.ServingPlan), around the PREDICT
