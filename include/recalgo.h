@@ -16,6 +16,12 @@
  *   - no hidden allocation: outputs and workspaces are caller-owned; required workspace
  *     sizes are given by the matching *_workspace_bytes() query.
  *   - nothing is read or written outside the extents documented per argument.
+ *   - a call outside the domain stated per entry returns hipErrorInvalidValue before anything is launched or written.  The
+ *     limits stated here are the ones the entry points check (tests/domain.py holds the two against each other, per check).
+ *   - B == 0: an entry that takes B >= 0 (every forward, and the backwards that only add into caller-owned gradients)
+ *     returns 0 and writes nothing.  The backwards that OVERWRITE parameter gradients by a two-pass sum (cross, cross_layer,
+ *     CIN, DIN attention, SENET, bilinear) require B > 0 and refuse B == 0: there is no partial row to sum.
+ *   - "LDS" below is a gfx950 workgroup's 160 KiB (163840 bytes); 64 KiB where a kernel does not opt in to more.
  *   - one environment knob, read once per process: RECALGO_SCATTER_TILE=32|64|128|256 overrides the
  *     examples-per-workgroup tile of the row-gradient scatter kernels (a tuning aid; results are the same).
  *
@@ -43,7 +49,9 @@ int recalgo_abi_version(void);
 const char* recalgo_target_arch(void);
 
 /* ------------------------------------------------------------------------------------------
- * K1  embedding gather, single-valued fields, uniform width K (K % 4 == 0).
+ * K1  embedding gather, single-valued fields, uniform width K >= 1 (float4 copies when K, out_stride and out_col are all
+ * multiples of 4, element-wise otherwise: K = 1, 2, 3 serve the first-order weights).  F >= 1, out_stride >= out_col + F*K,
+ * B * F * K / (4 | 1) < 2^31.
  * Replaces fc.embedding_column + fc.input_layer (TF safe_embedding_lookup_sparse) for
  * single-valued categorical columns: algorithm/DeepFM/deepfm.py:83-93,187-190;
  * algorithm/DCN/dcn.py:97-107,152-153; algorithm/xDeepFM/xdeepfm.py:102-112,157-158;
@@ -70,7 +78,8 @@ typedef struct {
 
 /* Backward of K1 (TF autodiff of the lookup; SURVEY.md Appendix D "Gather"):
  *   grad_arena[row_base[f] + ids[b,f], :] += g[b, out_col + f*K : +K]   for ids[b,f] >= 0
- * Duplicate ids accumulate (fp32 hardware atomics; order-nondeterministic in the last ulp). */
+ * Duplicate ids accumulate (fp32 hardware atomics; order-nondeterministic in the last ulp).
+ * 1 <= K <= 64 (a workgroup combines its items' rows in LDS first), F >= 1, g_stride >= g_col + F*K. */
 int recalgo_embedding_gather_bwd(const int64_t* ids, const float* g, const int64_t* row_base,
                                  int B, int F, int K, int g_stride, int g_col, float* grad_arena,
                                  const recalgo_live_t* live, recalgo_stream_t stream);
@@ -80,7 +89,8 @@ int recalgo_embedding_gather_bwd(const int64_t* ids, const float* g, const int64
  *   grad[sorted_rows[i], :] += vals[perm[i], :]   for sorted_rows[i] >= 0
  * sorted_rows [M] ascending (a STABLE sort of the lookup's arena rows, -1 = OOV first), perm [M] the sort's
  * permutation, vals [M, K] the per-item row gradients.  Each row is summed in item order by one thread group and
- * written by a plain read-modify-write: no atomics, bit-identical from run to run. */
+ * written by a plain read-modify-write: no atomics, bit-identical from run to run.
+ * M >= 0 (M == 0: returns 0, no pointer is looked at), K >= 1, M * K <= 256 * (2^31 - 1). */
 int recalgo_scatter_rows_sorted(const int64_t* sorted_rows, const int64_t* perm, const float* vals, int64_t M, int K,
                                 float* grad, recalgo_stream_t stream);
 
@@ -92,6 +102,7 @@ int recalgo_scatter_rows_sorted(const int64_t* sorted_rows, const int64_t* perm,
  *   values [nnz] int64, offsets [B+1] int64, table = arena + row_base*K.
  * The sum runs sequentially in bag order in fp32 (TF SparseSegmentMean order).  The forward is
  * recalgo_embedding_bag_mean_fwd_deferred (with deferred = NULL: the plain lookup).
+ * Backward: 1 <= K <= 64, g_stride >= g_col + K.
  * ------------------------------------------------------------------------------------------ */
 int recalgo_embedding_bag_mean_bwd(const int64_t* values, const int64_t* offsets, const float* g,
                                    int B, int K, int g_stride, int g_col, float* grad_table,
@@ -102,6 +113,7 @@ int recalgo_embedding_bag_mean_bwd(const int64_t* values, const int64_t* offsets
  * Replaces tf.contrib.feature_column.sequence_input_layer: algorithm/DIN/din.py:207-214.
  *   out[b, t, :] = t < len(b) && values[offsets[b]+t] >= 0 ? table[value,:] : 0, t < T
  *   seq_len[b]   = min(offsets[b+1]-offsets[b], T)           (int32; counts OOV entries)
+ * T >= 1, K >= 1; forward: B * T * K / (4 | 1) < 2^31 (4 when K % 4 == 0); backward: K <= 64, B * T < 2^31.
  * ------------------------------------------------------------------------------------------ */
 int recalgo_sequence_gather_fwd(const int64_t* values, const int64_t* offsets, const float* table,
                                 int B, int T, int K, float* out, int32_t* seq_len,
@@ -119,7 +131,8 @@ int recalgo_sequence_gather_bwd(const int64_t* values, const int64_t* offsets, c
  *   fm2[b] = 0.5 * sum_k ( (sum_f e_fk)^2 - sum_f e_fk^2 )
  *   field_sum[b, :] = sum_f e_f   ([B, K]; saved for the backward)
  *   w1 [rows] fp32 (the (sum V,1) dense kernel of `fm_first_order_dense`), bias [1].
- * K % 4 == 0, K <= 64.
+ * K % 4 == 0, 4 <= K <= 64, F >= 1; field_sum is required.  The forward keeps four examples' rows in 64 KiB of LDS:
+ * 16 * (F*K + 16 + F) <= 65536 bytes, i.e. F * (K + 1) <= 4080 (F <= 816 at K = 4, F <= 62 at K = 64).
  * ------------------------------------------------------------------------------------------ */
 int recalgo_deepfm_sparse_fwd(const int64_t* ids, const float* arena, const float* w1,
                               const float* bias, const int64_t* row_base, int B, int F, int K,
@@ -143,15 +156,16 @@ int recalgo_deepfm_sparse_bwd(const int64_t* ids, const float* emb, const float*
  *   x0 [B, d] (row stride x_stride), w [L, d], b [L, d], out [B, d] (row stride out_stride).
  * Evaluated through the stack's closed form  x_l = c_l*x0 + B_l,  c_{l+1} = c_l*(1 + x0.w_l) +
  * B_l.w_l,  B_l = sum_{j<l} b_j  (identical math, one batched reduction per example).
- * d % 4 == 0, d <= 1024, 1 <= L <= 6  (beyond: chain recalgo_cross_layer_fwd).
+ * d % 4 == 0, 4 <= d <= 1024, 1 <= L <= 6  (beyond: chain recalgo_cross_layer_fwd); every row stride % 4 == 0 and >= d.
+ * recalgo_cross_bwd: B > 0.
  * ------------------------------------------------------------------------------------------ */
 int recalgo_cross_fwd(const float* x0, int x_stride, const float* w, const float* b, int B, int d,
                       int L, float* out, int out_stride, recalgo_stream_t stream);
 /* recalgo_embedding_gather_fwd + recalgo_cross_fwd in ONE launch (fc.input_layer over F single-valued embedding columns of one
  * width K feeding the cross network, dcn.py:152-160): the wave that computes an example's stack gathers the example's row from
  * the arena itself — x0 [B, F*K] is an OUTPUT here (bit-exact copy of the table rows, id < 0: zeros; the MLP branch and the
- * backward read it), out as recalgo_cross_fwd.  K % 4 == 0, F * K <= 1024; arena rows already current (a TRAIN lookup's
- * recalgo_scatter_prepare ran before). */
+ * backward read it), out as recalgo_cross_fwd.  K % 4 == 0, K >= 4, F >= 1, F * K <= 1024; arena and x0 16-byte aligned; no
+ * pointer NULL; arena rows already current (a TRAIN lookup's recalgo_scatter_prepare ran before). */
 int recalgo_gather_cross_fwd(const int64_t* ids, const float* arena, const int64_t* row_base, int B, int F, int K,
                              const float* w, const float* b, int L, float* x0, int x_stride, float* out, int out_stride,
                              recalgo_stream_t stream);
@@ -170,7 +184,8 @@ int64_t recalgo_cross_bwd_workspace_bytes(int B, int d, int L);
 int recalgo_cross_bwd_partial_rows(int B);
 /* Single layer with the reference's exact signature cross_layer(x0, xl, index)
  * (algorithm/DCN/cross_layer.py:4): out = x0 * (xl . w) + b + xl, xl distinct from x0.
- * w, b [d].  Backward also returns dxl; workspace as recalgo_cross_bwd_workspace_bytes(B,d,1). */
+ * w, b [d].  Backward also returns dxl; workspace as recalgo_cross_bwd_workspace_bytes(B,d,1).
+ * d % 4 == 0, 4 <= d <= 2048 (eight float4 per lane of the example's wave); row strides % 4 == 0 and >= d; backward: B > 0. */
 int recalgo_cross_layer_fwd(const float* x0, const float* xl, int x_stride, const float* w,
                             const float* b, int B, int d, float* out, int out_stride,
                             recalgo_stream_t stream);
@@ -189,7 +204,7 @@ int recalgo_cross_bwd(const float* x0, int x_stride, const float* w, const float
  *   out[b, n, d]  = sum_{i<Hk} sum_{j<m} filters[i*m + j, n] * xk[b, i, d] * x0[b, j, d]
  *   pool[b, pool_col + n] = sum_d out[b, n, d]          (row stride pool_stride; pool may be NULL)
  *   x0 [B, m, D], xk [B, Hk, D], filters [Hk*m, N] (the reference's (1, Hk*m, N) variable),
- *   out [B, N, D].   D in {4, 8, 16, 32}; N <= 128.  No bias, no activation (quirk B-8).
+ *   out [B, N, D].   D in {4, 8, 16, 32}; 1 <= N <= 128; m, Hk >= 1.  No bias, no activation (quirk B-8).
  * ------------------------------------------------------------------------------------------ */
 int recalgo_cin_layer_fwd(const float* x0, const float* xk, const float* filters, int B, int m,
                           int Hk, int N, int D, float* out, float* pool, int pool_stride,
@@ -199,7 +214,8 @@ int recalgo_cin_layer_fwd(const float* x0, const float* xk, const float* filters
  *   dxk[b,i,d] (=|+=) sum_{j,n} W[(i,j),n] x0[b,j,d] G[b,n,d]      (dxk may be NULL)
  *   dx0[b,j,d] (=|+=) sum_{i,n} W[(i,j),n] xk[b,i,d] G[b,n,d]
  *   dfilters[(i,j),n] = sum_{b,d} xk[b,i,d] x0[b,j,d] G[b,n,d]     (overwritten, deterministic)
- * m, Hk, N <= 128, m >= 4.  workspace: recalgo_cin_layer_bwd_workspace_bytes(). */
+ * B > 0; 4 <= m <= 128, 1 <= Hk <= 128, 1 <= N <= 128, D as the forward; g_out and g_pool not both NULL.
+ * workspace: recalgo_cin_layer_bwd_workspace_bytes(). */
 int64_t recalgo_cin_layer_bwd_workspace_bytes(int B, int m, int Hk, int N, int D);
 int recalgo_cin_layer_bwd(const float* x0, const float* xk, const float* filters, const float* g_out,
                           const float* g_pool, int pool_stride, int pool_col, int B, int m, int Hk,
@@ -226,7 +242,8 @@ int recalgo_din_attention_fwd(const float* query, const float* keys, const int32
  * workspace: recalgo_din_attention_bwd_workspace_bytes(B, T, H).  d_f1_w == NULL: the second pass is left to the caller —
  * the workspace then holds recalgo_din_attention_bwd_partial_rows(B) rows of recalgo_din_attention_bwd_partial_floats(H)
  * floats laid out [d_f1_w | d_f1_b | d_f2_w | d_f2_b | d_f3_w | d_f3_b], to be summed column-wise in row order (e.g. as
- * jobs of recalgo_dense_bwd_weights_reduce, the step's deferred-sum launch). */
+ * jobs of recalgo_dense_bwd_weights_reduce, the step's deferred-sum launch).
+ * B > 0, 1 <= T <= 64, H in {4, 8, 16}; g_out 16-byte aligned; workspace required. */
 int64_t recalgo_din_attention_bwd_workspace_bytes(int B, int T, int H);
 int recalgo_din_attention_bwd_partial_rows(int B);
 int recalgo_din_attention_bwd_partial_floats(int H);
@@ -240,7 +257,7 @@ int recalgo_din_attention_bwd(const float* query, const float* keys, const int32
 /* The same backward reading g_out with a row stride (ldg floats, a multiple of 4, rows 16-byte aligned: the attention output's
  * column block of a wider gradient matrix, in place) and adding dq_extra [B][ld_extra] (or NULL) to dquery — the gradient the
  * query's OTHER consumer produced (din.py:240-249: the target embedding feeds the attention and the fcn input), instead of a
- * slice copy and an add launch. */
+ * slice copy and an add launch.  ldg >= H; ld_extra >= H when dq_extra is given. */
 int recalgo_din_attention_bwd_joined(const float* query, const float* keys, const int32_t* keys_length, const float* f1_w,
                                      const float* f1_b, const float* f2_w, const float* f2_b, const float* f3_w,
                                      const float* f3_b, const float* g_out, int ldg, const float* dq_extra, int ld_extra, int B,
@@ -254,7 +271,10 @@ int recalgo_din_attention_bwd_joined(const float* query, const float* keys, cons
  *   z = mean_k(emb);  a = relu(relu(z @ w1) @ w2);  v_out = emb * a[..., None]     (no biases)
  *   emb, v_out [B, F, K];  w1 [F, reduction_dim];  w2 [reduction_dim, F];  a_out [B, F] or NULL.
  * reduction_dim = embedding_dim // reduction_ratio, derived from K (not F) and required to be
- * < K exactly like the reference's assert (senet.py:18-19).
+ * < K exactly like the reference's assert (senet.py:18-19): 0 < reduction_dim < K, F >= 1.
+ * The four waves of a workgroup keep their examples and both weights in LDS, X = (2*F*K + 3*F + 2*reduction_dim + 3) & ~3:
+ *   forward   4 * (4*X +  2 * F*reduction_dim) <= 163840 bytes   (F <= 69 at K = 64, reduction_dim = 32)
+ *   backward  4 * (4*X + 10 * F*reduction_dim) <= 163840 bytes   (F <= 48 there); the backward also requires B > 0.
  * ------------------------------------------------------------------------------------------ */
 int recalgo_senet_fwd(const float* emb, const float* w1, const float* w2, int B, int F, int K,
                       int reduction_dim, float* v_out, float* a_out, recalgo_stream_t stream);
@@ -279,7 +299,12 @@ int recalgo_senet_bwd(const float* emb, const float* w1, const float* w2, const 
  *   zip-truncates to the first P: only those are read, and only those receive gradient).
  *   x_s [B, F, K]; x1 == w1 == NULL for a single set.  out row stride `out_stride` floats per
  *   pair (>= out_col + n_sets*K), out_stride % 4 == 0, out_col % 4 == 0.
- * K in {4, 8, 16, 32, 64};  3 <= F <= 128.
+ * K in {4, 8, 16, 32, 64};  3 <= F <= 128, and the LDS bound below, which is the tighter one from K = 32 on
+ * (n = F-1, P pairs, n_sets = 1 | 2, Wl = n_sets * K * (K + 4) for type ALL, else 0):
+ *   forward   4 * (4 * ((2*P + 15) / 16) + Wl + 4 * n_sets * (F + n) * K) <= 163840 bytes
+ *             (two sets, K = 64: F <= 31 for ALL, F <= 40 for EACH / INTERACTION; one set, ALL: F <= 69)
+ *   backward  4 * (4 * ((2*P + 15) / 16) + Wl + 2 * n_sets * (F + n) * K) <= 163840 bytes   (one wave per workgroup at the bound)
+ *             (two sets, K = 64: F <= 61 for ALL, F <= 77 for EACH / INTERACTION); the backward also requires B > 0.
  * ------------------------------------------------------------------------------------------ */
 #define RECALGO_BILINEAR_ALL 0
 #define RECALGO_BILINEAR_EACH 1
@@ -314,6 +339,9 @@ int recalgo_bilinear_bwd(const float* x0, const float* w0, const float* x1, cons
  *   omega [T, D].  The features forward zero-fills the columns [T, ld_phi) of every row, so a caller that pads the
  *   row stride to a multiple of 4 (T = 351 for 26 fields) hands the GEMM a float4-addressable operand whose padding
  *   is inert; the backward reads dphi with its own row stride and ignores the padding columns.
+ *   Features forward: R <= 255 (R = F for IPNN, K for OPNN: the pair table holds bytes).  Features backward: a wave keeps its
+ *   example and its dphi row in LDS, 16 * (F*K + T) <= 163840 bytes for IPNN (F <= 138 at K = 4, F <= 127 at K = 16) and
+ *   16 * (2*K + T) <= 163840 for OPNN (K <= 140).  F, K, D >= 1 everywhere; ld_phi / ld_dphi >= T.
  * ------------------------------------------------------------------------------------------ */
 #define RECALGO_PNN_IPNN 0
 #define RECALGO_PNN_OPNN 1
@@ -542,10 +570,13 @@ int recalgo_batchnorm_bwd_apply(const float* x, const float* gamma, const float*
  *       kernel with W = I), att [B, P] (the attention MLP's scores: the dense kernels) ->
  *       score = softmax over P, out[b, :] = sum_p score[b, p] * pairs[b, p, :];  score [B, P] is saved for
  *       bwd: d_pairs[b, p, :] = score * g[b, :], d_att = score * (<g, pairs_p> - sum_q score_q <g, pairs_q>)
- *       (K <= 64; the backward parks <g, pairs_p> in LDS: P <= 4096)
+ *       (1 <= K <= 64, P >= 1; the backward parks <g, pairs_p> of its four examples in 64 KiB of LDS: 16 * P <= 65536
+ *       bytes, P <= 4096)
  *   FFM field-aware pair dots (algorithm/FFM/ffm.py:146-160): x [B, F, F-1, K], row (i, s) = field i looked up in
  *       its s-th sub-table -> out[b] = sum_{i<j} <x[b, i, j-1, :], x[b, j, i, :]>
  *       bwd: dx[b, a, s, :] = g[b] * x[b, partner(a, s), :]
+ *   One thread per output element, counted in 32 bits: B * K < 2^31 (bi-interaction), B * F * (F-1) * K < 2^31 (FFM backward).
+ *   F >= 1 (bi-interaction), F >= 2 (FFM), K >= 1.
  * ------------------------------------------------------------------------------------------ */
 int recalgo_bi_interaction_fwd(const float* emb, int B, int F, int K, float* out, recalgo_stream_t stream);
 int recalgo_bi_interaction_bwd(const float* emb, const float* g, int B, int F, int K, float* d_emb, recalgo_stream_t stream);

@@ -1208,9 +1208,10 @@ RECALGO_EXPORT int recalgo_cin_layer_bwd(const float* x0, const float* xk, const
                                          int B, int m, int Hk, int N, int D, float* dx0, int dx0_accumulate,
                                          float* dxk, int dxk_accumulate, float* dfilters, void* workspace,
                                          recalgo_stream_t stream) {
-    RECALGO_REQUIRE(B > 0 && m > 0 && m <= 128 && Hk > 0 && Hk <= 128 && N > 0 && N <= 128 && d_ok(D));
+    // m >= 4: the 128 kk rows of a filter-gradient workgroup touch at most 127 / m + 2 distinct p values, and Ps has kPW columns
+    static_assert(127 / 4 + 2 <= kPW, "kPW holds the p values of a workgroup for every m >= 4");
+    RECALGO_REQUIRE(B > 0 && m >= 4 && m <= 128 && Hk > 0 && Hk <= 128 && N > 0 && N <= 128 && d_ok(D));
     RECALGO_REQUIRE(workspace != nullptr && (g_out != nullptr || g_pool != nullptr));
-    RECALGO_REQUIRE(127 / m + 2 <= kPW);
     hipStream_t st = as_stream(stream);
     const BwdWs ws = bwd_ws(B, m, Hk, N, D);
     char* base = static_cast<char*>(workspace);

@@ -469,7 +469,14 @@ __global__ __launch_bounds__(kThreads) void deepfm_sparse_fwd_kernel(
                     s += x;
                     sq = fmaf(x, x, sq);
                 }
-                acc2 += 0.5f * (s * s - sq);
+                float r;
+                {   // tf.square, then the subtraction, each rounded as the reference rounds them: one fma leaves the rounding
+                    // error of s * s behind where the two cancel (F == 1 is exactly 0)
+#pragma clang fp contract(off)
+                    const float ss = s * s;
+                    r = ss - sq;
+                }
+                acc2 += 0.5f * r;
                 fsum[(size_t)(b0 + e) * K + k] = s;
             }
             for (unsigned f = l16; f < F; f += 16) acc1 += w1s[e * F + f];

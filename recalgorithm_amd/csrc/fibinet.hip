@@ -722,6 +722,13 @@ inline size_t bi_smem(int F, int K, int nv, int type, bool bwd) {
     fl += (size_t)kWaves * nv * (bwd ? 2 : 1) * ((size_t)F * K + (size_t)n * K);
     return fl * sizeof(float);
 }
+// the least launch_bi_bwd can ask for: one wave per workgroup, the per-example gradient tile not staged
+inline size_t bi_bwd_smem1(int F, int K, int nv, int type) {
+    const unsigned n = F - 1, P = n * (n - 1) / 2;
+    const size_t fl = (size_t)ptab_floats(P) + (type == kAll ? (size_t)nv * K * kWS(K) : 0) +
+                      (size_t)nv * 2 * ((size_t)F * K + (size_t)n * K);
+    return fl * sizeof(float);
+}
 struct BiWs {
     size_t dvw, partials, total;
 };
@@ -810,6 +817,7 @@ RECALGO_EXPORT int recalgo_senet_fwd(const float* emb, const float* w1, const fl
     if (B == 0) return 0;
     const size_t smem = ((size_t)kWaves * ((2 * (size_t)F * K + 3 * F + 2 * reduction_dim + 3) & ~(size_t)3) +
                          2 * (size_t)F * reduction_dim) * sizeof(float);
+    RECALGO_REQUIRE(smem <= kLdsMax);
     RECALGO_CHECK(launch_lds<senet_fwd_kernel>(dim3(grid_for(B)), dim3(kThreads), smem, as_stream(stream), emb, w1, w2,
             (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)reduction_dim, v_out, a_out));
     RECALGO_RETURN_LAST();
@@ -827,6 +835,7 @@ RECALGO_EXPORT int recalgo_senet_bwd(const float* emb, const float* w1, const fl
     const unsigned WR = (unsigned)F * reduction_dim;
     const size_t smem = ((size_t)kWaves * ((2 * (size_t)F * K + 3 * F + 2 * reduction_dim + 3) & ~(size_t)3) +
                          (size_t)kWaves * 2 * WR + 2 * (size_t)WR) * sizeof(float);
+    RECALGO_REQUIRE(smem <= kLdsMax);
     const int grid = grid_for(B);        // one partial row per workgroup; up to 1024 workgroups = 16 waves per CU in flight (256 left
                                          // one wave per SIMD walking its four examples' latency chains alone: 44 us)
     float* partials = static_cast<float*>(workspace);
@@ -844,6 +853,8 @@ RECALGO_EXPORT int recalgo_bilinear_fwd(const float* x0, const float* w0, const 
     RECALGO_REQUIRE(B >= 0 && F >= 3 && F <= 128 && k_ok(K) && type >= kAll && type <= kInteraction);
     RECALGO_REQUIRE(x0 && w0 && (x1 == nullptr) == (w1 == nullptr));
     RECALGO_REQUIRE(out_stride % 4 == 0 && out_col % 4 == 0 && out_stride >= out_col + nv * K);
+    const size_t smem = bi_smem(F, K, nv, type, false);      // the four waves' rows of x and x W: what launch_bi_fwd asks for
+    RECALGO_REQUIRE(smem <= kLdsMax);
     if (B == 0) return 0;
     BiSets a{{x0, x1}, {w0, w1}, {nullptr, nullptr}};
     hipStream_t st = as_stream(stream);
@@ -868,6 +879,8 @@ RECALGO_EXPORT int recalgo_bilinear_bwd(const float* x0, const float* w0, const 
     RECALGO_REQUIRE((x1 == nullptr) == (w1 == nullptr) && (x1 == nullptr) == (dx1 == nullptr) &&
                     (x1 == nullptr) == (dw1 == nullptr));
     RECALGO_REQUIRE(g_stride % 4 == 0 && g_col % 4 == 0 && g_stride >= g_col + nv * K);
+    const size_t smem = bi_bwd_smem1(F, K, nv, type);
+    RECALGO_REQUIRE(smem <= kLdsMax);
     const BiWs ws = bi_ws(B, F, K, nv, type);
     char* base = static_cast<char*>(workspace);
     float* dvw = reinterpret_cast<float*>(base + ws.dvw);

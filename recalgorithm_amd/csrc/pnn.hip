@@ -347,8 +347,12 @@ RECALGO_EXPORT int recalgo_pnn_features_fwd(const float* emb, int B, int F, int 
 RECALGO_EXPORT int recalgo_pnn_features_bwd(const float* emb, const float* dphi, int ld_dphi, int B, int F, int K, int method,
                                             float* d_emb, int accumulate, recalgo_stream_t stream) {
     RECALGO_REQUIRE(B >= 0 && F > 0 && K > 0 && (method == kIPNN || method == kOPNN));
-    RECALGO_REQUIRE((method == kIPNN ? F : K) <= 255);
     RECALGO_REQUIRE(ld_dphi >= recalgo_pnn_feature_count(F, K, method));
+    // A wave keeps its example's rows and its dphi triangle in LDS: the least either method's kernel asks for.  (This bounds
+    // R = F | K well below the forward's 255.)
+    const size_t R = method == kIPNN ? F : K;
+    const size_t smem = (size_t)kWaves * ((method == kIPNN ? (size_t)F * K : 2 * (size_t)K) + R * (R + 1) / 2) * sizeof(float);
+    RECALGO_REQUIRE(smem <= kLdsMax);
     if (B == 0) return 0;
     hipStream_t st = as_stream(stream);
     if (method == kIPNN) {
@@ -359,12 +363,9 @@ RECALGO_EXPORT int recalgo_pnn_features_bwd(const float* emb, const float* dphi,
                     (unsigned)B, (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate));
             RECALGO_RETURN_LAST();
         }
-        const size_t smem = (size_t)kWaves * ((size_t)F * K + T) * sizeof(float);
         RECALGO_CHECK(launch_lds<ipnn_features_bwd_kernel>(dim3(grid_for(B)), dim3(kThreads), smem, st, emb, dphi, (unsigned)B,
                 (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate));
     } else {
-        const unsigned T = (unsigned)K * (K + 1) / 2;
-        const size_t smem = (size_t)kWaves * (2 * (size_t)K + T) * sizeof(float);
         RECALGO_CHECK(launch_lds<opnn_features_bwd_kernel>(dim3(grid_for(B)), dim3(kThreads), smem, st, emb, dphi, (unsigned)B,
                 (unsigned)F, (unsigned)K, (unsigned)ld_dphi, d_emb, accumulate));
     }

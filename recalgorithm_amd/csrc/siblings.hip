@@ -24,7 +24,14 @@ __global__ __launch_bounds__(256) void bi_interaction_fwd_kernel(const float* __
         s += x;
         q = fmaf(x, x, q);
     }
-    out[i] = 0.5f * (s * s - q);
+    float r;
+    {   // tf.square, then the subtraction, each rounded as the reference rounds them: one fma leaves the rounding error of s * s
+        // behind where the two cancel (F == 1 is exactly 0)
+#pragma clang fp contract(off)
+        const float ss = s * s;
+        r = ss - q;
+    }
+    out[i] = 0.5f * r;
 }
 // d e[b,f,k] = g[b,k] * (S[b,k] - e[b,f,k])
 __global__ __launch_bounds__(256) void bi_interaction_bwd_kernel(const float* __restrict__ emb, const float* __restrict__ g,
