@@ -16,9 +16,11 @@
 // evaluated in double as well.  The backward kernels recompute the forward from its inputs (the attention one twice per head:
 // once for concat_h(P_h V_h), which LayerNorm's backward needs first, once for the head's own gradients) and add every
 // parameter gradient into an LDS accumulator whose entry i is only ever touched by thread i % 512: the workgroup's
-// partial row, written once; bst_colsum_kernel adds the rows in order.  No float atomics.
+// partial row, written once; recalgo_slabs::launch_colsums adds the rows in the fixed order of slab_sum.h.  No float
+// atomics.
 // The kernels are instantiated per d (4, 8, 12, 16): every loop over d unrolls, so its LDS reads are issued together.
 #include "common.h"
+#include "slab_sum.h"
 
 #include "../../include/recalgo_bst.h"
 
@@ -519,38 +521,6 @@ __global__ __launch_bounds__(kThreads) void bst_ffn_bwd_kernel(FfnArgs a, FfnLds
     for (int i = threadIdx.x; i < L.n_acc; i += kThreads) prow[i] = acc[i];
 }
 
-// ---- second pass: out_s[c - start_s] = sum_{r < rows} partials[r][c], the rows added in order ------------------------------------
-constexpr int kSegs = 8;
-struct Segments {
-    float* out[kSegs];
-    int start[kSegs + 1];           // segment s holds the columns [start[s], start[s + 1])
-    int count;
-};
-
-__global__ __launch_bounds__(256) void bst_colsum_kernel(const float* __restrict__ partials, int rows, int n, Segments sg) {
-    __shared__ float sh[16][17];
-    const int cl = threadIdx.x & 15, rg = threadIdx.x >> 4;
-    const int c = blockIdx.x * 16 + cl;
-    float a = 0.f;
-    if (c < n)
-        for (int r = rg; r < rows; r += 16) a += partials[(size_t)r * n + c];
-    sh[rg][cl] = a;
-    __syncthreads();
-    if (rg == 0 && c < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) t += sh[g][cl];
-        int s = 0;
-        while (s + 1 < sg.count && c >= sg.start[s + 1]) ++s;
-        sg.out[s][c - sg.start[s]] = t;
-    }
-}
-
-template <typename... P>
-bool aligned4(const P*... p) {
-    return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & 3) == 0;
-}
-
 bool shape_ok(int T, int d, int H) {
     return T >= 1 && T <= kMaxT && d >= 4 && d <= kMaxD && (d & 3) == 0 && H >= 1 && H <= kMaxH &&
            sizeof(float) * (size_t)attn_lds(T, d, H, true).total <= kLdsMax;
@@ -591,7 +561,7 @@ RECALGO_EXPORT int recalgo_bst_attn_fwd(const float* x, const float* pos, const 
                                         recalgo_stream_t stream) {
     RECALGO_REQUIRE(B >= 1 && shape_ok(T, d, H));
     RECALGO_REQUIRE(x && pos && keys_length && w_q && w_k && w_v && w_o && gamma && beta && n1);
-    RECALGO_REQUIRE(aligned4(x, pos, w_q, w_k, w_v, w_o, gamma, beta, n1, stats) && aligned4(keys_length));
+    RECALGO_REQUIRE(aligned_to<4>(x, pos, w_q, w_k, w_v, w_o, gamma, beta, n1, stats) && aligned_to<4>(keys_length));
     const AttnArgs a = {x, pos, w_q, w_k, w_v, w_o, gamma, beta, keys_length, B, T, d, H, sqrtf((float)d)};
     const AttnLds L = attn_lds(T, d, H, false);      // (the layout travels as a kernel argument)
     BST_LAUNCH(bst_attn_fwd_kernel, d, dim3(rows_for(B, kFwdGrid)), sizeof(float) * (size_t)L.total, as_stream(stream), a, L, n1, stats);
@@ -606,21 +576,16 @@ RECALGO_EXPORT int recalgo_bst_attn_bwd(const float* x, const float* pos, const 
     RECALGO_REQUIRE(B >= 1 && shape_ok(T, d, H));
     RECALGO_REQUIRE(x && pos && keys_length && w_q && w_k && w_v && w_o && gamma && g_n1);
     RECALGO_REQUIRE(dx && dpos && dw_q && dw_k && dw_v && dw_o && dgamma && dbeta && workspace);
-    RECALGO_REQUIRE(aligned4(x, pos, w_q, w_k, w_v, w_o, gamma, g_n1) && aligned4(keys_length));
-    RECALGO_REQUIRE(aligned4(dx, dpos, dw_q, dw_k, dw_v, dw_o, dgamma, dbeta, workspace));
+    RECALGO_REQUIRE(aligned_to<4>(x, pos, w_q, w_k, w_v, w_o, gamma, g_n1) && aligned_to<4>(keys_length));
+    RECALGO_REQUIRE(aligned_to<4>(dx, dpos, dw_q, dw_k, dw_v, dw_o, dgamma, dbeta, workspace));
     const AttnArgs a = {x, pos, w_q, w_k, w_v, w_o, gamma, nullptr, keys_length, B, T, d, H, sqrtf((float)d)};
     const AttnLds L = attn_lds(T, d, H, true);
     const int rows = rows_for(B, kBwdGrid);
     hipStream_t st = as_stream(stream);
     BST_LAUNCH(bst_attn_bwd_kernel, d, dim3(rows), sizeof(float) * (size_t)L.total, st, a, L, g_n1, dx, workspace);
-    Segments sg = {};
-    sg.count = 7;
-    float* outs[7] = {dpos, dw_q, dw_k, dw_v, dw_o, dgamma, dbeta};
+    float* const outs[7] = {dpos, dw_q, dw_k, dw_v, dw_o, dgamma, dbeta};
     const int starts[8] = {L.a_pos, L.a_wq, L.a_wk, L.a_wv, L.a_wo, L.a_gam, L.a_bet, L.n_acc};
-    for (int s = 0; s < 7; ++s) sg.out[s] = outs[s], sg.start[s] = starts[s];
-    sg.start[7] = starts[7];
-    hipLaunchKernelGGL(bst_colsum_kernel, dim3(cdiv(L.n_acc, 16)), dim3(256), 0, st, workspace, rows, L.n_acc, sg);
-    RECALGO_RETURN_LAST();
+    return recalgo_slabs::launch_colsums(workspace, rows, 7, outs, starts, st);
 }
 
 RECALGO_EXPORT int recalgo_bst_ffn_fwd(const float* n1, const float* ffn_w, const float* ffn_b, const float* gamma,
@@ -628,7 +593,7 @@ RECALGO_EXPORT int recalgo_bst_ffn_fwd(const float* n1, const float* ffn_w, cons
                                        float* stats, recalgo_stream_t stream) {
     RECALGO_REQUIRE(B >= 1 && shape_ok(T, d, 1));
     RECALGO_REQUIRE(n1 && ffn_w && ffn_b && gamma && beta && (out || pool));
-    RECALGO_REQUIRE(aligned4(n1, ffn_w, ffn_b, gamma, beta, out, pool, stats));
+    RECALGO_REQUIRE(aligned_to<4>(n1, ffn_w, ffn_b, gamma, beta, out, pool, stats));
     const FfnArgs a = {n1, ffn_w, ffn_b, gamma, beta, B, T, d, mean_pool != 0};
     const FfnLds L = ffn_lds(T, d, false);
     BST_LAUNCH(bst_ffn_fwd_kernel, d, dim3(rows_for(B, kFwdGrid)), sizeof(float) * (size_t)L.total, as_stream(stream), a, L, out, pool, stats);
@@ -641,18 +606,13 @@ RECALGO_EXPORT int recalgo_bst_ffn_bwd(const float* n1, const float* ffn_w, cons
                                        recalgo_stream_t stream) {
     RECALGO_REQUIRE(B >= 1 && shape_ok(T, d, 1));
     RECALGO_REQUIRE(n1 && ffn_w && ffn_b && gamma && (g_out || g_pool) && dn1 && dw && db && dgamma && dbeta && workspace);
-    RECALGO_REQUIRE(aligned4(n1, ffn_w, ffn_b, gamma, g_out, g_pool, dn1, dw, db, dgamma, dbeta, workspace));
+    RECALGO_REQUIRE(aligned_to<4>(n1, ffn_w, ffn_b, gamma, g_out, g_pool, dn1, dw, db, dgamma, dbeta, workspace));
     const FfnArgs a = {n1, ffn_w, ffn_b, gamma, nullptr, B, T, d, mean_pool != 0};
     const FfnLds L = ffn_lds(T, d, true);
     const int rows = rows_for(B, kBwdGrid);
     hipStream_t st = as_stream(stream);
     BST_LAUNCH(bst_ffn_bwd_kernel, d, dim3(rows), sizeof(float) * (size_t)L.total, st, a, L, g_out, g_pool, dn1, workspace);
-    Segments sg = {};
-    sg.count = 4;
-    float* outs[4] = {dw, db, dgamma, dbeta};
+    float* const outs[4] = {dw, db, dgamma, dbeta};
     const int starts[5] = {L.a_w, L.a_b, L.a_gam, L.a_bet, L.n_acc};
-    for (int s = 0; s < 4; ++s) sg.out[s] = outs[s], sg.start[s] = starts[s];
-    sg.start[4] = starts[4];
-    hipLaunchKernelGGL(bst_colsum_kernel, dim3(cdiv(L.n_acc, 16)), dim3(256), 0, st, workspace, rows, L.n_acc, sg);
-    RECALGO_RETURN_LAST();
+    return recalgo_slabs::launch_colsums(workspace, rows, 4, outs, starts, st);
 }

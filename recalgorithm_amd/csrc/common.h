@@ -35,10 +35,15 @@ static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 __host__ __device__ __forceinline__ int round4(int v) { return (v + 3) & ~3; }
 
-// True when every pointer is 16-byte aligned (a null pointer counts as aligned).
+// True when every pointer is N-byte aligned (N a power of two; a null pointer counts as aligned).
+template <uintptr_t N, typename... P>
+static inline bool aligned_to(const P*... p) {
+    static_assert(N != 0 && (N & (N - 1)) == 0, "N is a power of two");
+    return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & (N - 1)) == 0;
+}
 template <typename... P>
 static inline bool aligned16(const P*... p) {
-    return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & 15) == 0;
+    return aligned_to<16>(p...);
 }
 
 // ---- dynamic LDS ----------------------------------------------------------
@@ -141,6 +146,7 @@ __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomic
 // rows rg, rg+16, ... in order, then the 16 groups are added in order (fixed summation order, and
 // S/16 instead of S dependent loads per thread — the one-thread-per-column form of this loop cost
 // 60-240 us for S = 256..1024 partial rows).  Columns [0, n0) go to out0, the rest to out1.
+// The order is slab_sum.h's sum_tall: a caller's deferred form (a job of the step's sum launch) gives the same bits.
 namespace {
 __global__ __launch_bounds__(256) void colsum16_kernel(const float* __restrict__ partials, unsigned S, unsigned n,
                                                        float* __restrict__ out0, unsigned n0,

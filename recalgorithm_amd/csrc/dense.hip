@@ -779,6 +779,33 @@ __global__ __launch_bounds__(256) void dense_sum_slabs_kernel(SplitJobs J) {
     }
 }
 
+// An entry's own second pass (recalgo_slabs::launch_colsums): the sum_tall sums of ALL the columns of the entry's partial rows,
+// 16 columns per workgroup, each written to the gradient whose run of columns holds it.  The same body as a vec == 2 job of
+// the kernel above — a column's sum does not depend on how the columns are tiled — behind a 120-byte argument block (two cache
+// lines) and no job search.
+using recalgo_slabs::kMaxColsumOuts;
+struct RowSums {
+    const float* partials;
+    int rows, count;
+    unsigned start[kMaxColsumOuts + 1];         // columns [start[s], start[s + 1]) -> out[s]; start[count]: the row's length
+    float* out[kMaxColsumOuts];
+};
+
+__global__ __launch_bounds__(256) void colsum_rows_kernel(RowSums A) {
+    __shared__ float sh[16][17];
+    SplitJob jb;
+    jb.partials = A.partials; jb.S = A.rows; jb.slab = jb.n = A.start[A.count];
+    const unsigned c = blockIdx.x * 16 + (threadIdx.x & 15);
+    const float tt = recalgo_slabs::sum_tall(jb, blockIdx.x, sh);
+    if ((threadIdx.x >> 4) == 0 && c < jb.n) {
+        int s = 0;
+#pragma unroll
+        for (int k = 1; k < kMaxColsumOuts; ++k)
+            if (k < A.count && c >= A.start[k]) s = k;
+        A.out[s][c - A.start[s]] = tt;
+    }
+}
+
 inline int vec_ok(const float* p, int ld) { return (aligned16(p) && ld % 4 == 0) ? 1 : 0; }
 // rows x cols: the extent of the matrix in memory (row-major, leading dimension ld)
 inline Operand operand(const float* p, const float* mask, int ld, int64_t rows, int64_t cols) {
@@ -901,25 +928,25 @@ static int launch_split_jobs(const SplitJobs& J, unsigned blocks, hipStream_t st
     return (int)hipGetLastError();
 }
 
-static SplitJob make_split_job(const float* ws, int S, int K, int N, float* dw, float* dbias, unsigned first_block,
-                               unsigned* blocks) {
+// (a job's first_block is set by whoever lays the jobs out in a grid: *blocks is how many it takes)
+static SplitJob make_split_job(const float* ws, int S, int K, int N, float* dw, float* dbias, unsigned* blocks) {
     SplitJob jb;
     jb.partials = ws; jb.out0 = dw; jb.out1 = dbias; jb.S = S;
     jb.slab = wgrad_slab(K, N);
     jb.n0 = (unsigned long long)K * N;
     jb.n = jb.n0 + (dbias ? (unsigned long long)N : 0ull);
     jb.vec = (jb.n0 % 4 == 0 && N % 4 == 0 && aligned16(dw) && (dbias == nullptr || aligned16(dbias)) && aligned16(ws)) ? 1 : 0;
-    jb.first_block = first_block;
+    jb.first_block = 0;
     *blocks = (unsigned)cdiv((int64_t)(jb.vec ? (jb.n + 3) / 4 : jb.n), 256);
     return jb;
 }
 
-static SplitJob make_colsum_job(const recalgo_colsum_t& c, unsigned first_block, unsigned* blocks) {
+static SplitJob make_colsum_job(const recalgo_colsum_t& c, unsigned* blocks) {
     SplitJob jb;
     jb.partials = c.partials; jb.out0 = c.out; jb.out1 = nullptr; jb.S = c.rows;
     jb.slab = (unsigned long long)c.row_stride; jb.n0 = jb.n = (unsigned long long)c.n;
     jb.vec = 2;
-    jb.first_block = first_block;
+    jb.first_block = 0;
     *blocks = (unsigned)cdiv((int64_t)jb.n, 16);
     return jb;
 }
@@ -949,7 +976,7 @@ static int finish_wgrad(int S, int defer_reduce, int K, int N, float* dw, float*
     if (S > 1 && !defer_reduce) {
         SplitJobs J;
         unsigned blocks = 0;
-        J.job[0] = make_split_job(static_cast<const float*>(workspace), S, K, N, dw, dbias, 0, &blocks);
+        J.job[0] = make_split_job(static_cast<const float*>(workspace), S, K, N, dw, dbias, &blocks);
         J.n_jobs = 1;
         J.step = nullptr;
         return launch_split_jobs(J, blocks, st);
@@ -1101,62 +1128,17 @@ RECALGO_EXPORT int recalgo_dense_bwd_rider_supported(const float* x, int ldx, co
     return 1;
 }
 
-RECALGO_EXPORT int recalgo_dense_bwd_weights_reduce(const recalgo_dense_split_t* jobs, int n_jobs,
-                                                    const recalgo_colsum_t* sums, int n_sums, int64_t* step_dev,
-                                                    recalgo_stream_t stream) {
+// The jobs of the two arrays, validated, column sums first: take(job, its blocks) gets each one with first_block still to
+// set and returns 0 to go on.  -> 0, hipErrorInvalidValue for a bad descriptor, or what take returned.
+template <typename Take>
+static int each_split_job(const recalgo_dense_split_t* jobs, int n_jobs, const recalgo_colsum_t* sums, int n_sums, Take take) {
     RECALGO_REQUIRE(n_jobs >= 0 && (n_jobs == 0 || jobs != nullptr) && n_sums >= 0 && (n_sums == 0 || sums != nullptr));
-    hipStream_t st = as_stream(stream);
-    SplitJobs J;
-    J.n_jobs = 0;
-    J.step = reinterpret_cast<long long*>(step_dev);
-    unsigned blocks = 0;
-    for (int i = 0; i < n_sums; ++i) {                       // plain column sums of partial rows (the loss tail's)
+    unsigned nb = 0;
+    for (int i = 0; i < n_sums; ++i) {                       // plain column sums of partial rows
         const recalgo_colsum_t& c = sums[i];
         RECALGO_REQUIRE(c.partials != nullptr && c.out != nullptr && c.rows >= 1 && c.n >= 1 && c.row_stride >= c.n);
-        unsigned nb = 0;
-        J.job[J.n_jobs++] = make_colsum_job(c, blocks, &nb);
-        blocks += nb;
-        if (J.n_jobs == kMaxSplitJobs) {
-            int rc = launch_split_jobs(J, blocks, st);
-            if (rc) return rc;
-            J.n_jobs = 0;
-            J.step = nullptr;
-            blocks = 0;
-        }
-    }
-    for (int i = 0; i < n_jobs; ++i) {
-        const recalgo_dense_split_t& d = jobs[i];
-        RECALGO_REQUIRE(d.M > 0 && d.K > 0 && d.N > 0 && d.dw != nullptr);
-        const int S = wgrad_splits(d.M, d.K, d.N);
-        if (S <= 1) continue;                               // nothing was deferred for this shape
-        RECALGO_REQUIRE(d.workspace != nullptr);
-        unsigned nb = 0;
-        J.job[J.n_jobs++] = make_split_job(static_cast<const float*>(d.workspace), S, d.K, d.N, d.dw, d.dbias, blocks, &nb);
-        blocks += nb;
-        if (J.n_jobs == kMaxSplitJobs) {
-            int rc = launch_split_jobs(J, blocks, st);
-            if (rc) return rc;
-            J.n_jobs = 0;
-            J.step = nullptr;
-            blocks = 0;
-        }
-    }
-    return launch_split_jobs(J, blocks, st);
-}
-
-// the same jobs in the same block layout for a launch that hosts them (slab_sum.h; tail.hip's sum-and-step launch)
-int recalgo_build_split_jobs(const recalgo_dense_split_t* jobs, int n_jobs, const recalgo_colsum_t* sums, int n_sums,
-                             SplitJob* out, int cap, int* n_out, unsigned* blocks_out) {
-    RECALGO_REQUIRE(n_jobs >= 0 && (n_jobs == 0 || jobs != nullptr) && n_sums >= 0 && (n_sums == 0 || sums != nullptr));
-    int n = 0;
-    unsigned blocks = 0;
-    for (int i = 0; i < n_sums; ++i) {
-        const recalgo_colsum_t& c = sums[i];
-        RECALGO_REQUIRE(c.partials != nullptr && c.out != nullptr && c.rows >= 1 && c.n >= 1 && c.row_stride >= c.n);
-        if (n == cap) return -1;
-        unsigned nb = 0;
-        out[n++] = make_colsum_job(c, blocks, &nb);
-        blocks += nb;
+        const SplitJob jb = make_colsum_job(c, &nb);
+        if (const int rc = take(jb, nb)) return rc;
     }
     for (int i = 0; i < n_jobs; ++i) {
         const recalgo_dense_split_t& d = jobs[i];
@@ -1164,11 +1146,68 @@ int recalgo_build_split_jobs(const recalgo_dense_split_t* jobs, int n_jobs, cons
         const int S = wgrad_splits(d.M, d.K, d.N);
         if (S <= 1) continue;                               // nothing was deferred for this shape: dw holds the gradient
         RECALGO_REQUIRE(d.workspace != nullptr);
-        if (n == cap) return -1;
-        unsigned nb = 0;
-        out[n++] = make_split_job(static_cast<const float*>(d.workspace), S, d.K, d.N, d.dw, d.dbias, blocks, &nb);
-        blocks += nb;
+        const SplitJob jb = make_split_job(static_cast<const float*>(d.workspace), S, d.K, d.N, d.dw, d.dbias, &nb);
+        if (const int rc = take(jb, nb)) return rc;
     }
+    return 0;
+}
+
+// one launch per kMaxSplitJobs jobs; the first advances the step counter
+static int run_split_jobs(const recalgo_dense_split_t* jobs, int n_jobs, const recalgo_colsum_t* sums, int n_sums,
+                          long long* step, hipStream_t st) {
+    SplitJobs J;
+    J.n_jobs = 0;
+    J.step = step;
+    unsigned blocks = 0;
+    const int rc = each_split_job(jobs, n_jobs, sums, n_sums, [&](SplitJob jb, unsigned nb) {
+        jb.first_block = blocks;
+        J.job[J.n_jobs++] = jb;
+        blocks += nb;
+        if (J.n_jobs < kMaxSplitJobs) return 0;
+        const int e = launch_split_jobs(J, blocks, st);
+        J.n_jobs = 0;
+        J.step = nullptr;
+        blocks = 0;
+        return e;
+    });
+    return rc ? rc : launch_split_jobs(J, blocks, st);
+}
+
+RECALGO_EXPORT int recalgo_dense_bwd_weights_reduce(const recalgo_dense_split_t* jobs, int n_jobs,
+                                                    const recalgo_colsum_t* sums, int n_sums, int64_t* step_dev,
+                                                    recalgo_stream_t stream) {
+    return run_split_jobs(jobs, n_jobs, sums, n_sums, reinterpret_cast<long long*>(step_dev), as_stream(stream));
+}
+
+// an entry's own second pass (slab_sum.h)
+int recalgo_slabs::launch_colsums(const float* partials, int rows, int count, float* const* outs, const int* starts, hipStream_t st) {
+    RECALGO_REQUIRE(partials != nullptr && outs != nullptr && starts != nullptr && rows >= 1 && count >= 1 && count <= kMaxColsumOuts);
+    RECALGO_REQUIRE(starts[0] == 0);
+    RowSums A;
+    A.partials = partials; A.rows = rows; A.count = count;
+    for (int s = 0; s < count; ++s) {
+        RECALGO_REQUIRE(outs[s] != nullptr && starts[s + 1] > starts[s]);
+        A.out[s] = outs[s];
+        A.start[s] = (unsigned)starts[s];
+    }
+    A.start[count] = (unsigned)starts[count];
+    hipLaunchKernelGGL(colsum_rows_kernel, dim3(cdiv(starts[count], 16)), dim3(256), 0, st, A);
+    return (int)hipGetLastError();
+}
+
+// the same jobs in the same block layout for a launch that hosts them (slab_sum.h; tail.hip's sum-and-step launch)
+int recalgo_build_split_jobs(const recalgo_dense_split_t* jobs, int n_jobs, const recalgo_colsum_t* sums, int n_sums,
+                             SplitJob* out, int cap, int* n_out, unsigned* blocks_out) {
+    int n = 0;
+    unsigned blocks = 0;
+    const int rc = each_split_job(jobs, n_jobs, sums, n_sums, [&](SplitJob jb, unsigned nb) {
+        if (n == cap) return -1;
+        jb.first_block = blocks;
+        out[n++] = jb;
+        blocks += nb;
+        return 0;
+    });
+    if (rc) return rc;
     *n_out = n;
     *blocks_out = blocks;
     return 0;

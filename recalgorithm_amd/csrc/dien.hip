@@ -16,9 +16,10 @@
 // The backward kernels recompute the gates of step t from the stored state of step t - 1 and keep every parameter gradient in
 // registers (doubles, added over the steps and the examples in a fixed order): a backward group is twice as wide, the second
 // half being helper lanes that own a third of the columns (see Acc).  The groups' registers are added in group order through
-// LDS into one partial row per workgroup; dien_colsum_kernel adds the rows in order.  No float atomics.  The kernels are
-// instantiated per nh (4, 8, 12, 16): every loop over the units unrolls.
+// LDS into one partial row per workgroup; recalgo_slabs::launch_colsums adds the rows in the fixed order of slab_sum.h.
+// No float atomics.  The kernels are instantiated per nh (4, 8, 12, 16): every loop over the units unrolls.
 #include "common.h"
+#include "slab_sum.h"
 
 #include "../../include/recalgo_dien.h"
 
@@ -495,38 +496,6 @@ __global__ __launch_bounds__(kThreads) void dien_evolve_bwd_kernel(const float* 
     for (int i = threadIdx.x; i < n_acc; i += kThreads) prow[i] = (float)sRed[i];
 }
 
-// ---- second pass: out_s[c - start_s] = sum_{r < rows} partials[r][c], the rows added in order ------------------------------------
-constexpr int kSegs = 5;
-struct Segments {
-    float* out[kSegs];
-    int start[kSegs + 1];           // segment s holds the columns [start[s], start[s + 1])
-    int count;
-};
-
-__global__ __launch_bounds__(256) void dien_colsum_kernel(const float* __restrict__ partials, int rows, int n, Segments sg) {
-    __shared__ float sh[16][17];
-    const int cl = threadIdx.x & 15, rg = threadIdx.x >> 4;
-    const int c = blockIdx.x * 16 + cl;
-    float a = 0.f;
-    if (c < n)
-        for (int r = rg; r < rows; r += 16) a += partials[(size_t)r * n + c];
-    sh[rg][cl] = a;
-    __syncthreads();
-    if (rg == 0 && c < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) t += sh[g][cl];
-        int s = 0;
-        while (s + 1 < sg.count && c >= sg.start[s + 1]) ++s;
-        sg.out[s][c - sg.start[s]] = t;
-    }
-}
-
-template <typename... P>
-bool aligned4(const P*... p) {
-    return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & 3) == 0;
-}
-
 bool width_ok(int n, int cap) { return n >= 4 && n <= cap && (n & 3) == 0; }
 
 bool shape_ok(int T, int na, int nh) { return T >= 1 && T <= kMaxT && width_ok(na, kMaxNA) && width_ok(nh, kMaxNH); }
@@ -538,14 +507,6 @@ int slots_of(int nh) { return kThreads / (nh <= 8 ? 8 : 16); }
 int gru_row(int na, int nh) { return (na + nh) * 3 * nh + 3 * nh; }
 
 int evolve_row(int na, int nh) { return nh * na + 2 * nh * 3 * nh + 3 * nh; }
-
-void launch_colsum(const float* ws, int rows, int n, int count, float* const* outs, const int* starts, hipStream_t st) {
-    Segments sg = {};
-    sg.count = count;
-    for (int s = 0; s < count; ++s) sg.out[s] = outs[s], sg.start[s] = starts[s];
-    sg.start[count] = n;
-    hipLaunchKernelGGL(dien_colsum_kernel, dim3(cdiv(n, 16)), dim3(256), 0, st, ws, rows, n, sg);
-}
 
 // nh is one of 4, 8, 12, 16 (shape_ok)
 #define DIEN_LAUNCH(KERNEL, nh, grid, st, ...)                                                             \
@@ -580,7 +541,7 @@ RECALGO_EXPORT int recalgo_dien_gru_fwd(const float* x, const int32_t* lengths, 
                                         const float* bc, int B, int T, int na, int nh, float* h, recalgo_stream_t stream) {
     RECALGO_REQUIRE(B >= 1 && shape_ok(T, na, nh));
     RECALGO_REQUIRE(x && Wg && bg && Wc && bc && h);
-    RECALGO_REQUIRE(aligned4(x, Wg, bg, Wc, bc, h) && aligned4(lengths));
+    RECALGO_REQUIRE(aligned_to<4>(x, Wg, bg, Wc, bc, h) && aligned_to<4>(lengths));
     const Cell w = {Wg, bg, Wc, bc};
     DIEN_LAUNCH(dien_gru_fwd_kernel, nh, dim3(cdiv(B, slots_of(nh))), as_stream(stream), x, lengths, w, B, T, na, h);
     RECALGO_RETURN_LAST();
@@ -592,16 +553,15 @@ RECALGO_EXPORT int recalgo_dien_gru_bwd(const float* x, const int32_t* lengths, 
                                         recalgo_stream_t stream) {
     RECALGO_REQUIRE(B >= 1 && shape_ok(T, na, nh));
     RECALGO_REQUIRE(x && h && Wg && bg && Wc && bc && g_h && dx && dWg && dbg && dWc && dbc && workspace);
-    RECALGO_REQUIRE(aligned4(x, h, Wg, bg, Wc, bc, g_h, dx, dWg, dbg, dWc, dbc, workspace) && aligned4(lengths));
+    RECALGO_REQUIRE(aligned_to<4>(x, h, Wg, bg, Wc, bc, g_h, dx, dWg, dbg, dWc, dbc, workspace) && aligned_to<4>(lengths));
     const Cell w = {Wg, bg, Wc, bc};
     const int rows = rows_for(B), n = gru_row(na, nh);
     hipStream_t st = as_stream(stream);
     DIEN_LAUNCH(dien_gru_bwd_kernel, nh, dim3(rows), st, x, lengths, h, w, g_h, B, T, na, dx, workspace);
     float* const outs[4] = {dWg, dbg, dWc, dbc};
     const int ng = (na + nh) * 2 * nh, nc = (na + nh) * nh;
-    const int starts[4] = {0, ng, ng + 2 * nh, ng + 2 * nh + nc};
-    launch_colsum(workspace, rows, n, 4, outs, starts, st);
-    RECALGO_RETURN_LAST();
+    const int starts[5] = {0, ng, ng + 2 * nh, ng + 2 * nh + nc, n};
+    return recalgo_slabs::launch_colsums(workspace, rows, 4, outs, starts, st);
 }
 
 RECALGO_EXPORT int recalgo_dien_evolve_fwd(const float* h, const float* target, const int32_t* lengths, const float* w_att,
@@ -610,7 +570,7 @@ RECALGO_EXPORT int recalgo_dien_evolve_fwd(const float* h, const float* target, 
                                            recalgo_stream_t stream) {
     RECALGO_REQUIRE(B >= 1 && shape_ok(T, na, nh) && (mode == RECALGO_DIEN_MODE_AGRU || mode == RECALGO_DIEN_MODE_AUGRU));
     RECALGO_REQUIRE(h && target && lengths && w_att && Wg && bg && Wc && bc && att && states && final_state);
-    RECALGO_REQUIRE(aligned4(h, target, w_att, Wg, bg, Wc, bc, att, states, final_state) && aligned4(lengths));
+    RECALGO_REQUIRE(aligned_to<4>(h, target, w_att, Wg, bg, Wc, bc, att, states, final_state) && aligned_to<4>(lengths));
     const Cell w = {Wg, bg, Wc, bc};
     DIEN_LAUNCH(dien_evolve_fwd_kernel, nh, dim3(cdiv(B, slots_of(nh))), as_stream(stream), h, target, lengths, w_att, w, B, T, na,
                 mode, att, states, final_state);
@@ -625,8 +585,8 @@ RECALGO_EXPORT int recalgo_dien_evolve_bwd(const float* h, const float* target, 
     RECALGO_REQUIRE(B >= 1 && shape_ok(T, na, nh) && (mode == RECALGO_DIEN_MODE_AGRU || mode == RECALGO_DIEN_MODE_AUGRU));
     RECALGO_REQUIRE(h && target && lengths && w_att && Wg && bg && Wc && bc && att && states && g_final);
     RECALGO_REQUIRE(dh && dtarget && dw_att && dWg && dbg && dWc && dbc && workspace);
-    RECALGO_REQUIRE(aligned4(h, target, w_att, Wg, bg, Wc, bc, att, states, g_final) && aligned4(lengths));
-    RECALGO_REQUIRE(aligned4(dh, dtarget, dw_att, dWg, dbg, dWc, dbc, workspace));
+    RECALGO_REQUIRE(aligned_to<4>(h, target, w_att, Wg, bg, Wc, bc, att, states, g_final) && aligned_to<4>(lengths));
+    RECALGO_REQUIRE(aligned_to<4>(dh, dtarget, dw_att, dWg, dbg, dWc, dbc, workspace));
     const Cell w = {Wg, bg, Wc, bc};
     const int rows = rows_for(B), n = evolve_row(na, nh);
     hipStream_t st = as_stream(stream);
@@ -634,7 +594,6 @@ RECALGO_EXPORT int recalgo_dien_evolve_bwd(const float* h, const float* target, 
                 dtarget, workspace);
     float* const outs[5] = {dw_att, dWg, dbg, dWc, dbc};
     const int na_ = nh * na, ng = 2 * nh * 2 * nh, nc = 2 * nh * nh;
-    const int starts[5] = {0, na_, na_ + ng, na_ + ng + 2 * nh, na_ + ng + 2 * nh + nc};
-    launch_colsum(workspace, rows, n, 5, outs, starts, st);
-    RECALGO_RETURN_LAST();
+    const int starts[6] = {0, na_, na_ + ng, na_ + ng + 2 * nh, na_ + ng + 2 * nh + nc, n};
+    return recalgo_slabs::launch_colsums(workspace, rows, 5, outs, starts, st);
 }

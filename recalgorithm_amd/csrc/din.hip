@@ -27,6 +27,7 @@
 // Fragment maps of v_mfma_f32_32x32x2_f32: lane l supplies A[row = l&31][k = l>>5] and
 // B[k = l>>5][col = l&31]; acc reg r holds C[row = (r&3) + 8*(r>>2) + 4*(l>>5)][col = l&31].
 #include "common.h"
+#include "slab_sum.h"
 
 namespace {
 
@@ -477,24 +478,6 @@ __global__ __launch_bounds__(kThreads) void din_attention_bwd_kernel(
     float* prow = partials + (size_t)blockIdx.x * PF;
     for (unsigned e = threadIdx.x; e < (unsigned)PF; e += kThreads) prow[e] = red[e];
 }
-
-// column sums of [nrows][ncols] -> out[ncols]; 64 columns x 4 row slices per workgroup
-__global__ __launch_bounds__(256) void din_sum_partials_kernel(const float* __restrict__ partials, unsigned nrows,
-                                                               unsigned stride, unsigned ncols,
-                                                               float* __restrict__ out) {
-    __shared__ float sh[4][64];
-    const unsigned cl = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const unsigned col = blockIdx.x * 64 + cl;
-    float acc = 0.f;
-    if (col < ncols) {
-#pragma unroll 8
-        for (unsigned r = slice; r < nrows; r += 4) acc += partials[(size_t)r * stride + col];
-    }
-    sh[slice][cl] = acc;
-    __syncthreads();
-    if (slice == 0 && col < ncols) out[col] = (sh[0][cl] + sh[1][cl]) + (sh[2][cl] + sh[3][cl]);
-}
-
 
 // =============================================================================================
 // H == 16 (the reference's fixed hidden size, din.py:103): the round-6 kernels.  Same math, same partial-row layout, but the
@@ -1256,22 +1239,10 @@ RECALGO_EXPORT int recalgo_din_attention_bwd_joined(const float* query, const fl
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (d_f1_w == nullptr) return 0;              // the caller sums the partial rows (a job of the step's deferred-sum launch)
-    // the partial row is laid out exactly as [d_f1_w | d_f1_b | d_f2_w | d_f2_b | d_f3_w | d_f3_b]:
-    // reduce it segment by segment into the caller's six buffers
-    struct Seg { float* dst; int off, n; };
+    // the partial row is laid out exactly as [d_f1_w | d_f1_b | d_f2_w | d_f2_b | d_f3_w | d_f3_b]: six jobs of one sum
+    // launch, wherever the caller's six buffers lie
+    float* const outs[6] = {d_f1_w, d_f1_b, d_f2_w, d_f2_b, d_f3_w, d_f3_b};
     const int o_b1 = 4 * H * N1, o_w2 = o_b1 + N1, o_b2 = o_w2 + N1 * N2, o_w3 = o_b2 + N2, o_b3 = o_w3 + N2;
-    const Seg segs[6] = {{d_f1_w, 0, o_b1}, {d_f1_b, o_b1, N1}, {d_f2_w, o_w2, N1 * N2},
-                         {d_f2_b, o_b2, N2}, {d_f3_w, o_w3, N2}, {d_f3_b, o_b3, 1}};
-    bool contiguous = true;                       // the six outputs laid out like the partial row (flat gradient buffer)?
-    for (int sgi = 1; sgi < 6; ++sgi) contiguous = contiguous && segs[sgi].dst == d_f1_w + segs[sgi].off;
-    if (contiguous) {
-        launch_colsum16(partials, (unsigned)grid, (unsigned)pf, d_f1_w, (unsigned)pf, static_cast<float*>(nullptr), st);
-    } else {
-        for (int sgi = 0; sgi < 6; ++sgi) {
-            const Seg& sg = segs[sgi];
-            hipLaunchKernelGGL(din_sum_partials_kernel, dim3(cdiv(sg.n, 64)), dim3(256), 0, st, partials + sg.off,
-                               (unsigned)grid, (unsigned)pf, (unsigned)sg.n, sg.dst);
-        }
-    }
-    RECALGO_RETURN_LAST();
+    const int starts[7] = {0, o_b1, o_w2, o_b2, o_w3, o_b3, pf};
+    return recalgo_slabs::launch_colsums(partials, grid, 6, outs, starts, st);
 }

@@ -90,8 +90,6 @@ __global__ __launch_bounds__(kThreads) void metrics_update_kernel(MetricsArgs P)
     }
 }
 
-bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // words of a slot's counters; 0: a slot the kernel does not serve
 long long slot_words(const recalgo_metrics_slot_t& s) {
     if (s.kind == RECALGO_METRICS_ACCURACY) return 2;
@@ -117,16 +115,16 @@ RECALGO_EXPORT int64_t recalgo_metrics_state_bytes(const recalgo_metrics_slot_t*
 RECALGO_EXPORT int recalgo_metrics_update(const recalgo_metrics_slot_t* slots, int n_slots, const float* loss, int n, void* state,
                                           recalgo_stream_t stream) {
     RECALGO_REQUIRE(n >= 1 && slots && state && n_slots >= 1 && n_slots <= kMaxSlots);
-    RECALGO_REQUIRE(aligned_to(state, 8) && aligned_to(loss, 4));
+    RECALGO_REQUIRE(aligned_to<8>(state) && aligned_to<4>(loss));
     MetricsArgs P = {};
     long long word = 2;
     for (int s = 0; s < n_slots; ++s) {
         const recalgo_metrics_slot_t& in = slots[s];
         const long long w = slot_words(in);
         RECALGO_REQUIRE(w && in.labels && in.predictions && in.label_stride >= 1 && in.prediction_stride >= 1);
-        RECALGO_REQUIRE(aligned_to(in.labels, 4) && aligned_to(in.predictions, 4));
+        RECALGO_REQUIRE(aligned_to<4>(in.labels) && aligned_to<4>(in.predictions));
         const bool auc = in.kind == RECALGO_METRICS_AUC;
-        RECALGO_REQUIRE(!auc || (in.thresholds && aligned_to(in.thresholds, 4)));
+        RECALGO_REQUIRE(!auc || (in.thresholds && aligned_to<4>(in.thresholds)));
         Slot& S = P.slot[s];
         S.labels = in.labels;
         S.predictions = in.predictions;

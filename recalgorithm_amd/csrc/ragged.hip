@@ -88,19 +88,17 @@ __global__ __launch_bounds__(kThreads) void bag_grad_rows_kernel(const int64_t* 
     }
 }
 
-bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 RECALGO_EXPORT int recalgo_ragged_abi_version(void) { return RECALGO_RAGGED_ABI_VERSION; }
 
 RECALGO_EXPORT int recalgo_ragged_pad(const int64_t* src, int64_t n, int64_t* dst, int64_t capacity, recalgo_stream_t stream) {
     RECALGO_REQUIRE(n >= 0 && n <= capacity && (dst || capacity == 0) && (src || n == 0));
-    RECALGO_REQUIRE(aligned_to(src, 8) && aligned_to(dst, 8) && capacity < (1ll << 38));
+    RECALGO_REQUIRE(aligned_to<8>(src) && aligned_to<8>(dst) && capacity < (1ll << 38));
     if (capacity == 0) return (int)hipSuccess;
     const long long pairs = (capacity + 1) / 2;
     hipLaunchKernelGGL(ragged_pad_kernel, dim3(cdiv(pairs, kThreads)), dim3(kThreads), 0, as_stream(stream), src, (long long)n, dst,
-                       (long long)capacity, aligned_to(dst, 16) ? 1 : 0);
+                       (long long)capacity, aligned_to<16>(dst) ? 1 : 0);
     RECALGO_RETURN_LAST();
 }
 
@@ -108,7 +106,7 @@ RECALGO_EXPORT int recalgo_bag_mean_grad_rows(const int64_t* values, const int64
                                               int g_stride, int g_col, int K, float* rows, recalgo_stream_t stream) {
     RECALGO_REQUIRE(B >= 0 && capacity >= 0 && K >= 1 && g_col >= 0 && (int64_t)g_stride >= (int64_t)g_col + K && offsets);
     RECALGO_REQUIRE(capacity == 0 || (values && g && rows));
-    RECALGO_REQUIRE(aligned_to(values, 8) && aligned_to(offsets, 8) && aligned_to(g, 4) && aligned_to(rows, 4));
+    RECALGO_REQUIRE(aligned_to<8>(values) && aligned_to<8>(offsets) && aligned_to<4>(g) && aligned_to<4>(rows));
     RECALGO_REQUIRE(capacity * (int64_t)K < (1ll << 38));
     if (capacity == 0) return (int)hipSuccess;
     const bool vec = K % 4 == 0 && g_stride % 4 == 0 && g_col % 4 == 0 && aligned16(g, rows);

@@ -232,11 +232,6 @@ __global__ __launch_bounds__(kThreads) void res_stack_bwd_kernel(const float* __
     tile_store<VEC>(dx + (size_t)b0 * D, Gs, GS, nb, D);
 }
 
-template <typename... P>
-bool aligned4(const P*... p) {
-    return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & 3) == 0;
-}
-
 bool supported(int D, int H, int L) {
     return D >= 1 && D <= kMaxD && H >= 16 && H <= kMaxH && (H & 15) == 0 && L >= 1 && L <= kMaxL && lds_bytes(D, H) <= kLdsMax;
 }
@@ -246,7 +241,7 @@ bool take_table(const float* const* src, int L, const float** dst) {
     if (src == nullptr) return false;
     for (int l = 0; l < kMaxL; ++l) {
         dst[l] = l < L ? src[l] : nullptr;
-        if (l < L && (dst[l] == nullptr || !aligned4(dst[l]))) return false;
+        if (l < L && (dst[l] == nullptr || !aligned_to<4>(dst[l]))) return false;
     }
     return true;
 }
@@ -261,7 +256,7 @@ RECALGO_EXPORT int recalgo_res_stack_fwd(const float* x, const float* const* w0,
                                          const float* const* b1, int B, int D, int H, int L, int save, float* hs, float* ys,
                                          recalgo_stream_t stream) {
     RECALGO_REQUIRE(supported(D, H, L) && B >= 1);
-    RECALGO_REQUIRE(x != nullptr && ys != nullptr && (save == 0 || hs != nullptr) && aligned4(x, hs, ys));
+    RECALGO_REQUIRE(x != nullptr && ys != nullptr && (save == 0 || hs != nullptr) && aligned_to<4>(x, hs, ys));
     ResTables T;
     RECALGO_REQUIRE(take_table(w0, L, T.w0) && take_table(b0, L, T.b0) && take_table(w1, L, T.w1) && take_table(b1, L, T.b1));
     const dim3 grid(cdiv(B, kRows)), block(kThreads);
@@ -278,7 +273,7 @@ RECALGO_EXPORT int recalgo_res_stack_bwd(const float* g, const float* hs, const 
                                          recalgo_stream_t stream) {
     RECALGO_REQUIRE(supported(D, H, L) && B >= 1);
     RECALGO_REQUIRE(g != nullptr && hs != nullptr && ys != nullptr && dzs != nullptr && dhs != nullptr && dx != nullptr);
-    RECALGO_REQUIRE(aligned4(g, hs, ys, dzs, dhs, dx));
+    RECALGO_REQUIRE(aligned_to<4>(g, hs, ys, dzs, dhs, dx));
     ResTables T;
     RECALGO_REQUIRE(take_table(w0, L, T.w0) && take_table(w1, L, T.w1));
     for (int l = 0; l < kMaxL; ++l) T.b0[l] = T.b1[l] = nullptr;

@@ -239,8 +239,7 @@ RECALGO_EXPORT int recalgo_serve_tower_fwd(const float* x, const float* const* w
                                            float* out, recalgo_stream_t stream) {
     RECALGO_REQUIRE(recalgo_serve_tower_supported(K0, units, L) && B >= 1);
     RECALGO_REQUIRE(x && out && w);
-    auto aligned4 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; };
-    RECALGO_REQUIRE(aligned4(x) && aligned4(out));
+    RECALGO_REQUIRE(aligned_to<4>(x, out));
     TowerArgs P = {};
     for (int l = 0; l < L; ++l) {
         P.w[l] = w[l];
@@ -249,7 +248,7 @@ RECALGO_EXPORT int recalgo_serve_tower_fwd(const float* x, const float* const* w
         P.shift[l] = (P.scale[l] && shift) ? shift[l] : nullptr;
         P.units[l] = units[l];
         RECALGO_REQUIRE(P.w[l] && (!P.scale[l] || P.shift[l]));
-        RECALGO_REQUIRE(aligned4(P.w[l]) && aligned4(P.b[l]) && aligned4(P.scale[l]) && aligned4(P.shift[l]));
+        RECALGO_REQUIRE(aligned_to<4>(P.w[l], P.b[l], P.scale[l], P.shift[l]));
     }
     P.x = x;
     P.out = out;

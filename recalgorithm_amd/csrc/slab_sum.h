@@ -1,7 +1,11 @@
-// The step's deferred fixed-order sums (weight-gradient split slabs, partial rows): the job descriptor and the three summation
-// bodies.  Two kernels run them — dense_sum_slabs_kernel (dense.hip: the sums alone) and sums_adam_tf1_step_kernel (tail.hip:
-// the sums and the dense optimizer update of the summed words in one launch) — and must agree bit for bit, so the order and the
-// association of every sum are stated here, once.
+// The fixed-order sums of every two-pass backward (weight-gradient split slabs, partial rows): the job descriptor and the three
+// summation bodies.  Two kernels run them — dense_sum_slabs_kernel (dense.hip: the sums alone) and sums_adam_tf1_step_kernel
+// (tail.hip: the sums and the dense optimizer update of the summed words in one launch) — and must agree bit for bit, so the
+// order and the association of every sum are stated here, once.  The entries of bst.hip, dien.hip and din.hip that sum their own
+// partial rows (the immediate second pass) run the same body: recalgo_slabs::launch_colsums below, a thin kernel around sum_tall.
+// Two older copies of sum_tall's order remain — colsum16_kernel (common.h: mlp, tail, fibinet) and colsum4_kernel (cross.hip):
+// through launch_colsums those entries measured 0.5-0.9 us slower per launch, and the cause is not found yet (DESIGN.md "One
+// second pass").  tests/test_gpu_colsums.py holds cross.hip's copy to the same bits.
 #pragma once
 #include "common.h"
 
@@ -86,3 +90,17 @@ __device__ __forceinline__ float sum_tall(const SplitJob& jb, size_t tile, float
 // -> 0, hipErrorInvalidValue for a bad descriptor, or -1 when more than `cap` jobs would be needed.
 int recalgo_build_split_jobs(const recalgo_dense_split_t* jobs, int n_jobs, const recalgo_colsum_t* sums, int n_sums,
                              recalgo_slabs::SplitJob* out, int cap, int* n_out, unsigned* blocks);
+
+namespace recalgo_slabs {
+
+constexpr int kMaxColsumOuts = 8;
+
+// An entry's immediate second pass.  The entry's partial rows are `count` (1..kMaxColsumOuts) gradients
+// side by side: columns [starts[s], starts[s + 1]) of every row belong to outs[s]; starts[0] == 0, every run is non-empty and
+// starts[count] is the row's length (the rows are contiguous).  outs[s][i] = the sum_tall sum of column starts[s] + i over the
+// `rows` rows: the bits a recalgo_colsum_t job {partials + starts[s], outs[s], rows, starts[count], the run's length} of the
+// step's deferred launch gives.  One launch (dense.hip: colsum_rows_kernel).
+// -> the launch's hipError_t (it also reports a failed launch of the kernel that wrote the rows), or hipErrorInvalidValue.
+int launch_colsums(const float* partials, int rows, int count, float* const* outs, const int* starts, hipStream_t st);
+
+}  // namespace recalgo_slabs

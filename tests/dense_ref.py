@@ -1,7 +1,8 @@
 """The dense ABI of include/recalgo.h (recalgo_dense_fwd / _bwd_input / _bwd_weights / _bwd / _bwd_weights_reduce) stated once in
 plain torch on the CPU, written from the header's comments.  `dtype` is the arithmetic: float64 is the reference, float32
-the same statement in the reference's own rounding (the `ref32` of tests/util.assert_close).  Nothing here follows the
-order in which a kernel adds; tests/test_dense_ref_host.py checks these functions against torch.autograd.
+the same statement in the reference's own rounding (the `ref32` of tests/util.assert_close).  Nothing here but
+colsum_fixed_order, the restatement of the fixed summation order, follows the order in which a kernel adds;
+tests/test_dense_ref_host.py checks these functions against torch.autograd.
 
 Tile rows: the BatchNorm partial rows are per 64 consecutive examples (recalgo_batchnorm_partial_rows(M) = ceil(M / 64))."""
 import torch
@@ -84,3 +85,23 @@ def colsum(partials, rows, row_stride, n, dtype=torch.float64):
     """recalgo_colsum_t: out[i] = sum_{r < rows} partials[r * row_stride + i], i < n; `partials` flat."""
     p = partials.reshape(-1).to(dtype)
     return torch.as_strided(p, (rows, n), (row_stride, 1)).sum(0)
+
+
+GROUPS = 16
+
+
+def colsum_fixed_order(partials, rows, row_stride, n):
+    """The ONE order in which the library adds partial rows (csrc/slab_sum.h, sum_tall), restated in fp32 on the CPU: for each
+    g < 16 the rows g, g + 16, g + 32, .. are added in row order starting from 0.0f, then the sixteen group sums are added in
+    group order starting from 0.0f.  Every add is one IEEE fp32 addition, so a kernel that keeps the order returns these bits.
+    (Unlike the functions above, this one does follow the kernels' order: it is the statement of the determinism contract.)"""
+    p = partials.detach().cpu().reshape(-1)
+    assert p.dtype == torch.float32
+    m = torch.as_strided(p, (rows, n), (row_stride, 1))
+    out = torch.zeros(n, dtype=torch.float32)
+    for g in range(GROUPS):
+        acc = torch.zeros(n, dtype=torch.float32)
+        for r in range(g, rows, GROUPS):
+            acc = acc + m[r]
+        out = out + acc
+    return out

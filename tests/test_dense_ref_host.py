@@ -124,6 +124,37 @@ def test_fwd_second_pair_dropout_and_colsum():
     assert all(o.dtype == torch.float32 for o in R.bwd(t["u"], t["up"], None, t["w"], dtype=torch.float32)[:3])
 
 
+@pytest.mark.parametrize("rows,stride,n", [(1, 5, 5), (3, 7, 4), (16, 9, 9), (17, 13, 10), (261, 40, 33)])
+def test_colsum_fixed_order_is_the_column_sum(rows, stride, n):
+    """Within fp32 rounding of the float64 colsum: `rows` - 1 additions per column at most, each off by at most half an ulp of
+    a partial sum no larger than the column's sum of magnitudes A: |error| <= (rows - 1) * 2^-24 * A."""
+    gen = torch.Generator().manual_seed(rows * 100 + n)
+    flat = torch.randn(rows * stride + 3, generator=gen)
+    got = R.colsum_fixed_order(flat, rows, stride, n)
+    assert got.dtype == torch.float32 and got.shape == (n,)
+    want = R.colsum(flat, rows, stride, n)
+    bound = (rows - 1) * 2.0 ** -24 * R.colsum(flat.abs(), rows, stride, n)
+    assert bool(((got.double() - want).abs() <= bound).all()), float(((got.double() - want).abs() - bound).max())
+    if rows == 1:
+        assert torch.equal(got, flat[:n])
+
+
+def test_colsum_fixed_order_is_not_the_row_order():
+    """Rows 0 and 16 (both group 0) hold +1e8 and -1e8, rows 1..15 hold 1: group 0 cancels exactly and the fifteen ones
+    survive, 15.0f.  In plain row order every 1 is absorbed by 1e8 (ulp 8) and the sum is 0.0f.  A second column has the pair
+    in rows 0 and 1 (groups 0 and 1): there row order is exact, and the group order loses row 16's 1 to row 0's 1e8."""
+    rows = 17
+    m = torch.ones(rows, 2)
+    m[0, 0], m[16, 0] = 1e8, -1e8
+    m[0, 1], m[1, 1] = 1e8, -1e8
+    got = R.colsum_fixed_order(m.reshape(-1), rows, 2, 2)
+    plain = torch.zeros(2)
+    for r in range(rows):
+        plain = plain + m[r]
+    assert got.tolist() == [15.0, 14.0] and plain.tolist() == [0.0, 15.0]
+    assert R.colsum(m.reshape(-1), rows, 2, 2).tolist() == [15.0, 15.0]
+
+
 # ---- the option tables of tests/test_gpu_dense_abi.py -----------------------------------------------------------------------
 def _uncovered(axes, rows, valid):
     """The pairs of values of two axes that some legal call has (a pair no legal call has is ruled out by a REQUIRE of the

@@ -21,8 +21,8 @@ aligned) allocations at the reference's shapes, which always lands on the fast a
  7  concat_sumsq_kernel, float4 and scalar     widths / column offsets % 4 and parts aligned ->    test_concat_sumsq_arms,
     arms; the last-workgroup ticket            float4, else scalar; > 256 workgroups at B = 4097;  test_concat_sumsq_ticket_*,
                                                B = 0                                               test_concat_sumsq_empty_batch
- 8  din_sum_partials_kernel vs colsum16        the six DIN weight gradients separate buffers vs    test_din_generic_arm (flat_grads)
-                                               one flat buffer in the partial row's order
+ 8  (no arm: one sum launch, six outputs)      the six DIN weight gradients in separate buffers    test_din_generic_arm (flat_grads):
+                                               or in one flat buffer in the partial row's order    the two layouts are bit-equal
  9  LDS ceilings (launch_lds)                  pnn: IPNN F = 255 (the largest accepted) at K = 16;  test_ipnn_lds_ceiling,
                                                fibinet: bilinear F = 128 (the largest accepted)    test_bilinear_lds_ceiling
 10  launch_lds's dynamic-LDS grant, kept per   bag_mean_bwd_kernel<4> at K = 32, 16, 64 in a fresh    test_lds_grant_grows,
@@ -31,7 +31,8 @@ aligned) allocations at the reference's shapes, which always lands on the fast a
 
 Each arm is compared with a float64 restatement (oracle.ref_ops, or a plain formula with its reference line) under the
 strict `ref32` guard of tests/util.py; where a fast arm exists for the same arguments, the same inputs also run through it.
-The two arms are not required to agree bit for bit: their summation orders differ."""
+The two arms of a row are not required to agree bit for bit: their summation orders differ.  Row 8 is no such pair: wherever
+the six gradient buffers lie, the same launch adds the same partial rows in the one fixed order (csrc/slab_sum.h)."""
 import ctypes
 import os
 import subprocess
@@ -93,7 +94,7 @@ def _din_inputs(B, T, H, gen):
 def _din_vars(ws, dev, flat_grads):
     vs = [Variable(f"v{i}", w.to(dev)) for i, w in enumerate(ws)]
     if flat_grads:
-        # the six gradients in one buffer, in the kernel's partial-row order: the single colsum16 launch
+        # the six gradients in one buffer, in the kernel's partial-row order (a model's flat gradient buffer)
         flat = torch.zeros(sum(w.numel() for w in ws), device=dev)
         off = 0
         for v in vs:
@@ -145,6 +146,12 @@ def test_din_generic_arm(dev, B, T, shift, flat_grads, is_softmax):
         out = ops.din_attention(store, qd, kd, lens.to(dev), vs, is_softmax)
         out.backward(g.to(dev))
         _din_check(f"din[{arm}]", out, qd.grad, kd.grad, vs, ref, a, r32, a32, is_softmax)
+        # the other layout of the six gradient buffers, same inputs, same kernel arm: the same bits
+        qd.grad = kd.grad = None
+        vs2 = _din_vars(ws, dev, not flat_grads)
+        ops.din_attention(store, qd, kd, lens.to(dev), vs2, is_softmax).backward(g.to(dev))
+        for i, nm in enumerate(["f1_w", "f1_b", "f2_w", "f2_b", "f3_w", "f3_b"]):
+            assert_bit_exact(vs2[i].grad, vs[i].grad, f"din[{arm}] d{nm}: flat against separate gradient buffers")
 
 
 @pytest.mark.parametrize("is_softmax", [False, True])
