@@ -2,12 +2,13 @@
 `create_feature_columns`, `example_parser`, `afm_model_fn(features, labels, mode, params)`, `main`, same variable names
 (`attention_part/attention_{w,b,h}`, `prediction_score_part/p`) and prediction keys (`logit`, `probabilities`).
 
-SURVEY.md §8f-3 sibling, built from the hot-path kernels plus one small one:
+SURVEY.md §8f-3 sibling:
   * per-field embeddings: gather / bag-mean kernels (one input_layer per column, afm.py:156-159);
-  * pair Hadamard products e_i * e_j, i < j over ALL F fields (afm.py:163-167) = the FiBiNET bilinear kernel with W = I
-    on the fields plus one zero field (that kernel pairs `combinations(range(F' - 1), 2)`, quirk B-3);
-  * attention MLP relu(pairs @ w + b) @ h (afm.py:181-183): the fp32-MFMA dense kernel on [B * P, K] and the one-unit head;
-  * softmax over the pairs + weighted sum (afm.py:184-188): `recalgo_attention_pool_*`;
+  * the attention network (afm.py:162-188) is nn.afm_attention, with params["afm_fused"] (not a reference parameter, absent in
+    every caller) as its `fused`: pair Hadamard products e_i * e_j, i < j over ALL F fields = the FiBiNET bilinear kernel with
+    W = I on the fields plus one zero field (that kernel pairs `combinations(range(F' - 1), 2)`, quirk B-3); relu(pairs @ w + b)
+    @ h: the fp32-MFMA dense kernel on [B * P, K] and the one-unit head; the softmax over the pairs + weighted sum:
+    `recalgo_attention_pool_*`;
   * afm_logit = weighted_sum @ p and the loss tail: the fused logit / loss kernel.
 Quirk kept: `category_input = fc.input_layer(...)` (:150-151) creates a second, unused set of tables.
 """
@@ -15,12 +16,10 @@ from __future__ import annotations
 
 from typing import Tuple
 
-import torch
-
 from ... import feature_column as fc
-from ... import flags, nn, ops
+from ... import flags, nn
 from ...model_tail import finish_model_fn
-from ...variables import Variable, current_store, variable_scope
+from ...variables import current_store, variable_scope
 from .. import _common as common
 from ..NFM.nfm import sibling_category_columns
 
@@ -40,17 +39,6 @@ total_feature_columns: list = []
 label_feature_columns: list = []
 example_parser = common.make_example_parser(lambda: (total_feature_columns, label_feature_columns))
 
-_identity = {}
-
-
-def _identity_weight(K: int, device) -> Variable:
-    """W = I for the bilinear kernel (a constant: its 'gradient' buffer is scratch)."""
-    key = (K, str(device))
-    v = _identity.get(key)
-    if v is None:
-        v = _identity[key] = Variable("afm/identity", torch.eye(K, device=device))
-    return v
-
 
 def afm_model_fn(features, labels, mode, params):
     """afm.py:130-237."""
@@ -63,7 +51,6 @@ def afm_model_fn(features, labels, mode, params):
 
     cols = params["category_feature_columns"]
     F, K, t = len(cols), int(params["embedding_dim"]), int(params["attention_factor"])
-    P = F * (F - 1) // 2
     with variable_scope("pair_interaction_part"):
         fields = fc.input_layers_concat(features, cols)                           # (batch, F*K), list order
     with variable_scope("attention_part"):
@@ -76,12 +63,7 @@ def afm_model_fn(features, labels, mode, params):
     if store.building:
         return finish_model_fn(mode, fields.new_zeros(B, 1), labels, params,
                                predictions=lambda prob: {"logit": fields.new_zeros(B, 1), "probabilities": prob})
-    # pair Hadamard products over all F fields: the bilinear kernel pairs the first F' - 1 of F' fields -> one zero field
-    padded = torch.cat([fields, fields.new_zeros(B, K)], dim=1).reshape(B, F + 1, K)
-    pairs = ops.bilinear_interaction(store, "all", padded.contiguous(), _identity_weight(K, fields.device))   # (B, P, K)
-    att = nn.dense_with(pairs.reshape(B * P, K), w, b, relu=True)                # relu(pairs @ w + b)   (B*P, t)
-    att = nn.dense_with(att, h, None, relu=False)                                 # @ h                   (B*P, 1)
-    weighted = ops.attention_pool(pairs, att.reshape(B, P))                       # softmax over pairs, weighted sum (B, K)
+    weighted = nn.afm_attention(fields, F, K, w, b, h, fused=params.get("afm_fused"))   # (B, K); afm.py:162-188
     afm_logit = nn.dense_with(weighted, p, None, relu=False)                      # (B, 1)
     total_logit = dense_logit + afm_logit
     return finish_model_fn(mode, total_logit, labels, params,

@@ -1161,3 +1161,40 @@ def residual_stack(x: torch.Tensor, internal_dim: int, num_units: int, first_ind
 def residual_unit(x: torch.Tensor, internal_dim: int, index: int, fused: Optional[bool] = None) -> torch.Tensor:
     """One residual unit (residual_unit.py:4-22) with the variables dense_<index>_0 / dense_<index>_1: the one-unit stack."""
     return residual_stack(x, internal_dim, 1, first_index=index, fused=fused)
+
+
+# ---- AFM's attention network (afm.py:162-188) ------------------------------------------------------------------------------------
+_afm_identity = {}
+
+
+def _afm_identity_weight(K: int, device) -> Variable:
+    """W = I for the bilinear kernel (a constant: its 'gradient' buffer is scratch)."""
+    key = (K, str(device))
+    v = _afm_identity.get(key)
+    if v is None:
+        v = _afm_identity[key] = Variable("afm/identity", torch.eye(K, device=device))
+    return v
+
+
+def afm_attention(fields: torch.Tensor, F: int, K: int, w: Variable, b: Variable, h: Variable,
+                  fused: Optional[bool] = None) -> torch.Tensor:
+    """algorithm/AFM/afm.py:162-188: the pair products e_i * e_j (i < j, row-major over the strict upper triangle) of the F field
+    embeddings of fields [B, F * K], their attention scores relu(pairs @ w + b) @ h, the softmax over the pairs and the weighted
+    sum -> [B, K].  w [K, t], b [t], h [t, 1] are the model's own variables.
+    fused (not a reference argument; the model: params["afm_fused"]), in the manner of residual_stack: None or False run the
+    composed chain — the FiBiNET bilinear kernel with W = I on the fields plus one zero field (that kernel pairs
+    `combinations(range(F' - 1), 2)`, quirk B-3), the fp32-MFMA dense kernel on [B * P, K], the one-unit head and
+    ops.attention_pool.  True asks for a fused kernel; none serves any shape yet, so True is a ValueError.
+    tests/afm_ref.py is the float64 restatement both paths answer to."""
+    from . import ops
+    store = current_store()
+    F, K = int(F), int(K)
+    if fused:
+        raise ValueError(f"afm_attention(fused=True): no fused kernel serves F={F} K={K} t={int(w.data.shape[1])} on {fields.device}")
+    B, P = fields.shape[0], F * (F - 1) // 2
+    # pair Hadamard products over all F fields: the bilinear kernel pairs the first F' - 1 of F' fields -> one zero field
+    padded = torch.cat([fields, fields.new_zeros(B, K)], dim=1).reshape(B, F + 1, K)
+    pairs = ops.bilinear_interaction(store, "all", padded.contiguous(), _afm_identity_weight(K, fields.device))   # (B, P, K)
+    att = dense_with(pairs.reshape(B * P, K), w, b, relu=True)                   # relu(pairs @ w + b)   (B*P, t)
+    att = dense_with(att, h, None, relu=False)                                    # @ h                   (B*P, 1)
+    return ops.attention_pool(pairs, att.reshape(B, P))                           # softmax over pairs, weighted sum (B, K)
