@@ -5,10 +5,11 @@
 SURVEY.md §8f-3 sibling:
   * per-field embeddings: gather / bag-mean kernels (one input_layer per column, afm.py:156-159);
   * the attention network (afm.py:162-188) is nn.afm_attention, with params["afm_fused"] (not a reference parameter, absent in
-    every caller) as its `fused`: pair Hadamard products e_i * e_j, i < j over ALL F fields = the FiBiNET bilinear kernel with
-    W = I on the fields plus one zero field (that kernel pairs `combinations(range(F' - 1), 2)`, quirk B-3); relu(pairs @ w + b)
-    @ h: the fp32-MFMA dense kernel on [B * P, K] and the one-unit head; the softmax over the pairs + weighted sum:
-    `recalgo_attention_pool_*`;
+    every caller) as its `fused`.  Where csrc/afm.hip serves the shape (attention_factor % 16 == 0, embedding_dim % 4 == 0)
+    it is one fused kernel each way; elsewhere, and with afm_fused=False, the composed chain: pair Hadamard products
+    e_i * e_j, i < j over ALL F fields = the FiBiNET bilinear kernel with W = I on the fields plus one zero field (that kernel
+    pairs `combinations(range(F' - 1), 2)`, quirk B-3); relu(pairs @ w + b) @ h: the fp32-MFMA dense kernel on [B * P, K] and
+    the one-unit head; the softmax over the pairs + weighted sum: `recalgo_attention_pool_*`;
   * afm_logit = weighted_sum @ p and the loss tail: the fused logit / loss kernel.
 Quirk kept: `category_input = fc.input_layer(...)` (:150-151) creates a second, unused set of tables.
 """

@@ -1176,21 +1176,41 @@ def _afm_identity_weight(K: int, device) -> Variable:
     return v
 
 
+def afm_fused_served(fields: torch.Tensor, F: int, K: int, t: int) -> bool:
+    """Whether afm_attention(fused=True) has a kernel for these fields: an fp32 [B >= 1, F * K] device tensor of a served shape."""
+    from . import ops
+    return (fields.is_cuda and fields.dtype == torch.float32 and fields.dim() == 2 and fields.shape[0] >= 1
+            and fields.shape[1] == F * K and ops.afm_supported(F, K, t))
+
+
+def afm_fused_default(fields: torch.Tensor, F: int, K: int, t: int) -> bool:
+    """Whether afm_attention(fused=None) runs the fused kernels: wherever they serve the shape."""
+    return afm_fused_served(fields, F, K, t)
+
+
 def afm_attention(fields: torch.Tensor, F: int, K: int, w: Variable, b: Variable, h: Variable,
                   fused: Optional[bool] = None) -> torch.Tensor:
     """algorithm/AFM/afm.py:162-188: the pair products e_i * e_j (i < j, row-major over the strict upper triangle) of the F field
     embeddings of fields [B, F * K], their attention scores relu(pairs @ w + b) @ h, the softmax over the pairs and the weighted
     sum -> [B, K].  w [K, t], b [t], h [t, 1] are the model's own variables.
-    fused (not a reference argument; the model: params["afm_fused"]), in the manner of residual_stack: None or False run the
+    fused (not a reference argument; the model: params["afm_fused"]), in the manner of residual_stack.  False runs the
     composed chain — the FiBiNET bilinear kernel with W = I on the fields plus one zero field (that kernel pairs
     `combinations(range(F' - 1), 2)`, quirk B-3), the fp32-MFMA dense kernel on [B * P, K], the one-unit head and
-    ops.attention_pool.  True asks for a fused kernel; none serves any shape yet, so True is a ValueError.
+    ops.attention_pool.  True runs ops.afm_attention, one launch each way (csrc/afm.hip), where afm_fused_served says so: an
+    fp32 device tensor and 2 <= F <= 64, K % 4 == 0 with 4 <= K <= 32, t % 16 == 0 with 16 <= t <= 256 (a non-contiguous
+    `fields` is copied first); anywhere else True is a ValueError.  None picks the kernel wherever True would succeed
+    (afm_fused_default; the measurement: DESIGN.md §5 "AFM attention").
     tests/afm_ref.py is the float64 restatement both paths answer to."""
     from . import ops
     store = current_store()
     F, K = int(F), int(K)
+    t = int(w.data.shape[1])
+    if fused is None:
+        fused = afm_fused_default(fields, F, K, t)
+    elif fused and not afm_fused_served(fields, F, K, t):
+        raise ValueError(f"afm_attention(fused=True): no fused kernel serves F={F} K={K} t={t} on {fields.device}")
     if fused:
-        raise ValueError(f"afm_attention(fused=True): no fused kernel serves F={F} K={K} t={int(w.data.shape[1])} on {fields.device}")
+        return ops.afm_attention(fields if fields.is_contiguous() else fields.contiguous(), F, K, w, b, h, anchor=store.anchor)
     B, P = fields.shape[0], F * (F - 1) // 2
     # pair Hadamard products over all F fields: the bilinear kernel pairs the first F' - 1 of F' fields -> one zero field
     padded = torch.cat([fields, fields.new_zeros(B, K)], dim=1).reshape(B, F + 1, K)

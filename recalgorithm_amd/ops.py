@@ -2744,6 +2744,70 @@ def residual_stack(x: torch.Tensor, w0s, b0s, w1s, b1s, anchor=None) -> torch.Te
 
 
 # =============================================================================================
+# AFM (csrc/afm.hip, include/recalgo_afm.h): the attention network over the pair products, one kernel each way
+# =============================================================================================
+def afm_supported(F: int, K: int, t: int) -> bool:
+    return bool(_lib_().recalgo_afm_supported(int(F), int(K), int(t)))
+
+
+class _AfmAttentionFn(Function):
+    """include/recalgo_afm.h recalgo_afm_attention_fwd / recalgo_afm_attention_bwd; params = (w, b, h), `tensors` the same three
+    with None where params holds a Variable.  Saved: the fields and the pre-softmax scores [B, P]."""
+
+    @staticmethod
+    def forward(ctx, anchor, fields, F, K, differentiated, params, *tensors):
+        ts, vs = _bst_split(params)
+        B, t = fields.shape[0], int(ts[0].shape[1])
+        out = torch.empty(B, K, device=fields.device, dtype=torch.float32)
+        # (the caller's grad mode: inside a Function's forward it is always off; PREDICT / EVAL keep no scores)
+        scores = torch.empty(B, F * (F - 1) // 2, device=fields.device, dtype=torch.float32) if differentiated else None
+        _lib_().recalgo_afm_attention_fwd(_p(fields), *[_p(x) for x in ts], B, F, K, t, _p(out), _p(scores), _stream(fields))
+        if differentiated:
+            ctx.ts, ctx.vs, ctx.F, ctx.K = ts, vs, F, K
+            ctx.save_for_backward(fields, scores)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ts, vs, F, K = ctx.ts, ctx.vs, ctx.F, ctx.K
+        fields, scores = ctx.saved_tensors
+        B, t = fields.shape[0], int(ts[0].shape[1])
+        g = g if g.is_contiguous() else g.contiguous()
+        lib = _lib_()
+        d_fields = torch.empty_like(fields)
+        outs = _bst_grad_buffers(ts, vs)                 # dw, db, dh
+        ws = _workspace(int(lib.recalgo_afm_bwd_workspace_bytes(B, F, K, t)), fields.device)
+        lib.recalgo_afm_attention_bwd(_p(g), _p(fields), *[_p(x) for x in ts], _p(scores), B, F, K, t, _p(d_fields),
+                                      *[_p(o) for o in outs], _p(ws), _stream(fields))
+        rets = [None if v is not None else o for o, v in zip(outs, vs)]
+        return (None, d_fields if ctx.needs_input_grad[1] else None, None, None, None, None, *rets)
+
+
+def afm_attention(fields: torch.Tensor, F: int, K: int, w, b, h, anchor=None) -> torch.Tensor:
+    """AFM's attention network (afm.py:162-188) as one launch each way: fields [B, F * K] (contiguous fp32 on the device) ->
+    sum_p softmax_p(relu(pair_p @ w + b) @ h) * pair_p over the pairs p = (i < j) of the F field rows, [B, K].  w [K, t],
+    b [t], h [t, 1] or [t] — Variables (gradient to Variable.grad, overwritten) or tensors.  With grad enabled the forward
+    keeps the fields and the [B, P] scores; the backward is one launch and the fixed-order sum of its partial rows.  Shapes
+    the kernels do not serve (afm_supported): ValueError, there is no fallback here (nn.afm_attention owns the composed chain)."""
+    F, K = int(F), int(K)
+    params = [w, b, h]
+    ts, _ = _bst_split(params)
+    t = int(ts[0].shape[1]) if ts[0].dim() == 2 else 0
+    if not afm_supported(F, K, t):
+        raise ValueError(f"afm_attention: the kernels serve 2 <= F <= 64, K % 4 == 0 with 4 <= K <= 32 and t % 16 == 0 with "
+                         f"16 <= t <= 256; got F={F} K={K} t={t} (there is no fallback)")
+    if fields.dim() != 2 or fields.shape[0] == 0 or fields.shape[1] != F * K:
+        raise ValueError(f"afm_attention: fields must be a non-empty [B, F * K = {F * K}] matrix, got {tuple(fields.shape)}")
+    _chk(fields, torch.float32, "afm_attention: fields")
+    for x, n, name in zip(ts, (K * t, t, t), ("w", "b", "h")):
+        _chk(x, torch.float32, f"afm_attention: {name}")
+        if x.numel() != n or (name == "w" and tuple(x.shape) != (K, t)):
+            raise ValueError(f"afm_attention: {name} has shape {tuple(x.shape)}")
+    tensors = [None if isinstance(p, Variable) else p for p in params]
+    return _AfmAttentionFn.apply(anchor, fields, F, K, torch.is_grad_enabled(), params, *tensors)
+
+
+# =============================================================================================
 # DIEN (csrc/dien.hip, include/recalgo_dien.h): the GRU recurrence; attention + the AGRU / AUGRU recurrence
 # =============================================================================================
 _CD = _lib.MORE_HEADERS["recalgo_dien.h"].constants           # the RECALGO_DIEN_* #defines of include/recalgo_dien.h
