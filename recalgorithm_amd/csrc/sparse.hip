@@ -46,6 +46,8 @@
 #include <cstdlib>
 
 #include "deferred.h"
+#include "copy_span.h"
+#include "../../include/recalgo_feed.h"
 
 // tuning knobs of `apply` (build-time): workgroups resident per CU (the register budget follows) and gradient rows in flight
 #ifndef RECALGO_APPLY_WGS
@@ -316,6 +318,11 @@ struct PrepareArgs {
     unsigned passes, passes1;      // a workgroup walks `passes` of the step's row blocks
     unsigned bshift, bshift1;      // sweep blocks are 256 << bshift rows (sweep_block_shift)
     int sweeping;                  // this launch carries the sweep: the catch-up leaves the rows of the step's blocks to it
+    // the feed (recalgo_scatter_prepare_feed): workgroups [b_copy, gridDim.x), the last of the grid, write
+    // feed_dst[0, feed_bytes) = feed_src[0, feed_bytes) (copy_span.h); none: b_copy == gridDim.x
+    unsigned b_copy;
+    unsigned char* feed_dst; const unsigned char* feed_src;
+    size_t feed_head, feed_n16, feed_bytes;
 };
 
 // request r (request-major: e = r / F, f = r % F) -> arena row, -1 if none
@@ -567,6 +574,13 @@ __device__ __forceinline__ void catchup_requests(const PrepareArgs& A, const Src
 
 __global__ __launch_bounds__(kThreads, 8) void sparse_prepare_kernel(PrepareArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned lds_u[];
+    if (blockIdx.x >= A.b_copy) {
+        // ---- feed: the step's batch into the captured step's static input span.  The LAST workgroups of the grid: dispatched
+        // behind every catch-up workgroup, whose dependent chain is what the launch lasts as long as -------------------------
+        recalgo_copy::copy_span(A.feed_dst, A.feed_src, A.feed_head, A.feed_n16, A.feed_bytes,
+                                (size_t)(blockIdx.x - A.b_copy) * kThreads + threadIdx.x, (size_t)(gridDim.x - A.b_copy) * kThreads);
+        return;
+    }
     const int target = A.D.last_step ? (int)(A.step[0] + A.step_off) : 0;
     const int cidx = A.period > 0 ? target % A.period : 0;
     if (blockIdx.x < A.b_catch) {
@@ -634,7 +648,7 @@ __global__ __launch_bounds__(kThreads, 8) void sparse_prepare_kernel(PrepareArgs
     }
     {
         const recalgo_deferred::LrWindow W = recalgo_deferred::lr_window(A.D1.lr_ring, target);
-        const long long wg = blockIdx.x - A.b_sweep, nwg = (long long)gridDim.x - A.b_sweep;
+        const long long wg = blockIdx.x - A.b_sweep, nwg = (long long)A.b_copy - A.b_sweep;
         sweep_units(A.D1, 1, A.passes1, [&](unsigned pu) { return sweep_unit_row(cidx, A.period, A.bshift1, wg + (long long)pu * nwg); },
                     A.rows1, target, C, W);
     }
@@ -1427,11 +1441,14 @@ RECALGO_EXPORT int64_t recalgo_scatter_plan_workspace_bytes(int64_t n_slots, int
            cap * (int64_t)(K + 1) * (int64_t)sizeof(float) + 64;
 }
 
+// the feed of recalgo_scatter_prepare_feed, checked (feed_check): dst == nullptr: no copy
+struct Feed { void* dst = nullptr; const void* src = nullptr; size_t bytes = 0; };
+
 static int scatter_prepare_impl(const recalgo_scatter_source_t* source, int n_sources, const int64_t* first_requests, int K,
                                 void* plan_workspace, int64_t plan_requests, int nb_log2, int flags,
                                 const recalgo_deferred_adam_t* deferred, const recalgo_deferred_adam_t* companion_deferred,
                                 int64_t rows, int64_t companion_rows, int sweep_period, const int64_t* step_dev, int step_offset,
-                                recalgo_stream_t stream);
+                                recalgo_stream_t stream, const Feed& feed);
 
 RECALGO_EXPORT int recalgo_scatter_prepare(const recalgo_scatter_source_t* source, int K, void* plan_workspace,
                                            int64_t plan_requests, int nb_log2, int64_t first_request, int flags,
@@ -1440,7 +1457,7 @@ RECALGO_EXPORT int recalgo_scatter_prepare(const recalgo_scatter_source_t* sourc
                                            int sweep_period, const int64_t* step_dev, int step_offset, recalgo_stream_t stream) {
     return scatter_prepare_impl(source, (source != nullptr && source->n_ex > 0) ? 1 : 0, &first_request, K, plan_workspace, plan_requests,
                                 nb_log2, flags, deferred, companion_deferred, rows, companion_rows, sweep_period, step_dev, step_offset,
-                                stream);
+                                stream, Feed{});
 }
 
 RECALGO_EXPORT int recalgo_scatter_prepare_multi(const recalgo_scatter_source_t* sources, int n_sources, const int64_t* first_requests,
@@ -1450,14 +1467,55 @@ RECALGO_EXPORT int recalgo_scatter_prepare_multi(const recalgo_scatter_source_t*
     RECALGO_REQUIRE(sources != nullptr && first_requests != nullptr && n_sources >= 1 && n_sources <= kPrepSources);
     for (int i = 0; i < n_sources; ++i) RECALGO_REQUIRE(sources[i].n_ex > 0);
     return scatter_prepare_impl(sources, n_sources, first_requests, K, plan_workspace, plan_requests, nb_log2, flags, deferred, nullptr,
-                                rows, 0, sweep_period, step_dev, step_offset, stream);
+                                rows, 0, sweep_period, step_dev, step_offset, stream, Feed{});
+}
+
+// ---- include/recalgo_feed.h ---------------------------------------------------------------------------------------------------
+// 1: a copy to launch, 0: nothing to copy (no source, no bytes, or dst == src), -1: refused
+static int feed_check(const void* dst, const void* src, int64_t nbytes) {
+    if (nbytes < 0) return -1;
+    if (src == nullptr || nbytes == 0 || dst == src) return 0;
+    if (dst == nullptr) return -1;
+    const uintptr_t d = reinterpret_cast<uintptr_t>(dst), s = reinterpret_cast<uintptr_t>(src), n = (uintptr_t)nbytes;
+    if ((d & 15) != (s & 15)) return -1;
+    if (d < s ? s - d < n : d - s < n) return -1;             // the ranges overlap
+    return 1;
+}
+
+RECALGO_EXPORT int recalgo_feed_abi_version(void) { return RECALGO_FEED_ABI_VERSION; }
+
+RECALGO_EXPORT int recalgo_scatter_prepare_feed_supported(const void* feed_dst, const void* feed_src, int64_t feed_bytes) {
+    return feed_check(feed_dst, feed_src, feed_bytes) >= 0 ? 1 : 0;
+}
+
+RECALGO_EXPORT int recalgo_scatter_prepare_feed(const void* sources, int n_sources, const int64_t* first_requests, int K,
+                                                void* plan_workspace, int64_t plan_requests, int nb_log2, int flags,
+                                                const void* deferred, const void* companion_deferred, int64_t rows,
+                                                int64_t companion_rows, int sweep_period, const int64_t* step_dev, int step_offset,
+                                                void* feed_dst, const void* feed_src, int64_t feed_bytes, recalgo_stream_t stream) {
+    const recalgo_scatter_source_t* src = static_cast<const recalgo_scatter_source_t*>(sources);
+    const recalgo_deferred_adam_t* d = static_cast<const recalgo_deferred_adam_t*>(deferred);
+    const recalgo_deferred_adam_t* d1 = static_cast<const recalgo_deferred_adam_t*>(companion_deferred);
+    const int fc = feed_check(feed_dst, feed_src, feed_bytes);
+    RECALGO_REQUIRE(fc >= 0 && n_sources >= 0 && n_sources <= kPrepSources && (n_sources == 0 || (src != nullptr && first_requests != nullptr)));
+    Feed feed;
+    if (fc > 0) { feed.dst = feed_dst; feed.src = feed_src; feed.bytes = (size_t)feed_bytes; }
+    const int64_t zero = 0;
+    if (n_sources <= 1)                                       // recalgo_scatter_prepare (a companion may ride)
+        return scatter_prepare_impl(src, (n_sources == 1 && src->n_ex > 0) ? 1 : 0, n_sources == 1 ? first_requests : &zero, K,
+                                    plan_workspace, plan_requests, nb_log2, flags, d, d1, rows, companion_rows, sweep_period, step_dev,
+                                    step_offset, stream, feed);
+    RECALGO_REQUIRE(d1 == nullptr && companion_rows == 0);    // recalgo_scatter_prepare_multi
+    for (int i = 0; i < n_sources; ++i) RECALGO_REQUIRE(src[i].n_ex > 0);
+    return scatter_prepare_impl(src, n_sources, first_requests, K, plan_workspace, plan_requests, nb_log2, flags, d, nullptr, rows, 0,
+                                sweep_period, step_dev, step_offset, stream, feed);
 }
 
 static int scatter_prepare_impl(const recalgo_scatter_source_t* source, int n_sources, const int64_t* first_requests, int K,
                                 void* plan_workspace, int64_t plan_requests, int nb_log2, int flags,
                                 const recalgo_deferred_adam_t* deferred, const recalgo_deferred_adam_t* companion_deferred,
                                 int64_t rows, int64_t companion_rows, int sweep_period, const int64_t* step_dev, int step_offset,
-                                recalgo_stream_t stream) {
+                                recalgo_stream_t stream, const Feed& feed) {
     RECALGO_REQUIRE(nb_ok(nb_log2) && plan_workspace != nullptr);
     RECALGO_REQUIRE(plan_requests >= 0 && plan_requests % kThreads == 0);
     RECALGO_REQUIRE(rows >= 0 && rows < (1ll << 31) && companion_rows >= 0 && companion_rows < (1ll << 31));
@@ -1538,7 +1596,17 @@ static int scatter_prepare_impl(const recalgo_scatter_source_t* source, int n_so
     A.b_comp = A.b_catch + comp_blocks;
     A.b_count = A.b_comp + count_blocks;
     A.b_sweep = A.b_count + sweep_blocks;
-    const unsigned blocks = A.b_sweep + sweep1_blocks;
+    A.b_copy = A.b_sweep + sweep1_blocks;
+    A.feed_dst = static_cast<unsigned char*>(feed.dst);
+    A.feed_src = static_cast<const unsigned char*>(feed.src);
+    A.feed_head = A.feed_n16 = 0;
+    A.feed_bytes = feed.dst != nullptr ? feed.bytes : 0;
+    unsigned copy_blocks = 0;
+    if (A.feed_bytes > 0) {
+        RECALGO_REQUIRE(recalgo_copy::copy_span_split(feed.dst, feed.src, A.feed_bytes, &A.feed_head, &A.feed_n16));
+        copy_blocks = recalgo_copy::copy_span_blocks(A.feed_n16);
+    }
+    const unsigned blocks = A.b_copy + copy_blocks;
     if (blocks == 0) return 0;
     const size_t smem = kSlots * 9 * sizeof(unsigned);        // (count tiles; the claim lists of the other workgroups are smaller)
     static_assert(kClaimsLdsBytes <= kSlots * 9 * sizeof(unsigned), "claim lists fit the count tiles' LDS");

@@ -17,7 +17,7 @@ from typing import Callable, Dict, Iterable, Optional
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .variables import VariableStore, use_store
 
 
@@ -599,6 +599,10 @@ def _clone_tree(obj):
     return walk(obj)
 
 
+# True: a captured step's first `prepare` launch is kept out of the graph and enqueued in front of every replay, where it also
+# moves a one-span batch into the static input buffers (sparse.StepHead) — no copy launch.  False (read when a step is captured):
+# everything inside the graph, the batch moved by a copy launch of its own (tests compare the two).
+FEED_IN_PREPARE = True
 HOUSEKEEPING_EVERY = 32      # steps between VariableStore.housekeeping() calls (live-row list ordering)
 OVERFLOW_POLL_EVERY = 64     # steps between reads of the static row-exchange overflow flag (N > 1; one host sync)
 
@@ -635,6 +639,9 @@ class GraphedTrainStep:
     # True (set by an Estimator with RunConfig(ragged_capacity=)): the static `values` of a Ragged is a buffer of fixed capacity,
     # and load() accepts the unpadded values of a device-resident batch that fit it
     pad_values = False
+    # the step's head (sparse.StepHead; None: every launch is a node of the graph) and the one-span load left to its next launch
+    _head = _feed = None
+    head_launches = fused_feeds = 0                           # head launches in front of a replay; ... that carried the batch
 
     def __init__(self, step_fn: Callable, features, labels, warmup: int = 3):
         self.step_fn = step_fn
@@ -664,10 +671,23 @@ class GraphedTrainStep:
         torch.cuda.synchronize()
         _quiesce_collectives()
         self.graph = torch.cuda.CUDAGraph()
-        # thread_local: HIP calls of OTHER threads (the RCCL watchdog of torch.distributed polls events)
-        # must not be treated as capture violations while this thread captures
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-            self.out = step_fn(features, labels)
+        # the step's head (sparse.HeadRecorder): its first `prepare` launch, when its ids are views of a static input allocation
+        from . import sparse
+        rec = None
+        if FEED_IN_PREPARE:
+            storages = {t.untyped_storage().data_ptr(): t.untyped_storage().nbytes() for _, t in self._static if t.is_cuda}
+            rec = sparse.HeadRecorder(storages.items())
+        prev, sparse.head_recorder = sparse.head_recorder, rec
+        try:
+            # thread_local: HIP calls of OTHER threads (the RCCL watchdog of torch.distributed polls events)
+            # must not be treated as capture violations while this thread captures
+            with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
+                self.out = step_fn(features, labels)
+        finally:
+            sparse.head_recorder = prev
+        if rec is not None:
+            self._head = rec.head
+        self._feed_ok = {}
         self.warmup_steps = warmup
         owner = getattr(step_fn, "__self__", None)                # Estimator.train_step -> its VariableStore
         self._housekeeping = getattr(getattr(owner, "store", None), "housekeeping", None)
@@ -676,10 +696,14 @@ class GraphedTrainStep:
     def load(self, features, labels):
         """Copy a new batch into the static input buffers.  Inputs that are views of one
         allocation with the same layout on both sides (the 26 id columns of one [B, F] matrix)
-        are moved by a single whole-allocation copy."""
+        are moved by a single whole-allocation copy — which a step with a head leaves to the head's launch in front of the
+        next replay (_feed_through_head): until that __call__ the static buffers hold the previous batch."""
         span = getattr(features, "device_span", None)
+        self._feed = None
         if span is not None and self._span_plan is not None and span[1] == self._span_plan[0]:
-            _device_copy(self._span_plan[1], span[0])
+            dst = self._span_plan[1]
+            if not self._feed_through_head(dst.data_ptr(), span[0], span[0].data_ptr(), dst.numel()):
+                _device_copy(dst, span[0])
             return
         new = list(_tree_tensors(features, "f")) + list(_tree_tensors(labels, "l"))
         if len(new) != len(self._static):
@@ -717,7 +741,8 @@ class GraphedTrainStep:
                         dv = torch.empty(0, dtype=torch.uint8, device=d0.device).set_(d0.untyped_storage(), d_lo, (d_hi - d_lo,), (1,))
                         self._dst_views[(spans[items[0][0]][0], d_lo, d_hi)] = dv
                     sv = torch.empty(0, dtype=torch.uint8, device=s0.device).set_(s0.untyped_storage(), s_lo, (d_hi - d_lo,), (1,))
-                    _device_copy(dv, sv)
+                    if not self._feed_through_head(dv.data_ptr(), sv, sv.data_ptr(), d_hi - d_lo):
+                        _device_copy(dv, sv)
                     continue
             singles.extend(i for i, _ in items)
         for i in singles:                        # (after every span copy: a per-tensor copy is never overwritten by one)
@@ -726,6 +751,24 @@ class GraphedTrainStep:
             # the values of a device-resident Ragged go into the static buffer of fixed capacity and the -1 tail is written
             # by the same launch (recalgo_ragged_pad)
             ops.ragged_pad(src.contiguous(), dst.numel(), out=dst)
+
+    def _feed_through_head(self, dst: int, keep: torch.Tensor, src: int, nbytes: int) -> bool:
+        """The one-copy load of static bytes [dst, dst + nbytes) from the caller's [src, ..): left to the step's head when the span
+        covers the ids of every source of the head and recalgo_scatter_prepare_feed accepts it — the next __call__ launches the
+        head on the caller's ids with the copy as workgroups of its grid (`keep` holds the caller's allocation until then)."""
+        h = self._head
+        if h is None or self._feed is not None or not (dst <= h.span_ptr + h.lo and h.span_ptr + h.hi <= dst + nbytes):
+            return False
+        ok = self._feed_ok.get((dst, src, nbytes))
+        if ok is None:
+            if len(self._feed_ok) >= 256:
+                self._feed_ok.clear()
+            ok = self._feed_ok[(dst, src, nbytes)] = (
+                dst != src and keep.is_cuda and keep.device == h.arena.weight.device and keep.is_contiguous()
+                and bool(_lib.load().recalgo_scatter_prepare_feed_supported(dst, src, nbytes)))
+        if ok:
+            self._feed = (dst, src, nbytes, keep)
+        return ok
 
     def _static_spans(self):
         """Per static input: (storage pointer, first byte, end byte, element size) — computed once: the per-step path of a
@@ -739,6 +782,11 @@ class GraphedTrainStep:
     def __call__(self, features=None, labels=None):
         if features is not None:
             self.load(features, labels)
+        if self._head is not None:
+            feed, self._feed = self._feed, None
+            self._head.launch(feed)
+            self.head_launches += 1
+            self.fused_feeds += feed is not None
         self.graph.replay()
         self._calls += 1
         if self._housekeeping is not None and self._calls % HOUSEKEEPING_EVERY == 0:
@@ -974,6 +1022,7 @@ class Estimator:
             pb = pb if pb is not None else self._packed_host_batch(features, labels)     # (the training loop passes its own)
             if pb is not None and pb[5] == plan[0] and plan[1].numel() == pb[4]:
                 self._h2d(pb[6], (pb[4],), torch.uint8, dst=plan[1])
+                graphed._feed = None             # (a load() left to the head would copy its batch over this one)
                 return graphed()
         features, labels = self._to_device(features, labels)
         return graphed(features, labels)

@@ -4,6 +4,9 @@ atomics, fused with the sparse optimizer) and the deferred-exact TF1 Adam state.
     forward of a lookup   begin_lookup(arena, ...)    registers the lookup's requests as a `Source`, launches
                                                       recalgo_scatter_prepare (ONE launch: bucket counts, catch-up of the
                                                       lookup's lagging rows, the step's share of the deferred-Adam sweep)
+    captured step         head_recorder / StepHead    the step's FIRST such launch stays out of the graph: enqueued in front of
+                                                      every replay (recalgo_scatter_prepare_feed), it reads the caller's ids
+                                                      and moves the batch into the static inputs by workgroups of its grid
     backward of a lookup  Source.set_grad(g)          records where the per-request gradient rows are
     optimizer             apply(arena, mode, ...)     recalgo_scatter_apply (two launches: place, apply) over all sources of the
                                                       arena (the prefix of the bucket counts rides on the dense optimizer
@@ -236,6 +239,91 @@ def deferred_view(arena, store):
     return ctypes.byref(d), ctypes.c_void_p(store.opt_state["step"].data_ptr())
 
 
+# ---- the head of a captured step: its first `prepare` launch, issued in front of every replay ---------------------------------------
+head_recorder = None         # a HeadRecorder while estimator.GraphedTrainStep captures (None otherwise)
+
+
+class StepHead:
+    """The first `prepare` launch of a captured step, kept OUT of the graph: GraphedTrainStep enqueues it in front of every replay
+    through recalgo_scatter_prepare_feed (include/recalgo_feed.h), so that it can read its ids from the CALLER's batch and move that
+    batch into the graph's static input span by workgroups of its own — the load of the step costs no launch.  The ctypes arguments
+    are built once; a launch patches the id pointers and the three feed arguments."""
+
+    def __init__(self, arena, entries, flags, d, d1, c_rows, step, span_ptr):
+        self.arena, self.span_ptr = arena, span_ptr
+        plan = plan_of(arena)
+        self.n = len(entries)
+        self._keep = (entries, d, d1, step, plan.ws)           # (what the pointers below point into)
+        self.arr = (_CSource * self.n)(*[cs for _, cs, _ in entries])
+        self.firsts = (ctypes.c_int64 * self.n)(*[first for _, _, first in entries])
+        self.static_ids = [src.ids.data_ptr() for src, _, _ in entries]
+        self.offs = [p - span_ptr for p in self.static_ids]    # byte offset of every source's ids inside the static span
+        self.lo = min(self.offs)
+        self.hi = max(o + src.ids.numel() * 8 for o, (src, _, _) in zip(self.offs, entries))
+        self.dst, self.src = ctypes.c_void_p(None), ctypes.c_void_p(None)
+        self.fn = _lib.load().recalgo_scatter_prepare_feed
+        self.args = [self.arr, self.n, self.firsts, arena.K, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity, plan.nb_log2, flags,
+                     None if d is None else ctypes.byref(d), None if d1 is None else ctypes.byref(d1), arena.weight.shape[0], c_rows,
+                     sweep_period(), None if step is None else ctypes.c_void_p(step.data_ptr()), 0, self.dst, self.src, 0, None]
+        self.fed = False
+
+    def launch(self, feed=None) -> None:
+        """feed = (static first byte, caller's first byte, bytes, ..) of a span that covers every source's ids, or None: the static
+        buffers are already filled."""
+        a = self.args
+        if feed is not None:
+            dst, src, n = feed[:3]
+            delta = src - dst
+            for i in range(self.n):
+                self.arr[i].ids = self.static_ids[i] + delta
+            self.dst.value, self.src.value, a[17] = dst, src, n
+            self.fed = True
+        elif self.fed:
+            for i in range(self.n):
+                self.arr[i].ids = self.static_ids[i]
+            self.src.value, a[17] = None, 0
+            self.fed = False
+        a[18] = _stream(self.arena.weight)
+        self.fn(*a)
+
+
+class HeadRecorder:
+    """Open around the capture of a step (GraphedTrainStep): the step's first `prepare` launch, if eligible, becomes its StepHead
+    instead of a node of the graph.  Eligible: every source a dense id matrix whose ids are a contiguous view inside ONE of the
+    step's static input allocations `spans` = [(first byte, bytes)], a local arena and a workspace this call did not have to
+    clear.  Whatever `prepare` launch comes first closes the recorder — every launch site of this module goes through take() or
+    close() —: at most one is hoisted, and only the step's first."""
+
+    def __init__(self, spans):
+        self.spans = [(int(p), int(n)) for p, n in spans]
+        self.head: Optional[StepHead] = None
+        self.closed = False
+
+    def close(self) -> None:
+        self.closed = True
+
+    def take(self, arena, entries, flags, d, d1, c_rows, step, clean: bool = True) -> bool:
+        """entries: [(Source, its c struct, first slot)] of ONE launch.  True: recorded, the caller launches nothing."""
+        if self.closed:
+            return False
+        self.closed = True
+        if not (clean and flags and 1 <= len(entries) <= MAX_PREPARE_SOURCES and (len(entries) == 1 or d1 is None)):
+            return False
+        if getattr(arena, "sharding", None) is not None or "__staged__" in getattr(arena, "tables", {}):
+            return False
+        at = entries[0][0].ids.data_ptr() if isinstance(entries[0][0].ids, torch.Tensor) else -1
+        lo, nbytes = next(((p, n) for p, n in self.spans if p <= at < p + n), (0, 0))
+        hi = lo + nbytes
+        for src, _, _ in entries:
+            ids = src.ids
+            if (src.offsets is not None or ids is None or src.n == 0 or ids.dtype != torch.int64 or not ids.is_contiguous()
+                    or not (lo <= ids.data_ptr() and ids.data_ptr() + ids.numel() * 8 <= hi)):
+                return False
+        # (whether a caller's span can be fed is decided per load, with both addresses: GraphedTrainStep._feed_through_head)
+        self.head = StepHead(arena, entries, flags, d, d1, c_rows, step, lo)
+        return True
+
+
 def begin_lookup(arena, store, ids: torch.Tensor, offsets: Optional[torch.Tensor], row_base: Optional[torch.Tensor],
                  base: int, n_ex: int, F: int, training: Optional[bool] = None, companion_arena=None,
                  can_defer: bool = False) -> Optional[Source]:
@@ -260,11 +348,14 @@ def begin_lookup(arena, store, ids: torch.Tensor, offsets: Optional[torch.Tensor
         return src
     lib = _lib.load()
     first = sum(s.slots for s in plan.sources)
+    clean = True                               # (nothing enqueued by this call that a hoisted launch would overtake: head_recorder)
     if plan.ws is None or first + src.slots > plan.capacity:
         # (a re-sized workspace starts with clean totals: the sources already counted are counted again by the optimizer's call)
         plan._ensure_ws(first + src.slots)
+        clean = False
     if plan.counted is None or plan.counted[:2] != (plan.ws.data_ptr(), plan.nb_log2):
         plan.clear_counts()
+        clean = False
     cs = src.c_struct(arena.K)
     # deferred Adam: the launch also brings the lookup's lagging rows up to date (claimed once per row, written back), so that
     # the forward kernel that follows — and `apply` at the end of the step — find them current; the first lookup of an arena
@@ -294,7 +385,9 @@ def begin_lookup(arena, store, ids: torch.Tensor, offsets: Optional[torch.Tensor
         # the model issues several lookups together (batch_lookups): ONE launch for all of an arena's at the end of the block; the
         # forward kernels of these lookups are enqueued behind it (ops: defer_launch)
         src.deferred = True
-        _batch["arenas"].setdefault(id(arena), (arena, plan, []))[2].append((src, cs, first, flags, d, step))
+        _batch["arenas"].setdefault(id(arena), (arena, plan, []))[2].append((src, cs, first, flags, d, step, clean))
+    elif flags and head_recorder is not None and head_recorder.take(arena, [(src, cs, first)], flags, d, d1, c_rows, step, clean):
+        pass                                   # (the captured step's head: GraphedTrainStep launches it in front of every replay)
     elif flags:
         lib.recalgo_scatter_prepare(ctypes.byref(cs), arena.K, ctypes.c_void_p(plan.ws.data_ptr()), plan.capacity, plan.nb_log2,
                                     first, flags, None if d is None else ctypes.byref(d),
@@ -367,8 +460,11 @@ def _flush_batch(b) -> None:
             step = next((e[5] for e in chunk if e[5] is not None), None)
             ws = ctypes.c_void_p(plan.ws.data_ptr())
             stp = None if step is None else ctypes.c_void_p(step.data_ptr())
-            if len(chunk) == 1:
-                _, cs, first, _, _, _ = chunk[0]
+            if head_recorder is not None and head_recorder.take(arena, [e[:3] for e in chunk], flags, d, None, 0, step,
+                                                                all(e[6] for e in chunk)):
+                prepare_stats["merged"] += len(chunk) - 1
+            elif len(chunk) == 1:
+                _, cs, first = chunk[0][:3]
                 lib.recalgo_scatter_prepare(ctypes.byref(cs), arena.K, ws, plan.capacity, plan.nb_log2, first, flags,
                                             None if d is None else ctypes.byref(d), None, arena.weight.shape[0], 0,
                                             sweep_period(), stp, 0, _stream(arena.weight))
@@ -525,6 +621,8 @@ def plan_scan_record(arena, lazy: bool):
 
 def _run(plan: ArenaPlan, sources: List[Source], mode: int, step_dev, step_offset: int, lr: float, live=None):
     lib = _lib.load()
+    if head_recorder is not None:
+        head_recorder.close()                  # (the optimizer's own prepare launches below: the step's forward is over)
     prescanned, plan.prescanned = plan.prescanned, None
     a = plan.arena
     comp_arena = _companion_arena(sources, mode)
