@@ -10,6 +10,9 @@ SURVEY.md §8f-3 sibling on the hot-path kernels:
     ONE launch of the gather kernel over F * (F-1) "virtual fields" (id + s * V_i inside the field's (F-1) * V_i-row
     table); a multi-valued field goes through `to_sparse_tensor` semantics (utils.py:49-64: the DISTINCT ids, mean);
   * sum over pairs i < j of <v_i[j-1], v_j[i]> (ffm.py:146-160): `recalgo_ffm_pairs_*`.
+The last two are `ops.ffm_interaction`.  That is its composed path (params["ffm_fused"] = False); by default, wherever they
+serve, the kernels of csrc/ffm.hip fetch the rows of every pair themselves, one launch each way, and a bag's distinct ids are
+found on the device in a launch of fixed shape — nothing synchronises, so a step with a bag field is captured.
 """
 from __future__ import annotations
 
@@ -47,20 +50,9 @@ example_parser = common.make_example_parser(lambda: (total_feature_columns, labe
 
 
 def _distinct_bags(x: Ragged) -> Ragged:
-    """utils.py:49-64 `to_sparse_tensor` of a multi-hot row: its DISTINCT valid ids, ascending."""
-    fc.data_dependent("FFM: the distinct ids of a bag (_distinct_bags) have a data-dependent count")
-    vals, offs = x.values, x.offsets
-    B = offs.numel() - 1
-    bag = torch.repeat_interleave(torch.arange(B, device=vals.device), offs[1:] - offs[:-1])
-    vals = vals[:bag.numel()]                                    # (a padded Ragged: the -1 tail belongs to no bag)
-    ok = vals >= 0
-    key = bag[ok] * (int(vals.max().item()) + 2 if vals.numel() else 1) + vals[ok]
-    uniq = torch.unique(key)                                     # sorted
-    mult = int(vals.max().item()) + 2 if vals.numel() else 1
-    ub, uv = torch.div(uniq, mult, rounding_mode="floor"), uniq % mult
-    counts = torch.zeros(B, dtype=torch.int64, device=vals.device).index_add_(0, ub, torch.ones_like(ub))
-    new_offs = torch.cat([torch.zeros(1, dtype=torch.int64, device=vals.device), counts.cumsum(0)])
-    return Ragged(uv.contiguous(), new_offs)
+    """utils.py:49-64 `to_sparse_tensor` of a multi-hot row: its DISTINCT valid ids, ascending (the composed path's form: its
+    shapes depend on the data; the fused path de-duplicates on the device, ops.ffm_bag_distinct)."""
+    return Ragged(*ops.ffm_distinct_bags_composed(x.values, x.offsets))
 
 
 def ffm_model_fn(features, labels, mode, params):
@@ -102,55 +94,37 @@ def ffm_model_fn(features, labels, mode, params):
     ids = [c.categorical_column.ids(features, dev) for c in cols]
     vocab = [int(v) for _, v in params["fields_vocabulary_size_tuple"]]
     single = [i for i, x in enumerate(ids) if not isinstance(x, Ragged)]
+    bags = {i: x for i, x in enumerate(ids) if isinstance(x, Ragged)}
+    # the field-aware term's kernels (ops.ffm_interaction) de-duplicate a bag on the device, in fixed shapes: its counts serve the
+    # first-order term too, and nothing below synchronises — the step captures.  The composed path (ffm_fused False, or a shape
+    # or arena the kernels do not serve) says fc.data_dependent and stays eager.
+    fused = ops.ffm_fused_serves(arena, F, K, len(bags), params.get("ffm_fused"))
+    if fused:
+        for i, x in bags.items():
+            kept, valid, distinct = ops.ffm_bag_distinct(x.values, x.offsets)
+            bags[i] = ops.FfmBag(kept, x.offsets, valid, distinct)
     # ---- first order ------------------------------------------------------------------------------------------
-    first = None
+    first = id1 = None
     if single:                                                   # every single-valued column in ONE gather of (B, n) weights
         rb1 = store.row_base_tensor(w1, [kprefix + cols[i].key for i in single])
         id1 = torch.stack([ids[i] for i in single], 1).contiguous()                                  # (B, n): both lookups' ids
         first = ops.embedding_gather(store, id1, w1, rb1).sum(dim=1, keepdim=True)                   # (B, 1)
-    for c, x in zip(cols, ids):
+    for i, (c, x) in enumerate(zip(cols, ids)):
         if not isinstance(x, Ragged):
             continue
         tn = kprefix + c.key
         mean = ops.embedding_bag_mean(store, x.values, x.offsets, w1, tn)                            # (B, 1)
-        lens = x.offsets[1:] - x.offsets[:-1]
-        bag = torch.repeat_interleave(torch.arange(B, device=dev), lens)
-        cnt = torch.zeros(B, device=dev).index_add_(0, bag, (x.values >= 0).float())
+        if fused:
+            cnt = bags[i].valid.to(torch.float32)
+        else:
+            lens = x.offsets[1:] - x.offsets[:-1]
+            bag = torch.repeat_interleave(torch.arange(B, device=dev), lens)
+            cnt = torch.zeros(B, device=dev).index_add_(0, bag, (x.values[:bag.numel()] >= 0).float())
         term = mean * cnt.unsqueeze(1)                           # counts: a repeated id counts twice (A-5)
         first = term if first is None else first + term
     first = first + bias.data                                    # (the bias gradient: sum of d logit, below)
-    # ---- field-aware lookups: X [B, F, F-1, K] ------------------------------------------------------------------
-    if single:
-        # view s of field i's (F-1, V, K) variable starts at arena row base_i + s * V_i: the F - 1 lookups of a field are the
-        # SAME id against F - 1 row bases (OOV stays -1), so the id matrix is one expanding copy, not 5 launches per field
-        key = (arena.name, "ffm_views", tuple(single))
-        rbv = store._rb_cache.get(key)
-        if rbv is None:
-            rbv = store._rb_cache[key] = torch.tensor([arena.tables[tnames[i]][0] + s * vocab[i] for i in single for s in range(F - 1)],
-                                                      dtype=torch.int64, device=dev)
-        idv = id1.unsqueeze(2).expand(B, len(single), F - 1).reshape(B, -1)
-        got = ops.embedding_gather(store, idv, arena, rbv)                                            # (B, n_single*(F-1)*K)
-    if len(single) == F:
-        X = got                                                  # all fields single-valued: the gather output IS X
-    else:
-        # runs of consecutive single-valued fields are one slice of the gather output each; a multi-valued field is F-1
-        # bag-mean lookups over its distinct ids
-        blocks, i, W = [], 0, (F - 1) * K
-        while i < F:
-            if isinstance(ids[i], Ragged):
-                d = _distinct_bags(ids[i])
-                blocks += [ops.embedding_bag_mean(store, torch.where(d.values >= 0, d.values + s * vocab[i], d.values),
-                                                  d.offsets, arena, tnames[i]) for s in range(F - 1)]
-                i += 1
-            else:
-                j = i
-                while j < F and not isinstance(ids[j], Ragged):
-                    j += 1
-                a = single.index(i)
-                blocks.append(got[:, a * W:(a + j - i) * W])
-                i = j
-        X = torch.cat(blocks, dim=1).contiguous()                # (B, F*(F-1)*K)
-    second = ops.ffm_pairs(X, F, K)                              # (B, 1)
+    # ---- field-aware lookups and the sum over pairs (ffm.py:146-160) -------------------------------------------------------
+    second = ops.ffm_interaction(store, id1, bags, arena, tnames, vocab, F, K, fused=fused)          # (B, 1)
     total_logit = _BiasGrad.apply(first, bias) + second
     return finish_model_fn(mode, total_logit, labels, params,
                            predictions=lambda prob: {"logit": total_logit, "probabilities": prob})

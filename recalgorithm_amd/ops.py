@@ -1260,6 +1260,230 @@ def ffm_pairs(x: torch.Tensor, F: int, K: int) -> torch.Tensor:
     return _FfmPairsFn.apply(x, int(F), int(K))
 
 
+# ---- FFM's field-aware term without its operand tensor (csrc/ffm.hip, include/recalgo_ffm.h) --------------------------------------
+_FFM = _lib.SERVING_HEADERS["recalgo_ffm.h"]
+_FfmField, _FfmBagC = _FFM.structs["recalgo_ffm_field_t"], _FFM.structs["recalgo_ffm_bag_t"]
+# fused=None with every field single-valued: the kernels, or the composed gather -> ffm_pairs chain.  Set from
+# scripts/bench_ffm.py (profiles/ffm_bench.json); with a bag field the kernels are the default either way: they are what makes the
+# step capturable.
+FFM_FUSED_ALL_SINGLE = True
+
+
+class FfmBag(NamedTuple):
+    """A bag field as ffm_bag_distinct left it: `values` de-duplicated ([capacity], dropped entries -1), the Ragged's `offsets`,
+    valid [B] int32 (entries with an id >= 0, a repeated id counted every time) and distinct [B] int32 (kept entries)."""
+    values: torch.Tensor
+    offsets: torch.Tensor
+    valid: torch.Tensor
+    distinct: torch.Tensor
+
+
+def ffm_supported(F: int, K: int, n_bags: int) -> bool:
+    return bool(_lib_().recalgo_ffm_supported(int(F), int(K), int(n_bags)))
+
+
+def ffm_bag_distinct(values: torch.Tensor, offsets: torch.Tensor):
+    """-> (values, valid, distinct) of recalgo_ffm_bag_distinct: the DISTINCT ids of every bag (utils.py:49-64
+    `to_sparse_tensor`) in place — an entry keeps its id when no earlier entry of its bag holds it, every other entry (a repeated
+    id, an OOV entry, the -1 tail of a padded Ragged) becomes -1 — and the two counts per bag.  One launch, shapes fixed by the
+    inputs' shapes alone, nothing read back."""
+    _chk(values, torch.int64, "ffm_bag_distinct: values")
+    _chk(offsets, torch.int64, "ffm_bag_distinct: offsets")
+    B = offsets.numel() - 1
+    if B < 1 or values.dim() != 1:
+        raise ValueError("ffm_bag_distinct: values [n] and offsets [B + 1] with B >= 1")
+    out = torch.empty_like(values)
+    valid = torch.empty(B, dtype=torch.int32, device=offsets.device)
+    distinct = torch.empty(B, dtype=torch.int32, device=offsets.device)
+    _lib_().recalgo_ffm_bag_distinct(_p(values) if values.numel() else None, _p(offsets), B, values.numel(),
+                                     _p(out) if values.numel() else None, _p(valid), _p(distinct), _stream(offsets))
+    return out, valid, distinct
+
+
+def ffm_distinct_bags_composed(values: torch.Tensor, offsets: torch.Tensor):
+    """-> (values, offsets) of the bags' DISTINCT valid ids, ascending per bag (utils.py:49-64), by torch.unique: the composed
+    path's form.  Its shapes depend on the data and it reads two values back: a model that comes here is not captured."""
+    from . import feature_column as fc
+    fc.data_dependent("FFM: the distinct ids of a bag (_distinct_bags) have a data-dependent count")
+    vals, offs = values, offsets
+    B = offs.numel() - 1
+    bag = torch.repeat_interleave(torch.arange(B, device=vals.device), offs[1:] - offs[:-1])
+    vals = vals[:bag.numel()]                                    # (a padded Ragged: the -1 tail belongs to no bag)
+    ok = vals >= 0
+    key = bag[ok] * (int(vals.max().item()) + 2 if vals.numel() else 1) + vals[ok]
+    uniq = torch.unique(key)                                     # sorted
+    mult = int(vals.max().item()) + 2 if vals.numel() else 1
+    ub, uv = torch.div(uniq, mult, rounding_mode="floor"), uniq % mult
+    counts = torch.zeros(B, dtype=torch.int64, device=vals.device).index_add_(0, ub, torch.ones_like(ub))
+    new_offs = torch.cat([torch.zeros(1, dtype=torch.int64, device=vals.device), counts.cumsum(0)])
+    return uv.contiguous(), new_offs
+
+
+def ffm_fused_serves(arena, F: int, K: int, n_bags: int, fused: Optional[bool] = None) -> bool:
+    """Whether ffm_interaction(.., fused) takes the kernels for a call in the current grad mode: a HIP device, a local arena, a
+    shape inside recalgo_ffm_supported and, when training a trainable arena, the owner-computes plan (sparse.py).  fused=None
+    asks for them wherever they serve (every field single-valued: where they were measured not to lose, FFM_FUSED_ALL_SINGLE);
+    fused=True raises where they do not serve; fused=False never takes them."""
+    if fused is False:
+        return False
+    why = None
+    if arena.weight is None or not arena.weight.is_cuda:
+        why = "the arena is not on a HIP device"
+    elif getattr(arena, "sharding", None) is not None or type(arena) is not EmbeddingArena:
+        why = "the arena is row-sharded"
+    elif arena.K != int(K) or not ffm_supported(F, K, n_bags):
+        c = _FFM.constants
+        why = (f"the kernels serve {c['RECALGO_FFM_MIN_F']} <= F <= {c['RECALGO_FFM_MAX_F']}, K % 4 == 0 with {c['RECALGO_FFM_MIN_K']} "
+               f"<= K <= {c['RECALGO_FFM_MAX_K']} and at most {c['RECALGO_FFM_MAX_BAGS']} bag fields; got F={F} K={K} bags={n_bags}")
+    elif torch.is_grad_enabled() and getattr(arena, "trainable", True) and not (sparse.scatter_mode() == "owner" and sparse._supported(arena)):
+        why = "training needs the arena on the owner-computes plan"
+    if why is None:
+        return True if (fused or n_bags) else bool(FFM_FUSED_ALL_SINGLE)
+    if fused:
+        raise ValueError(f"ffm_interaction(fused=True): {why}")
+    return False
+
+
+class _FfmFn(Function):
+    """include/recalgo_ffm.h recalgo_ffm_fwd / recalgo_ffm_bwd.  ids [B, n_single]; desc = (fields array, single-valued row bases
+    [n_single (F - 1)], per bag its row bases [F - 1], F, K); bags = [FfmBag] in the order of the fields.  Nothing is saved: the
+    backward fetches the rows again."""
+
+    @staticmethod
+    def forward(ctx, anchor, ids, arena: EmbeddingArena, desc, bags, training=False):
+        fields, rbv, rb_bags, F, K = desc
+        B = ids.shape[0] if ids is not None else bags[0].offsets.numel() - 1
+        ns = F - len(bags)
+        dev = arena.weight.device
+        st = anchor_store(anchor)
+        out = torch.empty(B, 1, device=dev, dtype=torch.float32)
+        # owner-computes scatter (sparse.py): ONE source for the single-valued requests — the id matrix against F - 1 row bases
+        # per field — and ONE per bag field — its entries against the field's F - 1 row bases
+        ctx.src, ctx.bag_srcs = None, []
+        registered = bool(training) and getattr(arena, "trainable", True)       # (ffm_fused_serves: then the arena is on the plan)
+        if registered and ns:
+            # (contiguous() before the reshape: with ONE single-valued field the expanded matrix reshapes to a stride-0 VIEW, and
+            # the scatter indexes its ids as a dense [B, n_single (F - 1)] matrix)
+            idv = ids.unsqueeze(2).expand(B, ns, F - 1).contiguous().view(B, -1)
+            ctx.src = sparse.begin_lookup(arena, st, idv, None, rbv, 0, B, ns * (F - 1), True)
+        if registered:
+            for bg, rb in zip(bags, rb_bags):
+                cap = bg.values.numel()
+                bid = bg.values.unsqueeze(1).expand(cap, F - 1).contiguous()
+                ctx.bag_srcs.append(sparse.begin_lookup(arena, st, bid, None, rb, 0, cap, F - 1, True) if cap else None)
+        # deferred Adam: registered lookups' rows were just caught up; any other call reads lagging rows as of now
+        dv, stp = (None, None) if registered else sparse.deferred_view(arena, st)
+        ctx.cbags = _ffm_bag_array(bags, None)
+        _lib_().recalgo_ffm_fwd(_p(ids), fields, ctx.cbags, len(bags), _p(arena.weight), B, F, K, _p(out), dv, stp, 0, _stream(out))
+        ctx.args = (ids, arena, desc, bags, B, registered)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ids, arena, (fields, _rbv, _rbb, F, K), bags, B, registered = ctx.args
+        if not registered:                   # (a frozen arena: nobody takes the rows)
+            return None, None, None, None, None, None
+        ns = F - len(bags)
+        W = (F - 1) * K
+        g = g.reshape(B)
+        g = g if g.is_contiguous() else g.contiguous()
+        d_single = torch.empty(B, ns * W, device=g.device, dtype=torch.float32) if ns else None
+        d_bags = [torch.empty(bg.values.numel(), W, device=g.device, dtype=torch.float32) for bg in bags]
+        cbags = _ffm_bag_array(bags, d_bags)
+        _lib_().recalgo_ffm_bwd(_p(g), _p(ids), fields, cbags, len(bags), _p(arena.weight), B, F, K, _p(d_single), _stream(g))
+        if ctx.src is not None:
+            ctx.src.set_grad(d_single)       # summed per row (and applied) by the optimizer's recalgo_scatter_apply
+        for src, d in zip(ctx.bag_srcs, d_bags):
+            if src is not None:
+                src.set_grad(d)
+        return None, None, None, None, None, None
+
+
+def _ffm_bag_array(bags, d_rows):
+    if not bags:
+        return None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    return (_FfmBagC * len(bags))(*[_FfmBagC(ptr(bg.values), bg.offsets.data_ptr(), bg.distinct.data_ptr(), bg.values.numel(),
+                                            None if d_rows is None else ptr(d_rows[k])) for k, bg in enumerate(bags)])
+
+
+def ffm_interaction(store, ids: Optional[torch.Tensor], bags, arena: EmbeddingArena, tables, vocab, F: int, K: int,
+                    fused: Optional[bool] = None) -> torch.Tensor:
+    """FFM's second-order term (ffm.py:146-160): [B, 1] = sum over the pairs i < j of <v_i[j - 1], v_j[i]>, v_i[s] the row of
+    field i in its sub-table s — view s of the arena table tables[i], an (F - 1, vocab[i], K) variable.
+      ids     [B, n_single] int64: the ids of the single-valued fields, in field order (id < 0: OOV, a zero row); None when
+              every field is a bag
+      bags    {field index: Ragged | FfmBag}: the multi-valued fields; such a field's row is the mean over the bag's DISTINCT
+              valid ids (utils.py:49-64)
+    fused (ffm_fused_serves): the kernels of csrc/ffm.hip — one launch each way that fetches the rows itself; the scatter gets ONE
+    source for the single-valued requests and one per bag field, and nothing on the way synchronises or has a data-dependent
+    shape — or (False) the composition gather / F - 1 bag means per bag field -> cat -> ffm_pairs."""
+    F, K = int(F), int(K)
+    bags = dict(bags or {})
+    single = [i for i in range(F) if i not in bags]
+    if len(tables) != F or len(vocab) != F or not all(0 <= i < F for i in bags) or (ids is None) != (not single):
+        raise ValueError("ffm_interaction: F tables and vocabulary sizes, bag fields inside [0, F), ids for the single-valued fields")
+    if single:
+        _chk(ids, torch.int64, "ffm_interaction: ids")
+        if ids.dim() != 2 or ids.shape[1] != len(single) or ids.shape[0] == 0:
+            raise ValueError(f"ffm_interaction: ids must be a non-empty [B, {len(single)}] matrix, got {tuple(ids.shape)}")
+    dev = arena.weight.device
+    if ffm_fused_serves(arena, F, K, len(bags), fused):
+        key = (arena.name, "ffm_fused", tuple(tables), tuple(int(v) for v in vocab), tuple(sorted(bags)))
+        desc = store._rb_cache.get(key)
+        if desc is None:
+            base = [arena.tables[t][0] for t in tables]
+            order = sorted(bags)
+            fields = (_FfmField * F)(*[_FfmField(base[i], int(vocab[i]), order.index(i) if i in bags else -1) for i in range(F)])
+            views = lambda i: [base[i] + s * int(vocab[i]) for s in range(F - 1)]
+            rbv = torch.tensor([r for i in single for r in views(i)], dtype=torch.int64, device=dev)
+            rb_bags = [torch.tensor(views(i), dtype=torch.int64, device=dev) for i in order]
+            desc = store._rb_cache[key] = (fields, rbv, rb_bags, F, K)
+        blist = []
+        for i in sorted(bags):
+            bg = bags[i]
+            if not isinstance(bg, FfmBag):
+                kept, valid, distinct = ffm_bag_distinct(bg.values, bg.offsets)
+                bg = FfmBag(kept, bg.offsets, valid, distinct)
+            blist.append(bg)
+        return _FfmFn.apply(store.anchor, ids, arena, desc, blist, torch.is_grad_enabled())
+    # ---- the composed path: X [B, F, F-1, K] in memory -----------------------------------------------------------------------------
+    B = ids.shape[0] if single else next(iter(bags.values())).offsets.numel() - 1
+    if single:
+        # view s of field i's (F-1, V, K) variable starts at arena row base_i + s * V_i: the F - 1 lookups of a field are the
+        # SAME id against F - 1 row bases (OOV stays -1), so the id matrix is one expanding copy, not 5 launches per field
+        key = (arena.name, "ffm_views", tuple(single))
+        rbv = store._rb_cache.get(key)
+        if rbv is None:
+            rbv = store._rb_cache[key] = torch.tensor([arena.tables[tables[i]][0] + s * int(vocab[i]) for i in single for s in range(F - 1)],
+                                                      dtype=torch.int64, device=dev)
+        idv = ids.unsqueeze(2).expand(B, len(single), F - 1).contiguous().view(B, -1)
+        got = embedding_gather(store, idv, arena, rbv)                                                # (B, n_single*(F-1)*K)
+    if len(single) == F:
+        X = got                                                  # all fields single-valued: the gather output IS X
+    else:
+        # runs of consecutive single-valued fields are one slice of the gather output each; a multi-valued field is F-1
+        # bag-mean lookups over its distinct ids
+        blocks, i, W = [], 0, (F - 1) * K
+        while i < F:
+            if i in bags:
+                if isinstance(bags[i], FfmBag):
+                    raise ValueError("ffm_interaction: the composed path takes a bag field as a Ragged")
+                dvals, doffs = ffm_distinct_bags_composed(bags[i].values, bags[i].offsets)
+                blocks += [embedding_bag_mean(store, torch.where(dvals >= 0, dvals + s * int(vocab[i]), dvals), doffs, arena, tables[i])
+                           for s in range(F - 1)]
+                i += 1
+            else:
+                j = i
+                while j < F and j not in bags:
+                    j += 1
+                a = single.index(i)
+                blocks.append(got[:, a * W:(a + j - i) * W])
+                i = j
+        X = torch.cat(blocks, dim=1).contiguous()                # (B, F*(F-1)*K)
+    return ffm_pairs(X, F, K)
+
+
 # =============================================================================================
 # context-MLP glue (csrc/mlp.hip): dense backward epilogue, BatchNorm training
 # =============================================================================================
