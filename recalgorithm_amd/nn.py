@@ -1218,3 +1218,24 @@ def afm_attention(fields: torch.Tensor, F: int, K: int, w: Variable, b: Variable
     att = dense_with(pairs.reshape(B * P, K), w, b, relu=True)                   # relu(pairs @ w + b)   (B*P, t)
     att = dense_with(att, h, None, relu=False)                                    # @ h                   (B*P, 1)
     return ops.attention_pool(pairs, att.reshape(B, P))                           # softmax over pairs, weighted sum (B, K)
+
+
+# ---- AutoInt's interacting layer (Song et al., CIKM 2019, eqs. 5-8) -------------------------------------------------------------------
+def interacting_layer(x: torch.Tensor, F: int, att_embedding_size: int, head_num: int, use_res: bool, index: int) -> torch.Tensor:
+    """One interacting layer over the F field rows of x [B, F * D]: multi-head self-attention over the fields, unscaled, with the
+    optional residual projection and a ReLU -> [B, F * head_num * att_embedding_size], head-major columns (the arithmetic:
+    include/recalgo_autoint.h; tests/autoint_ref.py is its float64 restatement).  Variables under the caller's scope, default
+    glorot-uniform: interacting_layer_<index>_w_query, _w_key, _w_value [head_num, D, att_embedding_size] and, with use_res,
+    _w_res [D, head_num * att_embedding_size].  One launch each way (ops.autoint_layer); sizes csrc/autoint.hip does not
+    serve are a ValueError — there is no composed path."""
+    from . import ops
+    store = current_store()
+    F, A, H = int(F), int(att_embedding_size), int(head_num)
+    if x.dim() != 2 or F < 1 or x.shape[1] % F:
+        raise ValueError(f"interacting_layer: x must be [B, F * D] with F = {F}, got {tuple(x.shape)}")
+    D = int(x.shape[1]) // F
+    ws = [store.get_variable(f"interacting_layer_{index}_w_{n}", (H, D, A)) for n in ("query", "key", "value")]
+    w_res = store.get_variable(f"interacting_layer_{index}_w_res", (D, H * A)) if use_res else None
+    if store.building:
+        return x.new_zeros(x.shape[0], F * H * A)
+    return ops.autoint_layer(x if x.is_contiguous() else x.contiguous(), F, *ws, w_res, anchor=store.anchor)

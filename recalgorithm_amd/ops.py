@@ -3032,6 +3032,81 @@ def afm_attention(fields: torch.Tensor, F: int, K: int, w, b, h, anchor=None) ->
 
 
 # =============================================================================================
+# AutoInt (csrc/autoint.hip, include/recalgo_autoint.h): one interacting layer — multi-head self-attention over the fields
+# =============================================================================================
+_CAI = _lib.SERVING_HEADERS["recalgo_autoint.h"].constants    # the RECALGO_AUTOINT_* #defines of include/recalgo_autoint.h
+
+
+def autoint_supported(F: int, D: int, A: int, H: int) -> bool:
+    return bool(_lib_().recalgo_autoint_supported(int(F), int(D), int(A), int(H)))
+
+
+class _AutoIntLayerFn(Function):
+    """include/recalgo_autoint.h recalgo_autoint_layer_fwd / recalgo_autoint_layer_bwd; params = (wq, wk, wv[, wres]), `tensors`
+    the same with None where params holds a Variable.  Saved: x and y (the backward recomputes everything between them)."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, F, differentiated, params, *tensors):
+        ts, vs = _bst_split(params)
+        B, (H, D, A) = x.shape[0], ts[0].shape
+        y = torch.empty(B, F * H * A, device=x.device, dtype=torch.float32)
+        wres = ts[3] if len(ts) == 4 else None
+        _lib_().recalgo_autoint_layer_fwd(_p(x), _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(wres), B, F, D, A, H, _p(y), _stream(x))
+        if differentiated:               # (the caller's grad mode: inside a Function's forward it is always off)
+            ctx.ts, ctx.vs, ctx.F = ts, vs, F
+            ctx.save_for_backward(x, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        ts, vs, F = ctx.ts, ctx.vs, ctx.F
+        x, y = ctx.saved_tensors
+        B, (H, D, A) = x.shape[0], ts[0].shape
+        g = g if g.is_contiguous() else g.contiguous()
+        lib = _lib_()
+        dx = torch.empty_like(x)
+        outs = _bst_grad_buffers(ts, vs)                 # dwq, dwk, dwv[, dwres]
+        has_res = len(ts) == 4
+        ws = _workspace(int(lib.recalgo_autoint_bwd_workspace_bytes(B, F, D, A, H, int(has_res))), x.device)
+        lib.recalgo_autoint_layer_bwd(_p(g), _p(x), _p(y), _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3] if has_res else None),
+                                      B, F, D, A, H, _p(dx), _p(outs[0]), _p(outs[1]), _p(outs[2]),
+                                      _p(outs[3] if has_res else None), _p(ws), _stream(x))
+        rets = [None if v is not None else o for o, v in zip(outs, vs)]
+        return (None, dx if ctx.needs_input_grad[1] else None, None, None, None, *rets)
+
+
+def autoint_layer(x: torch.Tensor, F: int, wq, wk, wv, wres=None, anchor=None) -> torch.Tensor:
+    """One AutoInt interacting layer (include/recalgo_autoint.h) as one launch each way: x [B, F * D] (contiguous fp32 on the
+    device), wq, wk, wv [H, D, A] and the optional residual projection wres [D, H * A] -> relu(concat_h softmax(Q_h K_h^T) V_h
+    + x Wres), [B, F * H * A] with head-major columns.  Each parameter is a Variable (gradient to Variable.grad, overwritten) or
+    a tensor.  With grad enabled the forward keeps x and y, nothing else; the backward is one launch and the fixed-order sum of
+    its partial rows.  Shapes the kernels do not serve (autoint_supported): ValueError — there is no fallback."""
+    F = int(F)
+    params = [wq, wk, wv] + ([wres] if wres is not None else [])
+    ts, _ = _bst_split(params)
+    if ts[0].dim() != 3:
+        raise ValueError(f"autoint_layer: wq must be [H, D, A], got {tuple(ts[0].shape)}")
+    H, D, A = (int(v) for v in ts[0].shape)
+    if not autoint_supported(F, D, A, H):
+        raise ValueError(f"autoint_layer: the kernels serve {_CAI['RECALGO_AUTOINT_MIN_F']} <= F <= {_CAI['RECALGO_AUTOINT_MAX_F']}, "
+                         f"D % 4 == 0 with {_CAI['RECALGO_AUTOINT_MIN_D']} <= D <= {_CAI['RECALGO_AUTOINT_MAX_D']}, A % 4 == 0 with "
+                         f"{_CAI['RECALGO_AUTOINT_MIN_A']} <= A <= {_CAI['RECALGO_AUTOINT_MAX_A']} and 1 <= H <= "
+                         f"{_CAI['RECALGO_AUTOINT_MAX_H']} with H * A <= {_CAI['RECALGO_AUTOINT_MAX_HA']}; got F={F} D={D} A={A} H={H} "
+                         f"(there is no fallback)")
+    if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] != F * D:
+        raise ValueError(f"autoint_layer: x must be a non-empty [B, F * D = {F * D}] matrix, got {tuple(x.shape)}")
+    for t, shape, name in zip(ts, ((H, D, A), (H, D, A), (H, D, A), (D, H * A)), ("wq", "wk", "wv", "wres")):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"autoint_layer: {name} has shape {tuple(t.shape)}, expected {shape}")
+    for t, name in zip([x] + ts, ("x", "wq", "wk", "wv", "wres")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != x.device:
+            raise ValueError(f"autoint_layer: {name} must be a contiguous float32 tensor on x's device, got {t.dtype} on {t.device}"
+                             f"{'' if t.is_contiguous() else ', not contiguous'}")
+    tensors = [None if isinstance(p, Variable) else p for p in params]
+    return _AutoIntLayerFn.apply(anchor, x, F, torch.is_grad_enabled(), params, *tensors)
+
+
+# =============================================================================================
 # DIEN (csrc/dien.hip, include/recalgo_dien.h): the GRU recurrence; attention + the AGRU / AUGRU recurrence
 # =============================================================================================
 _CD = _lib.MORE_HEADERS["recalgo_dien.h"].constants           # the RECALGO_DIEN_* #defines of include/recalgo_dien.h
