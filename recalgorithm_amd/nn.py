@@ -1239,3 +1239,53 @@ def interacting_layer(x: torch.Tensor, F: int, att_embedding_size: int, head_num
     if store.building:
         return x.new_zeros(x.shape[0], F * H * A)
     return ops.autoint_layer(x if x.is_contiguous() else x.contiguous(), F, *ws, w_res, anchor=store.anchor)
+
+
+# ---- DCN-V2's cross layer (Wang et al., WWW 2021, eq. 4) ---------------------------------------------------------------------------------
+def cross_mix_fused_default(x0: torch.Tensor, low_rank: int, num_experts: int) -> bool:
+    """What cross_mix_layer(fused=None) picks: the kernels wherever they serve the tensor and the shape (csrc/dcnv2.hip; the
+    measurement: DESIGN.md §5 "DCN-V2 cross layer")."""
+    from . import ops
+    return bool(isinstance(x0, torch.Tensor) and x0.dim() == 2 and x0.is_cuda and x0.dtype == torch.float32
+                and ops.dcnv2_supported(int(x0.shape[1]), int(low_rank), int(num_experts)))
+
+
+def cross_mix_layer(x0: torch.Tensor, xl: torch.Tensor, low_rank: int, num_experts: int, index: int, fused=None) -> torch.Tensor:
+    """One DCN-V2 cross layer, the mixture of `num_experts` low-rank experts of rank `low_rank` with a softmax gate over xl (the
+    arithmetic: include/recalgo_dcnv2.h; tests/dcnv2_ref.py is its float64 restatement):
+        x0 * sum_e p_e (tanh(tanh(xl V_e) C_e) U_e^T + bias) + xl,   p = softmax_e(xl . gate_e)
+    Variables under the caller's scope: cross_layer_<index>/V, U [E, D, r], C [E, r, r], gate [E, D] (default glorot-uniform) and
+    bias [D] (zeros).  fused (not a paper argument), in the manner of residual_stack: True runs ops.dcnv2_layer, one entry each way
+    (csrc/dcnv2.hip), and is a ValueError where the kernels do not serve the shape; False runs the layer composed from torch ops —
+    the path the bench compares against, and the one for shapes outside the kernels' domain; None takes the kernels wherever True
+    would succeed (cross_mix_fused_default)."""
+    from . import ops
+    store = current_store()
+    D, r, E = int(x0.shape[-1]), int(low_rank), int(num_experts)
+    with store.variable_scope(f"cross_layer_{index}"):
+        V, C, U = store.get_variable("V", (E, D, r)), store.get_variable("C", (E, r, r)), store.get_variable("U", (E, D, r))
+        gate = store.get_variable("gate", (E, D))
+        bias = store.get_variable("bias", (D,), zeros)
+    if store.building:
+        return torch.zeros_like(x0)
+    if fused is None:
+        fused = cross_mix_fused_default(x0, r, E)
+    if fused:
+        same = xl is x0
+        x0 = x0 if x0.is_contiguous() else x0.contiguous()
+        return ops.dcnv2_layer(x0, x0 if same else (xl if xl.is_contiguous() else xl.contiguous()), V, C, U, gate, bias,
+                               anchor=store.anchor)
+    Vt, Ct, Ut, gt, bt = (ops.variable_leaf(v, store.anchor) for v in (V, C, U, gate, bias))
+    v = torch.tanh(torch.einsum("bd,edr->ber", xl, Vt))
+    c = torch.tanh(torch.einsum("ber,ers->bes", v, Ct))
+    u = torch.einsum("ber,edr->bed", c, Ut) + bt
+    p = torch.softmax(xl @ gt.t(), dim=-1)
+    return x0 * torch.einsum("be,bed->bd", p, u) + xl
+
+
+def cross_mix_network(x0: torch.Tensor, num_cross_layer: int, low_rank: int, num_experts: int, fused=None) -> torch.Tensor:
+    """x_{l+1} = cross_mix_layer(x0, x_l, l) for l = 0 .. num_cross_layer - 1, x_0 = x0: one entry each way per layer."""
+    xl = x0
+    for i in range(int(num_cross_layer)):
+        xl = cross_mix_layer(x0, xl, low_rank, num_experts, i, fused=fused)
+    return xl

@@ -3107,6 +3107,112 @@ def autoint_layer(x: torch.Tensor, F: int, wq, wk, wv, wres=None, anchor=None) -
 
 
 # =============================================================================================
+# DCN-V2 (csrc/dcnv2.hip, include/recalgo_dcnv2.h): one cross layer — the mixture of low-rank experts with a softmax gate
+# =============================================================================================
+_CDX = _lib.SERVING_HEADERS["recalgo_dcnv2.h"].constants      # the RECALGO_DCNV2_* #defines of include/recalgo_dcnv2.h
+
+
+def dcnv2_supported(D: int, r: int, E: int) -> bool:
+    return bool(_lib_().recalgo_dcnv2_supported(int(D), int(r), int(E)))
+
+
+class _Dcnv2LayerFn(Function):
+    """include/recalgo_dcnv2.h recalgo_dcnv2_layer_fwd / recalgo_dcnv2_layer_bwd; params = (V, C, U, gate | None, bias), `tensors`
+    the same with None where params holds a Variable.  Saved: x0 and xl (the backward recomputes everything from them).  `same`:
+    xl IS x0 (a stack's first layer) — x0 is passed once and receives dx0 + dxl."""
+
+    @staticmethod
+    def forward(ctx, anchor, x0, xl, differentiated, params, *tensors):
+        same = xl is None
+        xl = x0 if same else xl
+        gated = params[3] is not None
+        ts, vs = _bst_split([p for p in params if p is not None])
+        B, (E, D, r) = x0.shape[0], ts[0].shape
+        y = torch.empty_like(x0)
+        gate, bias = (ts[3], ts[4]) if gated else (None, ts[3])
+        _lib_().recalgo_dcnv2_layer_fwd(_p(x0), _p(xl), _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(gate), _p(bias), B, D, r, E, _p(y),
+                                        _stream(x0))
+        if differentiated:               # (the caller's grad mode: inside a Function's forward it is always off)
+            ctx.ts, ctx.vs, ctx.gated, ctx.same = ts, vs, gated, same
+            ctx.save_for_backward(x0, xl)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        ts, vs, gated, same = ctx.ts, ctx.vs, ctx.gated, ctx.same
+        x0, xl = ctx.saved_tensors
+        B, (E, D, r) = x0.shape[0], ts[0].shape
+        g = g if g.is_contiguous() else g.contiguous()
+        lib = _lib_()
+        dx0, dxl = torch.empty_like(x0), torch.empty_like(xl)
+        outs = _bst_grad_buffers(ts, vs)                 # dV, dC, dU[, dgate], dbias
+        gate, bias = (ts[3], ts[4]) if gated else (None, ts[3])
+        dgate, dbias = (outs[3], outs[4]) if gated else (None, outs[3])
+        ws = _workspace(int(lib.recalgo_dcnv2_bwd_workspace_bytes(B, D, r, E)), x0.device)
+        lib.recalgo_dcnv2_layer_bwd(_p(g), _p(x0), _p(xl), _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(gate), _p(bias), B, D, r, E,
+                                    _p(dx0), _p(dxl), _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(dgate), _p(dbias), _p(ws),
+                                    _stream(x0))
+        rets = [None if v is not None else o for o, v in zip(outs, vs)]
+        if not gated:
+            rets.insert(3, None)
+        if same:
+            return (None, dx0.add_(dxl) if ctx.needs_input_grad[1] else None, None, None, None, *rets)
+        return (None, dx0 if ctx.needs_input_grad[1] else None, dxl if ctx.needs_input_grad[2] else None, None, None, *rets)
+
+
+def dcnv2_layer(x0: torch.Tensor, xl: torch.Tensor, V, C, U, gate, bias, anchor=None) -> torch.Tensor:
+    """One DCN-V2 cross layer (include/recalgo_dcnv2.h), the mixture of E low-rank experts, as one entry each way: x0, xl
+    [B, D] (contiguous fp32 on the device; xl may BE x0, a stack's first layer), V, U [E, D, r], C [E, r, r], gate [E, D] (None
+    with E == 1: the plain low-rank layer) and bias [D] -> x0 * sum_e p_e (tanh(tanh(xl V_e) C_e) U_e^T + bias) + xl with
+    p = softmax(xl gate^T).  Each parameter is a Variable (gradient to Variable.grad, overwritten) or a tensor.  With grad enabled
+    the forward keeps x0 and xl, nothing else; the backward recomputes from them and sums its partial rows in fixed order.
+    Shapes the kernels do not serve (dcnv2_supported): ValueError — the composed layer is nn.cross_mix_layer(fused=False)."""
+    params = [V, C, U, gate, bias]
+    ts, _ = _bst_split([p for p in params if p is not None])
+    if ts[0].dim() != 3:
+        raise ValueError(f"dcnv2_layer: V must be [E, D, r], got {tuple(ts[0].shape)}")
+    E, D, r = (int(v) for v in ts[0].shape)
+    if not dcnv2_supported(D, r, E):
+        raise ValueError(f"dcnv2_layer: the kernels serve {_CDX['RECALGO_DCNV2_MIN_D']} <= D <= {_CDX['RECALGO_DCNV2_MAX_D']}, "
+                         f"r % 4 == 0 with {_CDX['RECALGO_DCNV2_MIN_R']} <= r <= {_CDX['RECALGO_DCNV2_MAX_R']} and 1 <= E <= "
+                         f"{_CDX['RECALGO_DCNV2_MAX_E']}; got D={D} r={r} E={E} (nn.cross_mix_layer(fused=False) is the composed layer)")
+    if gate is None and E != 1:
+        raise ValueError(f"dcnv2_layer: only a single expert runs without a gate, got E={E}")
+    if x0.dim() != 2 or x0.shape[0] == 0 or x0.shape[1] != D or tuple(xl.shape) != tuple(x0.shape):
+        raise ValueError(f"dcnv2_layer: x0 and xl must be non-empty [B, D = {D}] matrices, got {tuple(x0.shape)} and {tuple(xl.shape)}")
+    names = ("V", "C", "U") + (("gate",) if gate is not None else ()) + ("bias",)
+    shapes = ((E, D, r), (E, r, r), (E, D, r)) + (((E, D),) if gate is not None else ()) + ((D,),)
+    for t, shape, name in zip(ts, shapes, names):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"dcnv2_layer: {name} has shape {tuple(t.shape)}, expected {shape}")
+    for t, name in zip([x0, xl] + ts, ("x0", "xl") + names):
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != x0.device:
+            raise ValueError(f"dcnv2_layer: {name} must be a contiguous float32 tensor on x0's device, got {t.dtype} on {t.device}"
+                             f"{'' if t.is_contiguous() else ', not contiguous'}")
+    tensors = [None if (p is None or isinstance(p, Variable)) else p for p in params]
+    return _Dcnv2LayerFn.apply(anchor, x0, None if xl is x0 else xl, torch.is_grad_enabled(), params, *tensors)
+
+
+class _VariableLeafFn(Function):
+    """A Variable as a leaf of a chain composed from torch ops: forward gives its data, backward OVERWRITES Variable.grad (the
+    convention of every parameter-owning op here; a variable is read once per step)."""
+
+    @staticmethod
+    def forward(ctx, anchor, var):
+        ctx.var = var
+        return var.data.view_as(var.data)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.var.grad.copy_(g)
+        return None, None
+
+
+def variable_leaf(var, anchor) -> torch.Tensor:
+    return _VariableLeafFn.apply(anchor, var) if isinstance(var, Variable) else var
+
+
+# =============================================================================================
 # DIEN (csrc/dien.hip, include/recalgo_dien.h): the GRU recurrence; attention + the AGRU / AUGRU recurrence
 # =============================================================================================
 _CD = _lib.MORE_HEADERS["recalgo_dien.h"].constants           # the RECALGO_DIEN_* #defines of include/recalgo_dien.h
