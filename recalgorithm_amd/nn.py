@@ -1289,3 +1289,76 @@ def cross_mix_network(x0: torch.Tensor, num_cross_layer: int, low_rank: int, num
     for i in range(int(num_cross_layer)):
         xl = cross_mix_layer(x0, xl, low_rank, num_experts, i, fused=fused)
     return xl
+
+
+# ---- FLEN's field-wise bi-interaction with Dicefactor (Chen et al., arXiv 1911.04690) -----------------------------------------------
+def flen_fused_default(fields: torch.Tensor, F: int, M: int, K: int) -> bool:
+    """What field_wise_bi_interaction(fused=None) picks: the kernels wherever they serve the tensor and the shape (csrc/flen.hip;
+    the measurement: DESIGN.md §5 "FLEN field-wise bi-interaction" — they were the faster path at every measured shape class)."""
+    from . import ops
+    return bool(isinstance(fields, torch.Tensor) and fields.dim() == 2 and fields.is_cuda and fields.dtype == torch.float32
+                and ops.flen_supported(int(F), int(M), int(K)))
+
+
+_flen_index_cache: dict = {}
+
+
+def _flen_indices(group_of: tuple, M: int, device):
+    """the composed path's index tensors — each group's fields, the pairs' first and second groups — made once per (grouping,
+    device): a captured step's replays find them on the device"""
+    from itertools import combinations
+    key = (group_of, str(device))
+    if key not in _flen_index_cache:
+        members = [torch.tensor([f for f, g in enumerate(group_of) if g == m], device=device) for m in range(M)]
+        first, second = (torch.tensor(ix, device=device) for ix in zip(*combinations(range(M), 2)))
+        _flen_index_cache[key] = (members, first, second)
+    return _flen_index_cache[key]
+
+
+def field_wise_bi_interaction(fields: torch.Tensor, group_of, dice_rate: float = 0.0, training: bool = False, fused=None):
+    """FLEN's field-wise bi-interaction over the F = len(group_of) field rows of fields [B, F * K]; group_of[f] in [0, M) is
+    field f's group and every group holds a field (the arithmetic: include/recalgo_flen.h; tests/flen_ref.py is its float64
+    restatement) -> (e [B, M * K], h [B, K]):
+        e_m = sum of group m's rows      h = bias + sum_{i<j} r_mf[p] c_p e_i e_j + sum_m r_fm[m] c_{P+m} (e_m^2 - sum x_f^2)
+    Variables under the caller's scope: r_mf [M (M - 1) / 2] (ones), r_fm [M] (0.5) and bias [K] (zeros).  Dicefactor: when
+    training with dice_rate > 0 the [B, P + M, K] path components are dropped like any other dropout of the model_fn (drop_spec:
+    the next call of the hash stream, or the next injected keep mask) and scaled by 1 / (1 - rate); EVAL and PREDICT apply none.
+    fused (not a paper argument), as in cross_mix_layer: True runs ops.flen_interaction, one launch each way, and is a ValueError
+    where the kernels do not serve; False runs the arithmetic composed from torch ops — the path the bench compares against, and
+    the one outside the kernels' domain; None takes the kernels wherever True would succeed (flen_fused_default)."""
+    from . import ops
+    from .variables import constant
+    store = current_store()
+    group_of = tuple(int(g) for g in group_of)
+    F = len(group_of)
+    M = max(group_of) + 1 if group_of else 0
+    if F < 2 or M < 2 or set(group_of) != set(range(M)):
+        raise ValueError(f"field_wise_bi_interaction: group_of must map at least two fields onto every one of M >= 2 groups "
+                         f"0 .. M - 1, got {group_of}")
+    if fields.dim() != 2 or fields.shape[1] % F:
+        raise ValueError(f"field_wise_bi_interaction: fields must be [B, F * K] with F = {F}, got {tuple(fields.shape)}")
+    B, K = int(fields.shape[0]), int(fields.shape[1]) // F
+    P = M * (M - 1) // 2
+    r_mf = store.get_variable("r_mf", (P,), ones)
+    r_fm = store.get_variable("r_fm", (M,), constant(0.5))
+    bias = store.get_variable("bias", (K,), zeros)
+    if store.building:
+        return fields.new_zeros(B, M * K), fields.new_zeros(B, K)
+    if fused is None:
+        fused = flen_fused_default(fields, F, M, K)
+    elif fused and not flen_fused_default(fields, F, M, K):
+        raise ValueError(f"field_wise_bi_interaction(fused=True): no fused kernel serves F={F} M={M} K={K} on {fields.device}")
+    dice = drop_spec((B, P + M, K), float(dice_rate), fields.device) if (training and dice_rate and dice_rate > 0.0) else None
+    if fused:
+        return ops.flen_interaction(fields if fields.is_contiguous() else fields.contiguous(), F, group_of, r_mf, r_fm, bias,
+                                    dice=dice, anchor=store.anchor)
+    mf_w, fm_w, b = (ops.variable_leaf(v, store.anchor) for v in (r_mf, r_fm, bias))
+    x = fields.reshape(B, F, K)
+    members, first, second = _flen_indices(group_of, M, fields.device)
+    e = torch.stack([x.index_select(1, idx).sum(1) for idx in members], dim=1)                          # [B, M, K]
+    q = torch.stack([x.index_select(1, idx).square().sum(1) for idx in members], dim=1)
+    paths = torch.cat([mf_w[:, None] * (e.index_select(1, first) * e.index_select(1, second)), fm_w[:, None] * (e * e - q)], dim=1)
+    if dice is not None:
+        keep = dice.mask if dice.mask is not None else ops.dropout_keep_mask((B, P + M, K), dice, fields.device)
+        paths = paths * (keep * dice.scale)
+    return e.reshape(B, M * K), b + paths.sum(1)

@@ -3193,6 +3193,103 @@ def dcnv2_layer(x0: torch.Tensor, xl: torch.Tensor, V, C, U, gate, bias, anchor=
     return _Dcnv2LayerFn.apply(anchor, x0, None if xl is x0 else xl, torch.is_grad_enabled(), params, *tensors)
 
 
+# =============================================================================================
+# FLEN (csrc/flen.hip, include/recalgo_flen.h): the field-wise bi-interaction with Dicefactor
+# =============================================================================================
+_CFL = _lib.SERVING_HEADERS["recalgo_flen.h"].constants       # the RECALGO_FLEN_* #defines of include/recalgo_flen.h
+
+
+def flen_supported(F: int, M: int, K: int) -> bool:
+    return bool(_lib_().recalgo_flen_supported(int(F), int(M), int(K)))
+
+
+def _flen_groups(group_of):
+    """-> the HOST int32 array the entries read at launch time"""
+    return (ctypes.c_int32 * len(group_of))(*group_of)
+
+
+class _FlenFn(Function):
+    """include/recalgo_flen.h recalgo_flen_fwd / recalgo_flen_bwd; params = (r_mf, r_fm, bias), `tensors` the same with None
+    where params holds a Variable.  Saved: x alone (the backward recomputes e and q, and the Dicefactor mask from its key)."""
+
+    @staticmethod
+    def forward(ctx, anchor, x, F, group_of, dice, differentiated, params, *tensors):
+        ts, vs = _bst_split(params)
+        B, M, K = x.shape[0], ts[1].shape[0], ts[2].shape[0]
+        e = torch.empty(B, M * K, device=x.device, dtype=torch.float32)
+        h = torch.empty(B, K, device=x.device, dtype=torch.float32)
+        groups = _flen_groups(group_of)
+        cd, keep = _cdrop(dice)
+        _lib_().recalgo_flen_fwd(_p(x), ctypes.cast(groups, ctypes.c_void_p), _p(ts[0]), _p(ts[1]), _p(ts[2]), cd, B, F, M, K,
+                                 _p(e), _p(h), _stream(x))
+        del keep
+        if differentiated:               # (the caller's grad mode: inside a Function's forward it is always off)
+            ctx.ts, ctx.vs, ctx.F, ctx.group_of, ctx.dice = ts, vs, F, group_of, dice
+            ctx.save_for_backward(x)
+        return e, h
+
+    @staticmethod
+    def backward(ctx, g_e, g_h):         # (the gradient of an output nobody used arrives as zeros)
+        ts, vs, F = ctx.ts, ctx.vs, ctx.F
+        x, = ctx.saved_tensors
+        B, M, K = x.shape[0], ts[1].shape[0], ts[2].shape[0]
+        g_e = g_e if g_e.is_contiguous() else g_e.contiguous()
+        g_h = g_h if g_h.is_contiguous() else g_h.contiguous()
+        lib = _lib_()
+        dx = torch.empty_like(x)
+        outs = _bst_grad_buffers(ts, vs)                 # dr_mf, dr_fm, dbias
+        groups = _flen_groups(ctx.group_of)
+        cd, keep = _cdrop(ctx.dice)
+        ws = _workspace(int(lib.recalgo_flen_bwd_workspace_bytes(B, F, M, K)), x.device)
+        lib.recalgo_flen_bwd(_p(g_e), _p(g_h), _p(x), ctypes.cast(groups, ctypes.c_void_p), _p(ts[0]), _p(ts[1]), cd, B, F, M, K,
+                             _p(dx), _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(ws), _stream(x))
+        del keep
+        rets = [None if v is not None else o for o, v in zip(outs, vs)]
+        return (None, dx if ctx.needs_input_grad[1] else None, None, None, None, None, None, *rets)
+
+
+def flen_interaction(fields: torch.Tensor, F: int, group_of, r_mf, r_fm, bias, dice: Optional["DropSpec"] = None, anchor=None):
+    """FLEN's field-wise bi-interaction (include/recalgo_flen.h) as one launch each way: fields [B, F * K] (contiguous fp32 on
+    the device), group_of the F group indices in [0, M), r_mf [M (M - 1) / 2], r_fm [M] and bias [K] -> (e [B, M * K], the
+    field-wise embeddings, h [B, K], the MF term across the groups plus the FM term inside each).  `dice`: the DropSpec of
+    Dicefactor over the [B, P + M, K] path components (None: none).  Each parameter is a Variable (gradient to Variable.grad,
+    overwritten) or a tensor.  With grad enabled the forward keeps `fields`, nothing else; the backward is one launch and the
+    fixed-order sum of its partial rows.  Shapes the kernels do not serve (flen_supported), an empty group or a group index
+    outside [0, M): ValueError — the composed arithmetic is nn.field_wise_bi_interaction(fused=False)."""
+    F = int(F)
+    group_of = tuple(int(g) for g in group_of)
+    params = [r_mf, r_fm, bias]
+    ts, _ = _bst_split(params)
+    if ts[1].dim() != 1 or ts[2].dim() != 1:
+        raise ValueError(f"flen_interaction: r_fm must be [M] and bias [K], got {tuple(ts[1].shape)} and {tuple(ts[2].shape)}")
+    M, K = int(ts[1].shape[0]), int(ts[2].shape[0])
+    P = M * (M - 1) // 2
+    if not flen_supported(F, M, K):
+        raise ValueError(f"flen_interaction: the kernels serve {_CFL['RECALGO_FLEN_MIN_F']} <= F <= {_CFL['RECALGO_FLEN_MAX_F']}, "
+                         f"{_CFL['RECALGO_FLEN_MIN_M']} <= M <= min(F, {_CFL['RECALGO_FLEN_MAX_M']}) and K % 4 == 0 with "
+                         f"{_CFL['RECALGO_FLEN_MIN_K']} <= K <= {_CFL['RECALGO_FLEN_MAX_K']}; got F={F} M={M} K={K} "
+                         f"(nn.field_wise_bi_interaction(fused=False) is the composed arithmetic)")
+    if len(group_of) != F or set(group_of) != set(range(M)):
+        raise ValueError(f"flen_interaction: group_of must map the F={F} fields onto every one of the M={M} groups, got {group_of}")
+    if fields.dim() != 2 or fields.shape[0] == 0 or fields.shape[1] != F * K:
+        raise ValueError(f"flen_interaction: fields must be a non-empty [B, F * K = {F * K}] matrix, got {tuple(fields.shape)}")
+    for t, shape, name in zip(ts, ((P,), (M,), (K,)), ("r_mf", "r_fm", "bias")):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"flen_interaction: {name} has shape {tuple(t.shape)}, expected {shape}")
+    for t, name in zip([fields] + ts, ("fields", "r_mf", "r_fm", "bias")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != fields.device:
+            raise ValueError(f"flen_interaction: {name} must be a contiguous float32 tensor on fields' device, got {t.dtype} on "
+                             f"{t.device}{'' if t.is_contiguous() else ', not contiguous'}")
+    if dice is not None:
+        if not 0.0 < dice.rate < 1.0:
+            raise ValueError(f"flen_interaction: the Dicefactor rate must lie in (0, 1), got {dice.rate}")
+        if fields.shape[0] * (P + M) * K >= 1 << 32:
+            raise ValueError("flen_interaction: Dicefactor indexes B (P + M) K < 2^32 path components")
+        dice.check_mask((fields.shape[0], P + M, K))
+    tensors = [None if isinstance(p, Variable) else p for p in params]
+    return _FlenFn.apply(anchor, fields, F, group_of, dice, torch.is_grad_enabled(), params, *tensors)
+
+
 class _VariableLeafFn(Function):
     """A Variable as a leaf of a chain composed from torch ops: forward gives its data, backward OVERWRITES Variable.grad (the
     convention of every parameter-owning op here; a variable is read once per step)."""

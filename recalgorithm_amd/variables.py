@@ -80,6 +80,13 @@ def ones(shape, gen=None):
     return torch.ones(*shape)
 
 
+def constant(value: float) -> Callable:
+    """tf.constant_initializer(value)"""
+    def init(shape, gen=None):
+        return torch.full(tuple(shape), float(value))
+    return init
+
+
 class VariableStore:
     def __init__(self, device: torch.device | str = "cpu", seed: int = 42):
         self.device = torch.device(device)
