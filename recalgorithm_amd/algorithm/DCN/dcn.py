@@ -38,6 +38,7 @@ flags.DEFINE_float("learning_rate", 0.005, "Learning rate")
 flags.DEFINE_string("hidden_units", "512,256,128", "Comma-separated list of number of units in each hidden layer")
 flags.DEFINE_integer("num_cross_layer", 1, "Number of cross layers")
 common.define_ragged_capacity_flag()
+common.define_group_auc_flags()
 FLAGS = flags.FLAGS
 
 DENSE_FEATURES = [  # dcn.py:59-76 (list order; input_layer sorts by name)
@@ -131,6 +132,7 @@ def main(unused_argv):
         "hidden_units": FLAGS.hidden_units.split(","),
         "num_cross_layer": FLAGS.num_cross_layer,
         "learning_rate": FLAGS.learning_rate,
+        **common.group_auc_params_from_flags(total_feature_columns),
     }
     print(params)
     estimator = Estimator(model_fn=dcn_model_fn, params=params,

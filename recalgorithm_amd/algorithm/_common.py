@@ -41,9 +41,33 @@ def ragged_capacity_from_flags():
     return None if n == 0 else "auto" if n == -1 else n
 
 
+def define_group_auc_flags():
+    """--group_auc_key, --group_auc_weighting (not reference flags): the per-user AUC of evaluate(), see group_auc_params_from_flags"""
+    flags.DEFINE_string("group_auc_key", "", "Categorical feature whose ids group the rows of a per-group AUC in evaluation, "
+                        "e.g. userid: eval_uauc, the mean over the users of each user's own AUC (empty: off)")
+    flags.DEFINE_enum("group_auc_weighting", "uniform", ["uniform", "samples"], "uniform: every user with a positive and a "
+                      "negative row counts once (uAUC); samples: weighted by the user's rows (GAUC, reported as eval_gauc)")
+
+
+def group_auc_params_from_flags(columns) -> dict:
+    """--group_auc_key / --group_auc_weighting as the model tails take them (model_tail.group_auc_metric_ops): {} when the flag
+    is empty (or the script does not have it), else the key, the weighting and the number of groups — the vocabulary size of the
+    categorical column of that key among `columns` (feature columns, embedding or indicator columns over one included)."""
+    key = getattr(FLAGS, "group_auc_key", "") or ""
+    if not key:
+        return {}
+    for c in columns:
+        cat = getattr(c, "categorical_column", c)
+        if isinstance(cat, fc.CategoricalColumn) and cat.key == key and not cat.is_sequence:
+            return {"group_auc_key": key, "group_auc_groups": int(cat.num_buckets),
+                    "group_auc_weighting": getattr(FLAGS, "group_auc_weighting", "uniform") or "uniform"}
+    raise ValueError(f"--group_auc_key={key}: no single-valued categorical feature column of that key")
+
+
 def define_common_flags(batch_size=1024, learning_rate=0.005, ragged_capacity=True):
     if ragged_capacity:                      # (False: a script whose flag list is exactly the reference's)
         define_ragged_capacity_flag()
+        define_group_auc_flags()
     flags.DEFINE_string("model_dir", "./model_dir", "Directory where model parameters, graph, etc are saved")
     flags.DEFINE_string("output_dir", "./output_dir", "Directory where pb file are saved")
     flags.DEFINE_string("train_data", "../../dataset/wechat_algo_data1/tfrecord/train.tfrecord", "Path to the train data")
@@ -127,6 +151,9 @@ def write_predictions(estimator, example_parser, out_csv="predictions.csv"):
 def run_estimator(model_fn, params, example_parser, predictions_writer=None):
     """main() body shared by the scripts: train_and_evaluate, evaluate, predict (predictions_writer: a script whose
     prediction keys are not `probabilities` writes its own predictions.csv)."""
+    getter = getattr(example_parser, "columns_getter", None)
+    if getter is not None:
+        params = dict(params, **group_auc_params_from_flags(getter()[0]))
     print(params)
     estimator = Estimator(model_fn=model_fn, params=params,
                           config=RunConfig(model_dir=FLAGS.model_dir,
@@ -140,7 +167,6 @@ def run_estimator(model_fn, params, example_parser, predictions_writer=None):
     # deepfm.py:307-314: the parsing serving receiver over the model's feature columns + BestExporter (keeps 5)
     from ..export import BestExporter, build_parsing_serving_input_receiver_fn
     exporters = []
-    getter = getattr(example_parser, "columns_getter", None)
     if getter is not None:
         total_feature_columns, _ = getter()
         feature_spec = fc.make_parse_example_spec(total_feature_columns)

@@ -83,9 +83,20 @@ def dense_as_ragged(ids: torch.Tensor):
     return Ragged(ids.contiguous(), torch.arange(ids.numel() + 1, dtype=torch.int64, device=ids.device))
 
 
+GROUP_AUC_CAPACITY = 1 << 22    # rows of an evaluation's per-group AUC log, unless RunConfig(group_auc_capacity=) says otherwise
+
+
+def check_group_auc_capacity(rows):
+    """An int in 1 .. ops.GAUC_MAX_ROWS, or ValueError"""
+    if not (isinstance(rows, int) and not isinstance(rows, bool) and 1 <= rows <= ops.GAUC_MAX_ROWS):
+        raise ValueError(f"group_auc_capacity = {rows!r}: expected an int in 1 .. {ops.GAUC_MAX_ROWS} (rows of one evaluation)")
+    return rows
+
+
 class RunConfig:
     def __init__(self, model_dir=None, save_checkpoints_steps=None, device=None, seed=42,
-                 use_hip_graph=True, device_metrics=True, ragged_capacity=None, **_ignored):
+                 use_hip_graph=True, device_metrics=True, ragged_capacity=None, group_auc_capacity=GROUP_AUC_CAPACITY,
+                 **_ignored):
         self.model_dir, self.save_checkpoints_steps = model_dir, save_checkpoints_steps
         self.device, self.seed, self.use_hip_graph = device, seed, use_hip_graph
         # bags and histories (feature_column.Ragged) in buffers of fixed capacity, so that a step over them is captured:
@@ -96,6 +107,10 @@ class RunConfig:
         # evaluate(): the metrics and the loss sum are accumulated on the device, one launch per batch and one copy at the end
         # (EvalAccumulator); False: the host loop over Metric.update(), which also serves whatever the kernel does not
         self.device_metrics = device_metrics
+        # the rows that the device log of a per-group AUC (GroupAUCMetric under device_metrics) holds for one evaluate() call: the
+        # buffers are allocated once, before the first batch, so that the step stays captured; an evaluation with more rows than
+        # this raises at its end and never reports a metric over part of the data
+        self.group_auc_capacity = check_group_auc_capacity(group_auc_capacity)
 
 
 class TrainSpec:
@@ -418,7 +433,101 @@ class AUCMetric(Metric):
         return float(((fpr[:-1] - fpr[1:]) * (tpr[:-1] + tpr[1:]) / 2).sum())
 
 
+GROUP_AUC_WEIGHTINGS = ("uniform", "samples")
+
+
+def group_auc_value(num2, pos, neg, weighting: str = "uniform"):
+    """The one step from a task's integer counts per group (int64 arrays [G]) to (the metric, its valid groups), for the host
+    loop and for the device path alike, so both return the same bits.  A group is valid when pos * neg > 0; its AUC is
+    num2 / (2 pos neg) in float64; "uniform" (uAUC): the mean over the valid groups; "samples" (GAUC): the mean weighted by
+    pos + neg; no valid group: 0.0."""
+    import numpy as np
+    if weighting not in GROUP_AUC_WEIGHTINGS:
+        raise ValueError(f"group AUC weighting {weighting!r}: expected one of {GROUP_AUC_WEIGHTINGS}")
+    num2, pos, neg = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (num2, pos, neg))
+    valid = pos * neg > 0
+    n = int(valid.sum())
+    if n == 0:
+        return 0.0, 0
+    auc = num2[valid].astype(np.float64) / (2.0 * (pos[valid] * neg[valid]).astype(np.float64))
+    if weighting == "uniform":
+        return float(auc.sum() / n), n
+    w = (pos[valid] + neg[valid]).astype(np.float64)
+    return float((w * auc).sum() / w.sum()), n
+
+
+def group_auc_counts(groups, y, p, num_groups: int):
+    """include/recalgo_gauc.h's counts on the host: groups int64 [n], y bool [n], p float32 [n] -> (num2, pos, neg [G] int64,
+    skipped), group by group with broadcast comparisons in float32 (the positives of a large group in slices)."""
+    import numpy as np
+    G = int(num_groups)
+    num2, pos, neg = (np.zeros(G, np.int64) for _ in range(3))
+    inside = (groups >= 0) & (groups < G)
+    g, y, p = groups[inside], y[inside], p[inside].astype(np.float32, copy=False)
+    order = np.argsort(g, kind="stable")
+    g, y, p = g[order], y[order], p[order]
+    ids, starts = np.unique(g, return_index=True)
+    ends = np.append(starts[1:], g.size)
+    for u, a, b in zip(ids.tolist(), starts.tolist(), ends.tolist()):
+        pp, pn = p[a:b][y[a:b]], p[a:b][~y[a:b]]
+        pos[u], neg[u] = pp.size, pn.size
+        if pp.size and pn.size:
+            step = max(1, (1 << 22) // pn.size)
+            for k in range(0, pp.size, step):
+                s = pp[k:k + step, None]
+                num2[u] += 2 * int((s > pn[None, :]).sum()) + int((s == pn[None, :]).sum())
+    return num2, pos, neg, int(groups.size - g.size)
+
+
+class GroupAUCMetric(Metric):
+    """The AUC of each group's own rows (a group: a user), averaged over the groups that have a positive and a negative row:
+    uAUC (weighting="uniform") or, weighted by the group's rows, GAUC ("samples").  groups: the int64 id of each row, valid in
+    0 .. num_groups - 1; any other id (-1: out of vocabulary) belongs to no group.  The definition is include/recalgo_gauc.h's,
+    in integers; update() keeps host copies of the batch and result() counts group by group, so the host loop serves it without a
+    kernel; under device_metrics the EvalAccumulator fills the same counts from the device (fill).  After result():
+    .num2 / .pos / .neg (int64 [G]), .valid_groups, .skipped_rows."""
+
+    def __init__(self, labels, predictions, groups, num_groups, weighting="uniform"):
+        if weighting not in GROUP_AUC_WEIGHTINGS:
+            raise ValueError(f"group_auc: weighting {weighting!r}, expected one of {GROUP_AUC_WEIGHTINGS}")
+        if not (isinstance(num_groups, int) and not isinstance(num_groups, bool) and num_groups >= 1):
+            raise ValueError(f"group_auc: num_groups = {num_groups!r}, expected an int >= 1")
+        self.labels, self.predictions, self.groups = labels, predictions, groups
+        self.num_groups, self.weighting = num_groups, weighting
+        self._rows = []
+        self.num2 = self.pos = self.neg = None
+        self.valid_groups, self.skipped_rows = 0, 0
+
+    def merge(self, other):
+        self.labels, self.predictions, self.groups = other.labels, other.predictions, other.groups
+
+    def update(self):
+        self._rows.append((self.groups.detach().reshape(-1).cpu().numpy(), (self.labels.detach().reshape(-1).cpu() > 0.5).numpy(),
+                           self.predictions.detach().reshape(-1).float().cpu().numpy()))
+        self.num2 = None
+
+    def fill(self, num2, pos, neg, skipped: int) -> None:
+        """the counts as the device path found them, in place of update()"""
+        self.num2, self.pos, self.neg, self.skipped_rows = num2, pos, neg, int(skipped)
+
+    def result(self):
+        import numpy as np
+        if self.num2 is None:
+            if self._rows:
+                g, y, p = (np.concatenate(c) for c in zip(*self._rows))
+            else:
+                g, y, p = np.zeros(0, np.int64), np.zeros(0, bool), np.zeros(0, np.float32)
+            self.num2, self.pos, self.neg, self.skipped_rows = group_auc_counts(g, y, p, self.num_groups)
+        value, self.valid_groups = group_auc_value(self.num2, self.pos, self.neg, self.weighting)
+        return value
+
+
 class metrics:  # namespace mirror of tf.metrics
+    @staticmethod
+    def group_auc(labels, predictions, groups, num_groups, weighting="uniform"):
+        m = GroupAUCMetric(labels, predictions, groups, num_groups, weighting)
+        return (m, m)
+
     @staticmethod
     def accuracy(labels, predictions):
         m = AccuracyMetric(labels, predictions)
@@ -441,18 +550,25 @@ class EvalAccumulator:
     below 2**53); the loss sum is the same sequence of double additions as `loss_sum += float(spec.loss)`.
 
     Serves AUCMetric and AccuracyMetric over fp32 tensors on the HIP device with a fp32 scalar loss there (`of` returns None for
-    any other spec: the caller keeps the host loop)."""
+    any other spec: the caller keeps the host loop), and beside at least one of them up to 8 GroupAUCMetric over one tensor of
+    int64 group ids: one recalgo_gauc_append launch per batch logs their rows on the device (ops.gauc_append), finish() groups the
+    log and counts the pairs there (ops.gauc_finish), and the integer counts per group come back in the same copy.  A spec
+    without a GroupAUCMetric makes exactly the launches, and owns exactly the state buffer, it did before they existed."""
 
-    def __init__(self, spec: EstimatorSpec, device):
+    def __init__(self, spec: EstimatorSpec, device, group_auc_capacity: int = GROUP_AUC_CAPACITY):
         self.device = torch.device(device)
         self.keys, self.metrics, self._th, self._layout = [], {}, {}, None
+        self.group_keys, self.gauc, self.group_auc_capacity = [], None, check_group_auc_capacity(group_auc_capacity)
         slots = self._slots(spec, first=True)
         _, self.first, words = ops.metrics_slot_table(slots)
         self.state = torch.zeros(words, dtype=torch.int64, device=spec.loss.device)
+        if self.group_keys:              # the row log, its result and the finish's scratch: allocated here, never in add()
+            self.gauc = ops.gauc_state(self.metrics[self.group_keys[0]].num_groups, len(self.group_keys), self.group_auc_capacity,
+                                       spec.loss.device)
 
     @classmethod
-    def of(cls, spec: EstimatorSpec, device) -> Optional["EvalAccumulator"]:
-        return cls(spec, device) if cls.serves(spec, device) else None
+    def of(cls, spec: EstimatorSpec, device, group_auc_capacity: int = GROUP_AUC_CAPACITY) -> Optional["EvalAccumulator"]:
+        return cls(spec, device, group_auc_capacity) if cls.serves(spec, device) else None
 
     @staticmethod
     def serves(spec: EstimatorSpec, device) -> bool:
@@ -460,11 +576,19 @@ class EvalAccumulator:
             return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() > 0
                     and _same_device(t.device, device))
         metric_ops = spec.eval_metric_ops or {}
-        if not (0 < len(metric_ops) <= ops.METRICS_MAX_SLOTS) or not on_device(spec.loss) or spec.loss.numel() != 1:
+        grouped = [m for m, _ in metric_ops.values() if type(m) is GroupAUCMetric]
+        if not (0 < len(metric_ops) - len(grouped) <= ops.METRICS_MAX_SLOTS) or not on_device(spec.loss) or spec.loss.numel() != 1:
             return False
+        if grouped:                      # up to 8 of them, over ONE tensor of int64 ids on the device and one number of groups
+            g = grouped[0].groups
+            if len(grouped) > ops.GAUC_MAX_TASKS or not ops.gauc_shape_ok(grouped[0].num_groups, len(grouped), 1) \
+                    or not (isinstance(g, torch.Tensor) and g.is_cuda and g.dtype == torch.int64 and _same_device(g.device, device)) \
+                    or g.numel() != grouped[0].labels.numel() or ops.metrics_element_stride(g) is None \
+                    or any(m.groups is not g or m.num_groups != grouped[0].num_groups for m in grouped):
+                return False
         n = None
         for m, _ in metric_ops.values():
-            if type(m) not in (AUCMetric, AccuracyMetric) or not (on_device(m.labels) and on_device(m.predictions)):
+            if type(m) not in (AUCMetric, AccuracyMetric, GroupAUCMetric) or not (on_device(m.labels) and on_device(m.predictions)):
                 return False
             n = m.labels.numel() if n is None else n
             if m.labels.numel() != n or m.predictions.numel() != n or ops.metrics_element_stride(m.labels) is None \
@@ -480,19 +604,26 @@ class EvalAccumulator:
         if first:
             self._layout = layout
             for k, (m, _) in metric_ops.items():
-                self.keys.append(k)
                 self.metrics[k] = m
+                if type(m) is GroupAUCMetric:  # (not a slot of the metrics launch: a task of the append launch)
+                    self.group_keys.append(k)
+                    continue
+                self.keys.append(k)
                 if type(m) is AUCMetric:       # the thresholds as the metric states them, on the device once
                     self._th[k] = m.th.to(device=m.predictions.device, dtype=torch.float32).contiguous()
         elif layout != self._layout or not self.serves(spec, self.device):
             raise ValueError("evaluate(device_metrics=True): a batch's eval_metric_ops differ from the first batch's "
-                             f"({[k for k, _, _ in layout]} against {self.keys}), or are not fp32 tensors on {self.device}")
+                             f"({[k for k, _, _ in layout]} against {list(self.metrics)}), or are not fp32 tensors on {self.device}")
         return [("auc", m.labels, m.predictions, self._th[k]) if type(m) is AUCMetric else ("accuracy", m.labels, m.predictions)
-                for k, (m, _) in metric_ops.items()]
+                for k, (m, _) in metric_ops.items() if type(m) is not GroupAUCMetric]
 
     def add(self, spec: EstimatorSpec) -> None:
-        """One launch: the batch's metrics and loss into the state buffer.  Capturable (no read-back, no allocation)."""
+        """One launch: the batch's metrics and loss into the state buffer; with group metrics one more, for all of them together:
+        the batch's rows into the log.  Capturable (no read-back, no allocation)."""
         ops.metrics_update(self._slots(spec), spec.loss.detach(), self.state)
+        if self.gauc is not None:
+            grouped = [spec.eval_metric_ops[k][0] for k in self.group_keys]
+            ops.gauc_append(self.gauc, grouped[0].groups, [(m.labels, m.predictions) for m in grouped])
 
     @staticmethod
     def fill_auc(m: "AUCMetric", hist: torch.Tensor) -> None:
@@ -508,8 +639,20 @@ class EvalAccumulator:
         m.correct, m.total = float(correct), float(total)
 
     def finish(self):
-        """-> ({key: filled Metric}, loss sum, batches) after ONE device-to-host copy"""
-        host = self.state.cpu()
+        """-> ({key: filled Metric}, loss sum, batches) after ONE device-to-host copy (with group metrics: the finish launches
+        first, and their result travels behind the state in that copy).  Rows that found no room in the log: RuntimeError."""
+        if self.gauc is None:
+            host = self.state.cpu()
+        else:
+            both = torch.cat([self.state, ops.gauc_finish(self.gauc)]).cpu()
+            host, counts = both[:self.state.numel()], both[self.state.numel():]
+            skipped, dropped, _, num2, pos, neg = ops.gauc_counts(counts, self.gauc.G, self.gauc.T)
+            if dropped > 0:
+                raise RuntimeError(f"evaluate(): group_auc_capacity = {self.group_auc_capacity} rows, and {dropped} more rows were "
+                                   "dropped; a per-group AUC over part of the data is not reported: raise "
+                                   "RunConfig(group_auc_capacity=) to the rows of one evaluation")
+            for t, k in enumerate(self.group_keys):
+                self.metrics[k].fill(num2[t].copy(), pos[t].copy(), neg[t].copy(), skipped)
         for k, first in zip(self.keys, self.first):
             m = self.metrics[k]
             if type(m) is AUCMetric:
@@ -1080,6 +1223,7 @@ class Estimator:
     def _call_model_fn(self, features, labels, mode) -> EstimatorSpec:
         with use_store(self.store):
             self.store.begin_call()
+            self.store.call_features = features      # (model_tail reads the group ids of a per-group AUC from them)
             return self.model_fn(features, labels, mode, self.params)
 
     def _build(self, features, labels, mode):
@@ -1223,7 +1367,7 @@ class Estimator:
                 self._build(features, labels, ModeKeys.EVAL)
             if acc is None:
                 spec = self._call_model_fn(features, labels, ModeKeys.EVAL)
-                acc = EvalAccumulator.of(spec, self.device)
+                acc = EvalAccumulator.of(spec, self.device, getattr(self.config, "group_auc_capacity", GROUP_AUC_CAPACITY))
                 if acc is None:                  # metrics the launch does not serve: the host loop, from this batch on
                     import itertools
                     return self._evaluate_on_host(itertools.chain([(features, labels)], batches), None if steps is None else steps - i)

@@ -1,6 +1,7 @@
 """The prediction / loss / metric / train_op tail every reference model_fn repeats
 (e.g. /root/reference algorithm/DeepFM/deepfm.py:214-273): sigmoid, mean sigmoid-CE
-(fused HIP kernel, a14), tf.metrics accuracy@0.5 + 200-bucket AUC, Adam(lr, .9, .999, 1e-8)."""
+(fused HIP kernel, a14), tf.metrics accuracy@0.5 + 200-bucket AUC, Adam(lr, .9, .999, 1e-8); on request
+(params["group_auc_key"], not a reference parameter) the per-user AUC of the evaluation beside them."""
 from __future__ import annotations
 
 from typing import Callable, Dict, Optional
@@ -14,6 +15,34 @@ from .variables import current_store
 
 def sigmoid(logit: torch.Tensor) -> torch.Tensor:
     return torch.sigmoid(logit)
+
+
+def group_auc_metric_ops(params, tasks) -> Dict[str, tuple]:
+    """params["group_auc_key"] names the categorical feature whose encoded ids group the rows of a per-group AUC (the user id),
+    params["group_auc_groups"] is its vocabulary size and params.get("group_auc_weighting") "uniform" (uAUC, the default) or
+    "samples" (GAUC).  tasks: [(task name or None, labels, probabilities)] -> {"eval_[<task>_]uauc" | "eval_[<task>_]gauc":
+    metrics.group_auc(..)}, every one over the same tensor of ids, as the model_fn received them (int64 [B] or [B, 1], an id < 0
+    for out-of-vocabulary); {} without the key."""
+    key = params.get("group_auc_key")
+    if not key:
+        return {}
+    from .feature_column import Ragged
+    weighting = params.get("group_auc_weighting") or "uniform"
+    features = current_store().call_features
+    if not isinstance(features, dict) or key not in features:
+        raise ValueError(f"params['group_auc_key'] = {key!r}: the model_fn's features hold no such key")
+    groups = features[key]
+    if isinstance(groups, Ragged):
+        raise ValueError(f"params['group_auc_key'] = {key!r}: a Ragged (a bag or a history) does not give each row one group")
+    if not isinstance(groups, torch.Tensor) or groups.dtype != torch.int64 or groups.dim() > 2 or (groups.dim() == 2 and groups.shape[1] != 1):
+        raise ValueError(f"params['group_auc_key'] = {key!r}: expected the feature's encoded ids, an int64 [B] or [B, 1] tensor")
+    num_groups = params.get("group_auc_groups")
+    if not (isinstance(num_groups, int) and not isinstance(num_groups, bool) and num_groups >= 1):
+        raise ValueError(f"params['group_auc_groups'] = {num_groups!r}: expected the vocabulary size of {key!r}, an int >= 1")
+    suffix = "gauc" if weighting == "samples" else "uauc"
+    return {f"eval_{suffix}" if name is None else f"eval_{name}_{suffix}":
+            metrics.group_auc(labels=y, predictions=p, groups=groups, num_groups=num_groups, weighting=weighting)
+            for name, y, p in tasks}
 
 
 def finish_model_fn(mode, logit: torch.Tensor, labels, params,
@@ -70,7 +99,8 @@ def finish_model_fn(mode, logit: torch.Tensor, labels, params,
     if mode == ModeKeys.EVAL:
         acc = metrics.accuracy(labels=y, predictions=(prob >= 0.5).to(torch.float32))
         auc = metrics.auc(labels=y, predictions=prob)
-        return EstimatorSpec(mode, loss=loss, eval_metric_ops={"eval_accuracy": acc, "eval_auc": auc})
+        return EstimatorSpec(mode, loss=loss, eval_metric_ops={"eval_accuracy": acc, "eval_auc": auc,
+                                                               **group_auc_metric_ops(params, [(None, y, prob)])})
 
     # TRAIN: the reference also builds the two metric ops here, but only to feed tf.summary /
     # LoggingTensorHook (deepfm.py:237-238,256-271); they are not part of the training step
@@ -106,7 +136,7 @@ def finish_multitask_model_fn(mode, logits: Dict[str, torch.Tensor], labels, par
         acc = {f"eval_{n}_accuracy": metrics.accuracy(labels=y, predictions=(p >= 0.5).to(torch.float32))
                for n, y, p in zip(names, ys, probs)}
         auc = {f"eval_{n}_auc": metrics.auc(labels=y, predictions=p) for n, y, p in zip(names, ys, probs)}
-        return EstimatorSpec(mode, loss=loss, eval_metric_ops={**acc, **auc})
+        return EstimatorSpec(mode, loss=loss, eval_metric_ops={**acc, **auc, **group_auc_metric_ops(params, list(zip(names, ys, probs)))})
 
     assert mode == ModeKeys.TRAIN
     opt_cls = LazyAdamOptimizer if params.get("lazy_adam") else AdamOptimizer      # lazy_adam: labelled deviation (§8f-1)

@@ -3562,3 +3562,78 @@ def metrics_update(slots, loss: Optional[torch.Tensor], state: torch.Tensor) -> 
     if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != state.device):
         raise TypeError(f"metrics_update: loss must be one float32 value on {state.device}")
     _lib_().recalgo_metrics_update(table, len(slots), _p(loss), n, _p(state), _stream(state))
+
+
+# =============================================================================================
+# Per-group AUC (csrc/gauc.hip, include/recalgo_gauc.h): uAUC / GAUC as integer pair counts per group — one append launch per
+# batch into a row log on the device, and a finish (count, scan, place, pairs) once per evaluation
+# =============================================================================================
+_GH = _lib.SERVING_HEADERS["recalgo_gauc.h"]
+_CG = _GH.constants                                            # the RECALGO_GAUC_* #defines of include/recalgo_gauc.h
+_GaucColumn = _GH.structs["recalgo_gauc_column_t"]
+GAUC_MAX_TASKS, GAUC_MAX_GROUPS, GAUC_MAX_ROWS = _CG["RECALGO_GAUC_MAX_TASKS"], _CG["RECALGO_GAUC_MAX_GROUPS"], _CG["RECALGO_GAUC_MAX_ROWS"]
+GAUC_STATE_HEADER_WORDS, GAUC_RESULT_HEADER_WORDS = _CG["RECALGO_GAUC_STATE_HEADER_WORDS"], _CG["RECALGO_GAUC_RESULT_HEADER_WORDS"]
+
+
+def gauc_shape_ok(num_groups, tasks, capacity) -> bool:
+    """What the header's launches accept (decided without loading the library)"""
+    ints = all(isinstance(v, int) and not isinstance(v, bool) for v in (num_groups, tasks, capacity))
+    return ints and 1 <= tasks <= GAUC_MAX_TASKS and 1 <= num_groups <= GAUC_MAX_GROUPS and 1 <= capacity <= GAUC_MAX_ROWS
+
+
+class GaucState:
+    """The three caller-owned buffers of include/recalgo_gauc.h for (num_groups, tasks, capacity), as int64 tensors:
+    .state (header zeroed: no row yet), .result [3 + 3 T G] and .workspace."""
+
+    def __init__(self, num_groups: int, tasks: int, capacity: int, device):
+        if not gauc_shape_ok(num_groups, tasks, capacity):
+            raise ValueError(f"gauc_state: 1 .. {GAUC_MAX_TASKS} tasks, 1 .. {GAUC_MAX_GROUPS} groups and a capacity of 1 .. "
+                             f"{GAUC_MAX_ROWS} rows; got {tasks}, {num_groups}, {capacity}")
+        self.G, self.T, self.C = num_groups, tasks, capacity
+        lib = _lib_()
+        sb, wb = int(lib.recalgo_gauc_state_bytes(self.G, self.T, self.C)), int(lib.recalgo_gauc_workspace_bytes(self.G, self.T, self.C))
+        self.state = torch.empty(sb // 8, dtype=torch.int64, device=device)
+        self.state[:GAUC_STATE_HEADER_WORDS].zero_()
+        self.workspace = torch.empty(wb // 8, dtype=torch.int64, device=device)
+        self.result = torch.empty(GAUC_RESULT_HEADER_WORDS + 3 * self.T * self.G, dtype=torch.int64, device=device)
+
+
+def gauc_state(num_groups: int, tasks: int, capacity: int, device) -> GaucState:
+    return GaucState(num_groups, tasks, capacity, device)
+
+
+def gauc_append(st: GaucState, groups: torch.Tensor, columns) -> None:
+    """recalgo_gauc_append: one launch logs a batch behind the rows `st` already holds.  groups: int64 ids, one per row, at one
+    element stride (a [B] column view of a packed [B, F] id matrix is fine); columns: st.T pairs (labels, predictions) of fp32
+    tensors with as many elements, each at one element stride.  No allocation, no read-back: capturable."""
+    n = int(groups.numel())
+    gs = metrics_element_stride(groups)
+    if groups.dtype != torch.int64 or groups.device != st.state.device or gs is None:
+        raise TypeError(f"gauc_append: groups must be int64 on {st.state.device} at one element stride")
+    if len(columns) != st.T:
+        raise ValueError(f"gauc_append: {len(columns)} columns for a state of {st.T} tasks")
+    table = (_GaucColumn * st.T)()
+    for c, (labels, predictions) in zip(table, columns):
+        for t, name in ((labels, "labels"), (predictions, "predictions")):
+            if t.dtype != torch.float32 or t.device != st.state.device:
+                raise TypeError(f"gauc_append: {name} must be float32 on {st.state.device}")
+        c.label_step, c.prediction_step = metrics_element_stride(labels) or 0, metrics_element_stride(predictions) or 0
+        if labels.numel() != n or predictions.numel() != n or not c.label_step or not c.prediction_step:
+            raise ValueError(f"gauc_append: labels and predictions must hold the batch's {n} values at one element stride")
+        c.labels, c.predictions = labels.data_ptr(), predictions.data_ptr()
+    _lib_().recalgo_gauc_append(_p(groups), gs, table, st.T, n, st.G, st.C, _p(st.state), _stream(st.state))
+
+
+def gauc_finish(st: GaucState) -> torch.Tensor:
+    """recalgo_gauc_finish over every row appended so far -> st.result on the device (gauc_counts reads a host copy of it).  The
+    log is left as it is: more rows may follow, and another finish then counts all of them."""
+    _lib_().recalgo_gauc_finish(_p(st.state), st.G, st.T, st.C, _p(st.result), _p(st.workspace), _stream(st.state))
+    return st.result
+
+
+def gauc_counts(result: torch.Tensor, num_groups: int, tasks: int):
+    """A host copy of a result buffer -> (skipped, dropped, rows, num2 [T, G], pos [T, G], neg [T, G]) as ints and int64 arrays"""
+    r = result.cpu().numpy()
+    h = GAUC_RESULT_HEADER_WORDS
+    num2, pos, neg = r[h:].reshape(3, tasks, num_groups)
+    return int(r[0]), int(r[1]), int(r[2]), num2, pos, neg

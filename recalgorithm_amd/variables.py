@@ -113,6 +113,7 @@ class VariableStore:
         # depend on the data (feature_column.sequence_input_layer without max_length, ..); the Estimator reads it and stays eager
         self.data_dependent: Optional[str] = None
         self._drop_calls = 0             # training-mode dropout calls of the current model_fn invocation (nn.dropout)
+        self.call_features = None        # the features of the current model_fn invocation (Estimator._call_model_fn)
         self._rb_cache: Dict[tuple, torch.Tensor] = {}
         # the serving switch, off by default: only export.ServingModel.compile sets it (an nn.ServingPlan), around the PREDICT
         # model_fn calls it captures; nn.dense / nn.batch_normalization then collect the hidden stack into an nn.LazyTower
