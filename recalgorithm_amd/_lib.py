@@ -42,7 +42,7 @@ MORE_HEADERS = {"recalgo_dien.h": _versioned("recalgo_dien.h")}
 SERVING_HEADERS = {h: _versioned(h) for h in ("recalgo_serve.h", "recalgo_metrics.h", "recalgo_sumstep.h",
                                                       "recalgo_ragged.h", "recalgo_afm.h", "recalgo_feed.h", "recalgo_ffm.h",
                                                       "recalgo_autoint.h", "recalgo_dcnv2.h", "recalgo_flen.h",
-                                                      "recalgo_gauc.h")}
+                                                      "recalgo_gauc.h", "recalgo_esmm.h", "recalgo_maskmetrics.h")}
 ABI = HEADERS["recalgo.h"]  # the first header's tables, under the names the product uses:
 SIGNATURES = ABI.functions  # name -> (restype, argtypes) of every function of the header
 STRUCTS = ABI.structs  # recalgo_*_t -> ctypes.Structure subclass

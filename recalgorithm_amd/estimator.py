@@ -385,27 +385,42 @@ class Metric:
         raise NotImplementedError
 
 
+def _takes_part(mask):
+    """mask (one value per row) -> bool [n]: the rows of a masked metric that take part, mask > 0.5 (a NaN takes no part);
+    include/recalgo_maskmetrics.h makes the same comparison on the device"""
+    return mask.detach().reshape(-1) > 0.5
+
+
 class AccuracyMetric(Metric):
-    def __init__(self, labels, predictions):
-        self.labels, self.predictions = labels, predictions
+    """tf.metrics.accuracy; with `mask` (tf's 0/1 `weights=`) over the rows whose mask is > 0.5."""
+
+    def __init__(self, labels, predictions, mask=None):
+        self.labels, self.predictions, self.mask = labels, predictions, mask
         self.correct, self.total = 0.0, 0.0
 
     def merge(self, other):
-        self.labels, self.predictions = other.labels, other.predictions
+        self.labels, self.predictions, self.mask = other.labels, other.predictions, other.mask
 
     def update(self):
-        self.correct += float((self.labels.reshape(-1) == self.predictions.reshape(-1)).sum())
-        self.total += self.labels.numel()
+        same = self.labels.reshape(-1) == self.predictions.reshape(-1)
+        if self.mask is None:
+            self.correct += float(same.sum())
+            self.total += self.labels.numel()
+        else:
+            part = _takes_part(self.mask)
+            self.correct += float((same & part).sum())
+            self.total += float(part.sum())
 
     def result(self):
         return self.correct / max(self.total, 1.0)
 
 
 class AUCMetric(Metric):
-    """tf.metrics.auc defaults: 200 thresholds, trapezoidal ROC."""
+    """tf.metrics.auc defaults: 200 thresholds, trapezoidal ROC; with `mask` (tf's 0/1 `weights=`) over the rows
+    whose mask is > 0.5."""
 
-    def __init__(self, labels, predictions, num_thresholds=200):
-        self.labels, self.predictions, self.n = labels, predictions, num_thresholds
+    def __init__(self, labels, predictions, num_thresholds=200, mask=None):
+        self.labels, self.predictions, self.n, self.mask = labels, predictions, num_thresholds, mask
         eps = 1e-7
         th = [(i + 1) * 1.0 / (num_thresholds - 1) for i in range(num_thresholds - 2)]
         self.th = torch.tensor([0.0 - eps] + th + [1.0 + eps], dtype=torch.float32)
@@ -415,11 +430,14 @@ class AUCMetric(Metric):
         self.tn = torch.zeros_like(self.tp)
 
     def merge(self, other):
-        self.labels, self.predictions = other.labels, other.predictions
+        self.labels, self.predictions, self.mask = other.labels, other.predictions, other.mask
 
     def update(self):
         p = self.predictions.detach().reshape(1, -1).float().cpu()
         y = self.labels.detach().reshape(1, -1).cpu() > 0.5
+        if self.mask is not None:
+            part = _takes_part(self.mask).cpu()
+            p, y = p[:, part], y[:, part]
         pred_pos = p > self.th.unsqueeze(1)
         self.tp += (pred_pos & y).sum(1)
         self.fp += (pred_pos & ~y).sum(1)
@@ -529,13 +547,14 @@ class metrics:  # namespace mirror of tf.metrics
         return (m, m)
 
     @staticmethod
-    def accuracy(labels, predictions):
-        m = AccuracyMetric(labels, predictions)
+    def accuracy(labels, predictions, mask=None):
+        m = AccuracyMetric(labels, predictions, mask)
         return (m, m)
 
     @staticmethod
-    def auc(labels, predictions, num_thresholds=200):
-        m = AUCMetric(labels, predictions, num_thresholds)
+    def auc(labels, predictions, num_thresholds=200, mask=None):
+        """mask, not tf's `weights`: only 0/1 keeps every count an integer"""
+        m = AUCMetric(labels, predictions, num_thresholds, mask)
         return (m, m)
 
 
@@ -553,14 +572,18 @@ class EvalAccumulator:
     any other spec: the caller keeps the host loop), and beside at least one of them up to 8 GroupAUCMetric over one tensor of
     int64 group ids: one recalgo_gauc_append launch per batch logs their rows on the device (ops.gauc_append), finish() groups the
     log and counts the pairs there (ops.gauc_finish), and the integer counts per group come back in the same copy.  A spec
-    without a GroupAUCMetric makes exactly the launches, and owns exactly the state buffer, it did before they existed."""
+    without a GroupAUCMetric makes exactly the launches, and owns exactly the state buffer, it did before they existed.
+
+    An AUCMetric or AccuracyMetric may carry a mask (fp32 on the device, one value per row: the rows with mask > 0.5 take part).
+    A spec with such a metric makes its one launch per batch through ops.maskmetrics_update, into the same state layout; a spec
+    without one makes the launches it made before masks existed."""
 
     def __init__(self, spec: EstimatorSpec, device, group_auc_capacity: int = GROUP_AUC_CAPACITY):
         self.device = torch.device(device)
         self.keys, self.metrics, self._th, self._layout = [], {}, {}, None
         self.group_keys, self.gauc, self.group_auc_capacity = [], None, check_group_auc_capacity(group_auc_capacity)
         slots = self._slots(spec, first=True)
-        _, self.first, words = ops.metrics_slot_table(slots)
+        _, self.first, words = ops.metrics_slot_table([s[:-1] for s in slots] if self.masked else slots)
         self.state = torch.zeros(words, dtype=torch.int64, device=spec.loss.device)
         if self.group_keys:              # the row log, its result and the finish's scratch: allocated here, never in add()
             self.gauc = ops.gauc_state(self.metrics[self.group_keys[0]].num_groups, len(self.group_keys), self.group_auc_capacity,
@@ -594,13 +617,16 @@ class EvalAccumulator:
             if m.labels.numel() != n or m.predictions.numel() != n or ops.metrics_element_stride(m.labels) is None \
                     or ops.metrics_element_stride(m.predictions) is None:
                 return False
+            mask = getattr(m, "mask", None)          # of an AUC or accuracy metric: fp32 on the device, one value per row
+            if mask is not None and not (on_device(mask) and mask.numel() == n and ops.metrics_element_stride(mask) is not None):
+                return False
             if type(m) is AUCMetric and not (2 <= m.n <= ops.METRICS_MAX_THRESHOLDS and m.th.numel() == m.n):
                 return False
         return True
 
     def _slots(self, spec: EstimatorSpec, first: bool = False):
         metric_ops = spec.eval_metric_ops or {}
-        layout = [(k, type(m), getattr(m, "n", None)) for k, (m, _) in metric_ops.items()]
+        layout = [(k, type(m), getattr(m, "n", None), getattr(m, "mask", None) is not None) for k, (m, _) in metric_ops.items()]
         if first:
             self._layout = layout
             for k, (m, _) in metric_ops.items():
@@ -613,14 +639,22 @@ class EvalAccumulator:
                     self._th[k] = m.th.to(device=m.predictions.device, dtype=torch.float32).contiguous()
         elif layout != self._layout or not self.serves(spec, self.device):
             raise ValueError("evaluate(device_metrics=True): a batch's eval_metric_ops differ from the first batch's "
-                             f"({[k for k, _, _ in layout]} against {list(self.metrics)}), or are not fp32 tensors on {self.device}")
-        return [("auc", m.labels, m.predictions, self._th[k]) if type(m) is AUCMetric else ("accuracy", m.labels, m.predictions)
-                for k, (m, _) in metric_ops.items() if type(m) is not GroupAUCMetric]
+                             f"({[k for k, *_ in layout]} against {list(self.metrics)}), or are not fp32 tensors on {self.device}")
+        slots = [("auc", m.labels, m.predictions, self._th[k]) if type(m) is AUCMetric else ("accuracy", m.labels, m.predictions)
+                 for k, (m, _) in metric_ops.items() if type(m) is not GroupAUCMetric]
+        if first:
+            self.masked = any(masked for *_, masked in layout)
+        if self.masked:                        # every slot carries its mask (or None) behind it: ops.maskmetrics_update's tuples
+            masks = [m.mask for m, _ in metric_ops.values() if type(m) is not GroupAUCMetric]
+            slots = [(*slot, mask) for slot, mask in zip(slots, masks)]
+        return slots
 
     def add(self, spec: EstimatorSpec) -> None:
-        """One launch: the batch's metrics and loss into the state buffer; with group metrics one more, for all of them together:
+        """One launch: the batch's metrics and loss into the state buffer (recalgo_metrics_update; when a metric of the spec
+        carries a mask, recalgo_maskmetrics_update for all of them); with group metrics one more, for all of them together:
         the batch's rows into the log.  Capturable (no read-back, no allocation)."""
-        ops.metrics_update(self._slots(spec), spec.loss.detach(), self.state)
+        update = ops.maskmetrics_update if self.masked else ops.metrics_update     # (one launch either way, for all slots)
+        update(self._slots(spec), spec.loss.detach(), self.state)
         if self.gauc is not None:
             grouped = [spec.eval_metric_ops[k][0] for k in self.group_keys]
             ops.gauc_append(self.gauc, grouped[0].groups, [(m.labels, m.predictions) for m in grouped])

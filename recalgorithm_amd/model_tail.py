@@ -144,3 +144,44 @@ def finish_multitask_model_fn(mode, logits: Dict[str, torch.Tensor], labels, par
     train_op = optimizer.minimize(loss=loss)
     return EstimatorSpec(mode, loss=loss, train_op=train_op,
                          predictions={f"{n}_probabilities": p for n, p in zip(names, probs)})
+
+
+def finish_esmm_model_fn(mode, ctr_logit: torch.Tensor, cvr_logit: torch.Tensor, labels, params) -> EstimatorSpec:
+    """The tail of ESMM (Ma et al., SIGIR 2018; no reference file): two [B, 1] logits over ALL impressions, the click label
+    labels[params["ctr_task_name"]] and the conversion label labels[params["cvr_task_name"]].
+    PREDICT: {"ctr_probabilities", "cvr_probabilities", "ctcvr_probabilities"} (pCTR, pCVR, their product).
+    EVAL: loss = L_ctr + L_ctcvr; eval_ctr_{auc, accuracy} against the click, eval_ctcvr_{auc, accuracy} against click *
+    conversion, and eval_cvr_{auc, accuracy}: the conversion against pCVR over the CLICKED impressions only (mask = the click:
+    the space the CVR tower is defined on); with params["group_auc_key"] the per-user AUC of ctr and ctcvr.
+    TRAIN: Adam on the total — one loss launch for both terms and both logit gradients (ops.esmm_loss).
+    As in the multi-task tail, every tower logit is evaluated by its own head kernel (LazyLogit.materialize)."""
+    from .nn import LazyLogit
+    a, b = (t.materialize() if isinstance(t, LazyLogit) else t for t in (ctr_logit, cvr_logit))
+    names = ("ctr_probabilities", "cvr_probabilities", "ctcvr_probabilities")
+    if mode == ModeKeys.PREDICT:
+        p_ctr, p_cvr = torch.sigmoid(a), torch.sigmoid(b)
+        preds = dict(zip(names, (p_ctr, p_cvr, p_ctr * p_cvr)))
+        return EstimatorSpec(mode, predictions=preds, export_outputs={"prediction": preds})
+
+    y, c = labels[params["ctr_task_name"]], labels[params["cvr_task_name"]]
+    if current_store().building:            # variable-registration pass: nothing is launched
+        loss, probs = a.new_zeros(()), [torch.zeros_like(a) for _ in names]
+    else:
+        loss, _, prob = ops.esmm_loss(a, b, y, c)
+        probs = [prob[:, i:i + 1] for i in range(3)]
+    if mode == ModeKeys.EVAL:
+        y = y.to(torch.float32).reshape(-1, 1)
+        c = c.to(torch.float32).reshape(-1, 1)
+        tasks = [("ctr", y, probs[0], None), ("ctcvr", y * c, probs[2], None), ("cvr", c, probs[1], y)]
+        metric_ops = {}
+        for n, lab, p, mask in tasks:
+            metric_ops[f"eval_{n}_auc"] = metrics.auc(labels=lab, predictions=p, mask=mask)
+            metric_ops[f"eval_{n}_accuracy"] = metrics.accuracy(labels=lab, predictions=(p >= 0.5).to(torch.float32), mask=mask)
+        return EstimatorSpec(mode, loss=loss, eval_metric_ops={
+            **metric_ops, **group_auc_metric_ops(params, [(n, lab, p) for n, lab, p, mask in tasks if mask is None])})
+
+    assert mode == ModeKeys.TRAIN
+    opt_cls = LazyAdamOptimizer if params.get("lazy_adam") else AdamOptimizer      # lazy_adam: labelled deviation (§8f-1)
+    optimizer = opt_cls(learning_rate=params["learning_rate"], beta1=0.9, beta2=0.999, epsilon=1e-8)
+    train_op = optimizer.minimize(loss=loss)
+    return EstimatorSpec(mode, loss=loss, train_op=train_op, predictions=dict(zip(names, probs)))

@@ -2515,6 +2515,64 @@ def multitask_sigmoid_cross_entropy(logits, labels):
 
 
 # =============================================================================================
+# ESMM (csrc/esmm.hip, include/recalgo_esmm.h): the click loss and the entire-space click-and-conversion loss, one launch
+# =============================================================================================
+ESMM_MAX_ROWS = _lib.SERVING_HEADERS["recalgo_esmm.h"].constants["RECALGO_ESMM_MAX_ROWS"]
+
+
+class _EsmmLossFn(Function):
+    """include/recalgo_esmm.h recalgo_esmm_loss_fwd_bwd: both losses, their sum, the three probabilities and both logit
+    gradients in one launch.  The header delivers each logit's gradient of the SUM, so only `total` is differentiable."""
+
+    @staticmethod
+    def forward(ctx, want, click, conversion, ctr_logit, cvr_logit):
+        # want: a logit requires grad and grad mode is on, as esmm_loss saw it (inside forward grad mode is always off)
+        ctx.set_materialize_grads(False)
+        ctx.seed = _loss_seed
+        B = ctr_logit.numel()
+        a, b = ctr_logit.contiguous().view(-1), cvr_logit.contiguous().view(-1)
+        y, c = (t.contiguous().view(-1).to(torch.float32) for t in (click, conversion))
+        dev = a.device
+        prob = torch.empty(B, 3, device=dev, dtype=torch.float32)
+        losses = torch.empty(2, device=dev, dtype=torch.float32)
+        total = torch.empty(1, device=dev, dtype=torch.float32)
+        da, db = (torch.empty_like(a), torch.empty_like(b)) if want else (None, None)
+        _lib_().recalgo_esmm_loss_fwd_bwd(_p(a), _p(b), _p(y), _p(c), B, 1.0 if ctx.seed is None else ctx.seed, _p(prob), _p(losses),
+                                          _p(total), _p(da), _p(db), _stream(a))
+        if want:
+            ctx.save_for_backward(da, db)
+        ctx.shapes = (ctr_logit.shape, cvr_logit.shape)
+        ctx.mark_non_differentiable(losses, prob)
+        return total.view(()), losses, prob
+
+    @staticmethod
+    def backward(ctx, gtotal, _glosses, _gprob):
+        if gtotal is None or not ctx.saved_tensors:
+            return None, None, None, None, None
+        grads = ctx.saved_tensors
+        if ctx.seed is None:
+            grads = [d * gtotal for d in grads]                                       # (the seed is baked in otherwise: ops.loss_seed)
+        return (None, None, None, *[d.view(s) if need else None for d, s, need in zip(grads, ctx.shapes, ctx.needs_input_grad[3:])])
+
+
+def esmm_loss(ctr_logit: torch.Tensor, cvr_logit: torch.Tensor, click: torch.Tensor, conversion: torch.Tensor):
+    """ESMM's loss over all impressions: L_ctr = mean sigmoid-CE(ctr_logit, click) — `sigmoid_cross_entropy`'s value bit for bit —
+    plus L_ctcvr = mean CE(sigmoid(ctr_logit) sigmoid(cvr_logit), click * conversion), evaluated in logit space
+    (include/recalgo_esmm.h).  Four tensors of B values -> (total (scalar, differentiable in both logits), the two losses [2],
+    probabilities [B, 3]: pCTR, pCVR, pCTCVR)."""
+    n = ctr_logit.numel()
+    if any(t.numel() != n for t in (cvr_logit, click, conversion)) or n == 0:
+        raise ValueError("esmm_loss: two logits and two labels of one batch size, at least one row")
+    if n > ESMM_MAX_ROWS:
+        raise NotImplementedError(f"esmm_loss: at most {ESMM_MAX_ROWS} rows")
+    if ctr_logit.dtype != torch.float32 or cvr_logit.dtype != torch.float32:
+        raise TypeError("esmm_loss: fp32 logits")
+    _stream(ctr_logit), _stream(cvr_logit)
+    want =torch.is_grad_enabled() and (ctr_logit.requires_grad or cvr_logit.requires_grad)
+    return _EsmmLossFn.apply(want, click, conversion, ctr_logit, cvr_logit)
+
+
+# =============================================================================================
 # a12: PReLU / Dice
 # =============================================================================================
 class _ActFn(Function):
@@ -3562,6 +3620,43 @@ def metrics_update(slots, loss: Optional[torch.Tensor], state: torch.Tensor) -> 
     if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != state.device):
         raise TypeError(f"metrics_update: loss must be one float32 value on {state.device}")
     _lib_().recalgo_metrics_update(table, len(slots), _p(loss), n, _p(state), _stream(state))
+
+
+# The same metrics over the rows a mask selects (include/recalgo_maskmetrics.h): one launch for masked and unmasked slots together
+_MaskMetricsSlot = _lib.SERVING_HEADERS["recalgo_maskmetrics.h"].structs["recalgo_maskmetrics_slot_t"]
+
+
+def maskmetrics_update(slots, loss: Optional[torch.Tensor], state: torch.Tensor) -> None:
+    """include/recalgo_maskmetrics.h recalgo_maskmetrics_update: `metrics_update` with one more element per slot tuple, a mask
+    (fp32 on state's device, the batch's n values at one element stride) or None: ("auc", labels, predictions, thresholds, mask) |
+    ("accuracy", labels, predictions, mask).  A row of a slot takes part iff the slot's mask is None or mask[i] > 0.5 (a NaN: no
+    part); an accuracy slot counts the rows that take part.  The state buffer is metrics_slot_table's, word for word."""
+    n = int(slots[0][1].numel()) if slots else 0
+    for slot in slots:
+        kind, labels, predictions, *th = slot[:-1]
+        named = ((labels, "labels"), (predictions, "predictions")) + (((th[0], "thresholds"),) if kind == "auc" else ()) \
+            + (((slot[-1], "mask"),) if slot[-1] is not None else ())
+        for t, name in named:
+            if t.dtype != torch.float32 or t.device != state.device:
+                raise TypeError(f"maskmetrics_update: {kind} {name} must be float32 on {state.device}")
+        if any(t.numel() != n or metrics_element_stride(t) is None for t, name in named if name != "thresholds") \
+                or (kind == "auc" and not th[0].is_contiguous()):
+            raise ValueError(f"maskmetrics_update: {kind} labels, predictions and mask must hold the batch's {n} values at one element stride")
+    _, _, words = metrics_slot_table([s[:-1] for s in slots])
+    table = (_MaskMetricsSlot * max(len(slots), 1))()
+    for s, (kind, labels, predictions, *th, mask) in zip(table, slots):
+        s.kind = METRICS_KINDS[kind]
+        s.labels, s.predictions = labels.data_ptr(), predictions.data_ptr()
+        s.label_step, s.prediction_step = metrics_element_stride(labels), metrics_element_stride(predictions)
+        if kind == "auc":
+            s.thresholds, s.num_thresholds = th[0].data_ptr(), int(th[0].numel())
+        if mask is not None:
+            s.mask, s.mask_step = mask.data_ptr(), metrics_element_stride(mask)
+    if state.dtype != torch.int64 or not state.is_contiguous() or state.numel() != words:
+        raise ValueError(f"maskmetrics_update: state must be a contiguous int64 tensor of {words} words")
+    if loss is not None and (loss.dtype != torch.float32 or loss.numel() != 1 or loss.device != state.device):
+        raise TypeError(f"maskmetrics_update: loss must be one float32 value on {state.device}")
+    _lib_().recalgo_maskmetrics_update(table, len(slots), _p(loss), n, _p(state), _stream(state))
 
 
 # =============================================================================================
