@@ -637,7 +637,7 @@ class _ExpertsFn(Function):
         for k, b, y, g, src in zip(ks, bs, ys, gs, ctx.srcs):
             if g is None:
                 continue
-            g2 = g if g.is_contiguous() else g.contiguous()
+            g2 = ops._contig(g)
             mask = None if src.take(g2) else y       # (ops.gate_mix masked the gradient it wrote: nn.ReluSource)
             if need_x:
                 dx = ops.dense_bwd(x2, g2, mask, k.data, k.grad, b.grad, c_in=dx, beta=0.0 if dx is None else 1.0, defer=True,
@@ -721,7 +721,7 @@ def dense_with(x: torch.Tensor, kernel: Variable, bias: Optional[Variable] = Non
     store = current_store()
     if kernel.data.shape[1] == 1 and not relu:
         from . import ops
-        xc = x if x.is_contiguous() else x.contiguous()
+        xc = ops._contig(x)
         if ops.dense1_supported([xc]):
             return _Dense1Fn.apply(store.anchor, kernel, bias, xc)
     return _DenseFn.apply(store.anchor, x, kernel, bias, relu, 0.0, None)
@@ -1038,8 +1038,7 @@ def bst_transformer(queries: torch.Tensor, keys_length: torch.Tensor, heads: int
                          f"{ops.BST_MAX_T}, d in (4, 8, 12, 16), heads <= {ops.BST_MAX_HEADS}); there is no fallback")
     if store.building:
         return queries.new_zeros((B, T, d) if pool is None else (B, d))
-    x = queries if queries.is_contiguous() else queries.contiguous()
-    n1 = ops.bst_attention(x, keys_length, pos, w_q, w_k, w_v, w_o, *norms[0], anchor=store.anchor)
+    n1 = ops.bst_attention(ops._contig(queries), keys_length, pos, w_q, w_k, w_v, w_o, *norms[0], anchor=store.anchor)
     out, pooled = ops.bst_ffn(n1, ffn_w, ffn_b, *norms[1], pool=pool, want_out=pool is None, anchor=store.anchor)
     return out if pool is None else pooled
 
@@ -1074,8 +1073,7 @@ def dien_gru(inputs: torch.Tensor, sequence_length: Optional[torch.Tensor], num_
     _dien_served("dien_gru", T, na, nh)
     if store.building:
         return inputs.new_zeros((B, T, nh))
-    x = inputs if inputs.is_contiguous() else inputs.contiguous()
-    return ops.dien_gru(x, sequence_length, *cell, anchor=store.anchor)
+    return ops.dien_gru(ops._contig(inputs), sequence_length, *cell, anchor=store.anchor)
 
 
 def dien_evolve(h: torch.Tensor, target: torch.Tensor, sequence_length: torch.Tensor, custom_gru_type: str = "AGRU",
@@ -1099,10 +1097,24 @@ def dien_evolve(h: torch.Tensor, target: torch.Tensor, sequence_length: torch.Te
     if store.building:
         outs = (h.new_zeros((B, nh)), h.new_zeros((B, T)), h.new_zeros((B, T, nh)))
     else:
-        hc = h if h.is_contiguous() else h.contiguous()
-        tc = target if target.is_contiguous() else target.contiguous()
-        outs = ops.dien_evolve(hc, tc, sequence_length, w_att, *cell, mode=custom_gru_type, anchor=store.anchor)
+        outs = ops.dien_evolve(ops._contig(h), ops._contig(target), sequence_length, w_att, *cell, mode=custom_gru_type, anchor=store.anchor)
     return outs if return_states else outs[:2]
+
+
+# ---- fused=: a layer on its fused kernels (True), composed from other ops (False), or whichever its default says (None) -----------
+def _fp32_matrix_on_device(x) -> bool:
+    """an fp32 2-D device tensor: what the kernels of every layer with a fused= argument read"""
+    return isinstance(x, torch.Tensor) and x.dim() == 2 and x.is_cuda and x.dtype == torch.float32
+
+
+def _resolve_fused(fused: Optional[bool], served: bool, default: bool, refusal: Optional[str]) -> bool:
+    """A layer's fused= argument -> whether this call runs the kernels.  served: whether they serve this call; default: what
+    None picks; refusal: the ValueError of fused=True where they do not serve (None: the op itself refuses)."""
+    if fused is None:
+        return bool(default)
+    if fused and not served and refusal is not None:
+        raise ValueError(refusal)
+    return bool(fused)
 
 
 # From this width on nn.residual_stack runs the composed dense layers by default; below it the fused kernels of
@@ -1137,11 +1149,9 @@ def residual_stack(x: torch.Tensor, internal_dim: int, num_units: int, first_ind
     from . import ops
     store = current_store()
     D, H, L = int(x.shape[-1]), int(internal_dim), int(num_units)
-    on_device = x.dim() == 2 and store.device.type == "cuda" and (store.building or (x.is_cuda and x.dtype == torch.float32))
-    if fused is None:
-        fused = on_device and residual_fused_default(D, H, L)
-    elif fused and not (on_device and L >= 1 and ops.residual_supported(D, H, L)):
-        raise ValueError(f"residual_stack(fused=True): the kernels do not serve D={D} H={H} units={L} on {store.device}")
+    on_device = store.device.type == "cuda" and (x.dim() == 2 if store.building else _fp32_matrix_on_device(x))
+    fused = _resolve_fused(fused, on_device and L >= 1 and ops.residual_supported(D, H, L), on_device and residual_fused_default(D, H, L),
+                           f"residual_stack(fused=True): the kernels do not serve D={D} H={H} units={L} on {store.device}")
     if not fused:
         for i in range(first_index, first_index + L):
             h = dense(x, H, activation="relu", name=f"dense_{i}_0")
@@ -1155,7 +1165,7 @@ def residual_stack(x: torch.Tensor, internal_dim: int, num_units: int, first_ind
                 params[2 * j + 1].append(store.get_variable("bias", shape[1:], zeros))
     if store.building:
         return torch.zeros_like(x)
-    return ops.residual_stack(x if x.is_contiguous() else x.contiguous(), *params, anchor=store.anchor)
+    return ops.residual_stack(ops._contig(x), *params, anchor=store.anchor)
 
 
 def residual_unit(x: torch.Tensor, internal_dim: int, index: int, fused: Optional[bool] = None) -> torch.Tensor:
@@ -1179,8 +1189,7 @@ def _afm_identity_weight(K: int, device) -> Variable:
 def afm_fused_served(fields: torch.Tensor, F: int, K: int, t: int) -> bool:
     """Whether afm_attention(fused=True) has a kernel for these fields: an fp32 [B >= 1, F * K] device tensor of a served shape."""
     from . import ops
-    return (fields.is_cuda and fields.dtype == torch.float32 and fields.dim() == 2 and fields.shape[0] >= 1
-            and fields.shape[1] == F * K and ops.afm_supported(F, K, t))
+    return _fp32_matrix_on_device(fields) and fields.shape[0] >= 1 and fields.shape[1] == F * K and ops.afm_supported(F, K, t)
 
 
 def afm_fused_default(fields: torch.Tensor, F: int, K: int, t: int) -> bool:
@@ -1205,12 +1214,9 @@ def afm_attention(fields: torch.Tensor, F: int, K: int, w: Variable, b: Variable
     store = current_store()
     F, K = int(F), int(K)
     t = int(w.data.shape[1])
-    if fused is None:
-        fused = afm_fused_default(fields, F, K, t)
-    elif fused and not afm_fused_served(fields, F, K, t):
-        raise ValueError(f"afm_attention(fused=True): no fused kernel serves F={F} K={K} t={t} on {fields.device}")
-    if fused:
-        return ops.afm_attention(fields if fields.is_contiguous() else fields.contiguous(), F, K, w, b, h, anchor=store.anchor)
+    served = afm_fused_served(fields, F, K, t)                                    # (= afm_fused_default)
+    if _resolve_fused(fused, served, served, f"afm_attention(fused=True): no fused kernel serves F={F} K={K} t={t} on {fields.device}"):
+        return ops.afm_attention(ops._contig(fields), F, K, w, b, h, anchor=store.anchor)
     B, P = fields.shape[0], F * (F - 1) // 2
     # pair Hadamard products over all F fields: the bilinear kernel pairs the first F' - 1 of F' fields -> one zero field
     padded = torch.cat([fields, fields.new_zeros(B, K)], dim=1).reshape(B, F + 1, K)
@@ -1238,7 +1244,7 @@ def interacting_layer(x: torch.Tensor, F: int, att_embedding_size: int, head_num
     w_res = store.get_variable(f"interacting_layer_{index}_w_res", (D, H * A)) if use_res else None
     if store.building:
         return x.new_zeros(x.shape[0], F * H * A)
-    return ops.autoint_layer(x if x.is_contiguous() else x.contiguous(), F, *ws, w_res, anchor=store.anchor)
+    return ops.autoint_layer(ops._contig(x), F, *ws, w_res, anchor=store.anchor)
 
 
 # ---- DCN-V2's cross layer (Wang et al., WWW 2021, eq. 4) ---------------------------------------------------------------------------------
@@ -1246,8 +1252,7 @@ def cross_mix_fused_default(x0: torch.Tensor, low_rank: int, num_experts: int) -
     """What cross_mix_layer(fused=None) picks: the kernels wherever they serve the tensor and the shape (csrc/dcnv2.hip; the
     measurement: DESIGN.md §5 "DCN-V2 cross layer")."""
     from . import ops
-    return bool(isinstance(x0, torch.Tensor) and x0.dim() == 2 and x0.is_cuda and x0.dtype == torch.float32
-                and ops.dcnv2_supported(int(x0.shape[1]), int(low_rank), int(num_experts)))
+    return _fp32_matrix_on_device(x0) and ops.dcnv2_supported(int(x0.shape[1]), int(low_rank), int(num_experts))
 
 
 def cross_mix_layer(x0: torch.Tensor, xl: torch.Tensor, low_rank: int, num_experts: int, index: int, fused=None) -> torch.Tensor:
@@ -1268,13 +1273,11 @@ def cross_mix_layer(x0: torch.Tensor, xl: torch.Tensor, low_rank: int, num_exper
         bias = store.get_variable("bias", (D,), zeros)
     if store.building:
         return torch.zeros_like(x0)
-    if fused is None:
-        fused = cross_mix_fused_default(x0, r, E)
-    if fused:
+    default = cross_mix_fused_default(x0, r, E)
+    if _resolve_fused(fused, default, default, None):        # (True on a shape the kernels do not serve: ops.dcnv2_layer refuses)
         same = xl is x0
-        x0 = x0 if x0.is_contiguous() else x0.contiguous()
-        return ops.dcnv2_layer(x0, x0 if same else (xl if xl.is_contiguous() else xl.contiguous()), V, C, U, gate, bias,
-                               anchor=store.anchor)
+        x0 = ops._contig(x0)
+        return ops.dcnv2_layer(x0, x0 if same else ops._contig(xl), V, C, U, gate, bias, anchor=store.anchor)
     Vt, Ct, Ut, gt, bt = (ops.variable_leaf(v, store.anchor) for v in (V, C, U, gate, bias))
     v = torch.tanh(torch.einsum("bd,edr->ber", xl, Vt))
     c = torch.tanh(torch.einsum("ber,ers->bes", v, Ct))
@@ -1296,8 +1299,7 @@ def flen_fused_default(fields: torch.Tensor, F: int, M: int, K: int) -> bool:
     """What field_wise_bi_interaction(fused=None) picks: the kernels wherever they serve the tensor and the shape (csrc/flen.hip;
     the measurement: DESIGN.md §5 "FLEN field-wise bi-interaction" — they were the faster path at every measured shape class)."""
     from . import ops
-    return bool(isinstance(fields, torch.Tensor) and fields.dim() == 2 and fields.is_cuda and fields.dtype == torch.float32
-                and ops.flen_supported(int(F), int(M), int(K)))
+    return _fp32_matrix_on_device(fields) and ops.flen_supported(int(F), int(M), int(K))
 
 
 _flen_index_cache: dict = {}
@@ -1344,14 +1346,12 @@ def field_wise_bi_interaction(fields: torch.Tensor, group_of, dice_rate: float =
     bias = store.get_variable("bias", (K,), zeros)
     if store.building:
         return fields.new_zeros(B, M * K), fields.new_zeros(B, K)
-    if fused is None:
-        fused = flen_fused_default(fields, F, M, K)
-    elif fused and not flen_fused_default(fields, F, M, K):
-        raise ValueError(f"field_wise_bi_interaction(fused=True): no fused kernel serves F={F} M={M} K={K} on {fields.device}")
+    served = flen_fused_default(fields, F, M, K)
+    fused = _resolve_fused(fused, served, served,
+                           f"field_wise_bi_interaction(fused=True): no fused kernel serves F={F} M={M} K={K} on {fields.device}")
     dice = drop_spec((B, P + M, K), float(dice_rate), fields.device) if (training and dice_rate and dice_rate > 0.0) else None
     if fused:
-        return ops.flen_interaction(fields if fields.is_contiguous() else fields.contiguous(), F, group_of, r_mf, r_fm, bias,
-                                    dice=dice, anchor=store.anchor)
+        return ops.flen_interaction(ops._contig(fields), F, group_of, r_mf, r_fm, bias, dice=dice, anchor=store.anchor)
     mf_w, fm_w, b = (ops.variable_leaf(v, store.anchor) for v in (r_mf, r_fm, bias))
     x = fields.reshape(B, F, K)
     members, first, second = _flen_indices(group_of, M, fields.device)

@@ -155,6 +155,64 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return w
 
 
+def _contig(t: Optional[torch.Tensor]):
+    """t itself where it is contiguous (or None), else a contiguous copy"""
+    return t if t is None or t.is_contiguous() else t.contiguous()
+
+
+# ---- Parameters of a fused layer: Variable or tensor --------------------------------------------------------------------------
+# The one statement of the convention of bst_attention, bst_ffn, afm_attention, autoint_layer, dcnv2_layer, flen_interaction,
+# dien_gru and dien_evolve.  Each parameter is a Variable or a plain tensor; an optional one (AutoInt's wres, DCN-V2's gate) may
+# be None.  The kernel writes a Variable's gradient into Variable.grad, OVERWRITING it, and autograd receives None for it; a
+# tensor's gradient goes to a new buffer that autograd receives.  The wrapper calls
+#     Fn.apply(anchor, inputs.., flags.., params, *_param_tail(params))
+# `anchor` (VariableStore.anchor | None) makes the node differentiable when every parameter is a Variable; autograd does not look
+# into the list `params`, so the tail shows it the tensors.  forward: ts, vs = _split_params(params).  backward: outs =
+# _grad_buffers(ts, vs), the launch, return _param_returns(ctx, {position among forward's arguments: input gradient}, outs, vs).
+def _split_params(params):
+    """-> (the tensors the kernels read, the Variables | None), each as long as params; an absent parameter is None in both"""
+    return [p.data if isinstance(p, Variable) else p for p in params], [p if isinstance(p, Variable) else None for p in params]
+
+
+def _param_tail(params):
+    """the `*tensors` of Function.apply: params with None where it holds a Variable (or nothing)"""
+    return [None if isinstance(p, Variable) else p for p in params]
+
+
+def _grad_buffers(ts, vs):
+    """per parameter, the buffer the kernel writes its gradient to: Variable.grad, a new tensor, None for an absent one"""
+    return [v.grad if v is not None else t if t is None else torch.empty_like(t) for t, v in zip(ts, vs)]
+
+
+def _param_returns(ctx, input_grads: dict, outs, vs) -> tuple:
+    """What backward returns, one slot per argument of forward (ctx.needs_input_grad counts them; the last len(vs) are the tail):
+    None before the tail except the input_grads that are needed; in the tail a tensor parameter's buffer, None for a Variable."""
+    need = ctx.needs_input_grad
+    head = [None] * (len(need) - len(vs))
+    for i, g in input_grads.items():
+        if need[i]:
+            head[i] = g
+    return (*head, *[None if v is not None else o for o, v in zip(outs, vs)])
+
+
+def _check_param_shapes(what: str, ts, shapes, names, chk: bool = False) -> None:
+    """Every present parameter has its shape, else ValueError; chk: each goes through _chk (float32, contiguous) first."""
+    for t, shape, name in zip(ts, shapes, names):
+        if t is not None and chk:
+            _chk(t, torch.float32, f"{what}: {name}")
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {shape}")
+
+
+def _check_fp32_on_device(what: str, ts, names) -> None:
+    """Every present tensor is contiguous float32 on the HIP device of the first one (the layer's input), else ValueError."""
+    for t, name in zip(ts, names):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != ts[0].device):
+            owner = names[0] + ("'" if names[0].endswith("s") else "'s")
+            raise ValueError(f"{what}: {name} must be a contiguous float32 tensor on {owner} device, got {t.dtype} on {t.device}"
+                             f"{', not contiguous' * (not t.is_contiguous())}")
+
+
 # =============================================================================================
 # K1: embedding gather
 # =============================================================================================
@@ -1385,8 +1443,7 @@ class _FfmFn(Function):
             return None, None, None, None, None, None
         ns = F - len(bags)
         W = (F - 1) * K
-        g = g.reshape(B)
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _contig(g.reshape(B))
         d_single = torch.empty(B, ns * W, device=g.device, dtype=torch.float32) if ns else None
         d_bags = [torch.empty(bg.values.numel(), W, device=g.device, dtype=torch.float32) for bg in bags]
         cbags = _ffm_bag_array(bags, d_bags)
@@ -2347,7 +2404,7 @@ class _MixFn(Function):
         x, p, *experts = ctx.saved_tensors
         G = len(ws)
         M = 1 if spec.sum_outputs else G
-        gs = [None if g is None else (g if g.is_contiguous() else g.contiguous()) for g in grads[:M]]
+        gs = [_contig(g) for g in grads[:M]]
         if spec.entry.skip_unused_backward and all(g is None for g in gs):
             return (None,) * (3 + E + G)
         B, In = x.shape
@@ -2390,7 +2447,7 @@ def _mix_launch(entry: _MixEntry, x, gate_kernels, experts, selection, sum_outpu
         _chk(k.data if isinstance(k, Variable) else k, torch.float32, "gate kernel")
     srcs = [getattr(t, "_recalgo_relu_src", None) if getattr(t, "_recalgo_relu_scale", 1.0) == 1.0 else None for t in experts]
     srcs = srcs if all(s is not None for s in srcs) else None
-    experts = [_mat(t if t.is_contiguous() else t.contiguous(), "expert") for t in experts]
+    experts = [_mat(_contig(t), "expert") for t in experts]
     spec = GateMixSpec(gate_kernels, selection, srcs, x_grad_sink, sum_outputs=sum_outputs, entry=entry)
     gate_ts = [None if isinstance(k, Variable) else k for k in gate_kernels]
     *outs, p = _MixFn.apply(anchor, spec, x, *experts, *gate_ts)
@@ -2810,24 +2867,13 @@ def bst_supported(T: int, d: int, H: int) -> bool:
     return bool(_lib_().recalgo_bst_supported(int(T), int(d), int(H)))
 
 
-def _bst_split(params):
-    """-> (the tensors the kernels read, the Variables | None).  A Variable's gradient is written to Variable.grad, a tensor's
-    is returned to autograd."""
-    return [p.data if isinstance(p, Variable) else p for p in params], [p if isinstance(p, Variable) else None for p in params]
-
-
-def _bst_grad_buffers(ts, vs):
-    """per parameter, the buffer its gradient is written to: Variable.grad, or a new tensor"""
-    return [v.grad if v is not None else torch.empty_like(t) for t, v in zip(ts, vs)]
-
-
 class _BstAttnFn(Function):
-    """include/recalgo_bst.h recalgo_bst_attn_fwd / recalgo_bst_attn_bwd; params = (pos, w_q, w_k, w_v, w_o, gamma, beta),
-    `tensors` the same seven with None where params holds a Variable."""
+    """include/recalgo_bst.h recalgo_bst_attn_fwd / recalgo_bst_attn_bwd; params = (pos, w_q, w_k, w_v, w_o, gamma, beta) ("Parameters
+    of a fused layer" above).  `pos` alone is not written by the kernel: its gradient is the table's first T rows."""
 
     @staticmethod
     def forward(ctx, anchor, x, keys_length, heads, differentiated, params, *tensors):
-        ts, vs = _bst_split(params)
+        ts, vs = _split_params(params)
         B, T, d = x.shape
         n1 = torch.empty(B, T, d, device=x.device, dtype=torch.float32)
         _lib_().recalgo_bst_attn_fwd(_p(x), *[_p(t) for t in ts[:1]], _p(keys_length), *[_p(t) for t in ts[1:]], B, T, d, heads,
@@ -2843,11 +2889,11 @@ class _BstAttnFn(Function):
         ts, vs, H = ctx.ts, ctx.vs, ctx.heads
         x, keys_length = ctx.saved_tensors
         B, T, d = x.shape
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _contig(g)
         lib = _lib_()
         dx = torch.empty_like(x)
         dpos = torch.empty(T, d, device=x.device, dtype=torch.float32)
-        outs = _bst_grad_buffers(ts[1:], vs[1:])         # dw_q, dw_k, dw_v, dw_o, dgamma, dbeta
+        outs = _grad_buffers(ts[1:], vs[1:])             # dw_q, dw_k, dw_v, dw_o, dgamma, dbeta
         ws = _workspace(int(lib.recalgo_bst_attn_bwd_workspace_bytes(B, T, d, H)), x.device)
         lib.recalgo_bst_attn_bwd(_p(x), _p(ts[0]), _p(keys_length), *[_p(t) for t in ts[1:6]], _p(g), B, T, d, H, _p(dx), _p(dpos),
                                  *[_p(o) for o in outs], _p(ws), _stream(x))
@@ -2866,18 +2912,17 @@ class _BstAttnFn(Function):
         else:
             dpos_ret = torch.zeros_like(ts[0])
             dpos_ret[:T].copy_(dpos)
-        rets = [dpos_ret] + [None if v is not None else o for o, v in zip(outs, vs[1:])]
-        return (None, dx if ctx.needs_input_grad[1] else None, None, None, None, None, *rets)
+        return _param_returns(ctx, {1: dx}, [dpos_ret] + outs, vs)
 
 
 class _BstFfnFn(Function):
-    """include/recalgo_bst.h recalgo_bst_ffn_fwd / recalgo_bst_ffn_bwd; params = (ffn_w, ffn_b, gamma, beta).  -> (out | None,
-    pool | None)."""
+    """include/recalgo_bst.h recalgo_bst_ffn_fwd / recalgo_bst_ffn_bwd; params = (ffn_w, ffn_b, gamma, beta) ("Parameters of a
+    fused layer" above).  -> (out | None, pool | None)."""
 
     @staticmethod
     def forward(ctx, anchor, n1, mean_pool, want_out, want_pool, params, *tensors):
         ctx.set_materialize_grads(False)
-        ts, vs = _bst_split(params)
+        ts, vs = _split_params(params)
         B, T, d = n1.shape
         out = torch.empty(B, T, d, device=n1.device, dtype=torch.float32) if want_out else None
         pool = torch.empty(B, d, device=n1.device, dtype=torch.float32) if want_pool else None
@@ -2891,32 +2936,28 @@ class _BstFfnFn(Function):
         ts, vs = ctx.ts, ctx.vs
         (n1,) = ctx.saved_tensors
         if g_out is None and g_pool is None:
-            return (None,) * (6 + len(ts))
+            return (None,) * len(ctx.needs_input_grad)
         B, T, d = n1.shape
-        g_out = None if g_out is None else (g_out if g_out.is_contiguous() else g_out.contiguous())
-        g_pool = None if g_pool is None else (g_pool if g_pool.is_contiguous() else g_pool.contiguous())
+        g_out, g_pool = _contig(g_out), _contig(g_pool)
         lib = _lib_()
         dn1 = torch.empty_like(n1)
-        outs = _bst_grad_buffers(ts, vs)                 # dw, db, dgamma, dbeta
+        outs = _grad_buffers(ts, vs)                     # dw, db, dgamma, dbeta
         ws = _workspace(int(lib.recalgo_bst_ffn_bwd_workspace_bytes(B, d)), n1.device)
         lib.recalgo_bst_ffn_bwd(_p(n1), *[_p(t) for t in ts[:3]], _p(g_out), _p(g_pool), B, T, d, ctx.mean_pool, _p(dn1),
                                 *[_p(o) for o in outs], _p(ws), _stream(n1))
-        rets = [None if v is not None else o for o, v in zip(outs, vs)]
-        return (None, dn1 if ctx.needs_input_grad[1] else None, None, None, None, None, *rets)
+        return _param_returns(ctx, {1: dn1}, outs, vs)
 
 
-def _bst_check(x, T, d, H, params, shapes, what):
+def _bst_check(x, T, d, H, ts, shapes, what):
     if not bst_supported(T, d, H):
         raise ValueError(f"{what}: the BST kernels serve 1 <= T <= {BST_MAX_T}, d in (4, 8, 12, 16) and 1 <= heads <= "
                          f"{BST_MAX_HEADS}; got T={T} d={d} heads={H} (there is no fallback)")
     if x.shape[0] == 0:
         raise ValueError(f"{what}: empty batch")
-    ts, _ = _bst_split(params)
-    for t, shape, name in zip(ts, shapes, ("pos", "w_q", "w_k", "w_v", "w_o", "gamma", "beta") if len(shapes) == 7
-                              else ("ffn_w", "ffn_b", "gamma", "beta")):
-        _chk(t, torch.float32, f"{what}: {name}")
-        if (tuple(t.shape) != shape) if name != "pos" else (t.dim() != 2 or t.shape[0] < T or t.shape[1] != d):
-            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {shape}")
+    names = ("pos", "w_q", "w_k", "w_v", "w_o", "gamma", "beta") if len(shapes) == 7 else ("ffn_w", "ffn_b", "gamma", "beta")
+    if names[0] == "pos" and ts[0].dim() == 2 and ts[0].shape[0] >= T and ts[0].shape[1] == d:
+        shapes = [tuple(ts[0].shape)] + shapes[1:]       # (the table may be longer than T: its first T rows are read)
+    _check_param_shapes(what, ts, shapes, names, chk=True)
 
 
 def bst_attention(x: torch.Tensor, keys_length: torch.Tensor, pos, w_q, w_k, w_v, w_o, gamma, beta, anchor=None) -> torch.Tensor:
@@ -2929,15 +2970,14 @@ def bst_attention(x: torch.Tensor, keys_length: torch.Tensor, pos, w_q, w_k, w_v
         raise ValueError("bst_attention: x must be [B, T, d]")
     B, T, d = x.shape
     params = [pos, w_q, w_k, w_v, w_o, gamma, beta]
-    wq_t = w_q.data if isinstance(w_q, Variable) else w_q
-    H = int(wq_t.shape[0]) if wq_t.dim() == 3 else 0
-    _bst_check(x, T, d, H, params, [(T, d), (H, d, d), (H, d, d), (H, d, d), (H * d, d), (d,), (d,)], "bst_attention")
+    ts, _ = _split_params(params)
+    H = int(ts[1].shape[0]) if ts[1].dim() == 3 else 0
+    _bst_check(x, T, d, H, ts, [(T, d), (H, d, d), (H, d, d), (H, d, d), (H * d, d), (d,), (d,)], "bst_attention")
     _chk(x, torch.float32, "bst_attention: x")
     keys_length = keys_length.reshape(-1).to(torch.int32).contiguous()
     if keys_length.numel() != B:
         raise ValueError("bst_attention: one keys_length per example")
-    tensors = [None if isinstance(p, Variable) else p for p in params]
-    return _BstAttnFn.apply(anchor, x, keys_length, H, torch.is_grad_enabled(), params, *tensors)
+    return _BstAttnFn.apply(anchor, x, keys_length, H, torch.is_grad_enabled(), params, *_param_tail(params))
 
 
 def bst_ffn(n1: torch.Tensor, ffn_w, ffn_b, gamma, beta, pool: Optional[str] = None, want_out: bool = True, anchor=None):
@@ -2948,10 +2988,9 @@ def bst_ffn(n1: torch.Tensor, ffn_w, ffn_b, gamma, beta, pool: Optional[str] = N
         raise ValueError("bst_ffn: n1 must be [B, T, d], pool one of None, 'sum', 'mean', and some output wanted")
     B, T, d = n1.shape
     params = [ffn_w, ffn_b, gamma, beta]
-    _bst_check(n1, T, d, 1, params, [(d, d), (d,), (d,), (d,)], "bst_ffn")
+    _bst_check(n1, T, d, 1, _split_params(params)[0], [(d, d), (d,), (d,), (d,)], "bst_ffn")
     _chk(n1, torch.float32, "bst_ffn: n1")
-    tensors = [None if isinstance(p, Variable) else p for p in params]
-    return _BstFfnFn.apply(anchor, n1, pool == "mean", bool(want_out), pool is not None, params, *tensors)
+    return _BstFfnFn.apply(anchor, n1, pool == "mean", bool(want_out), pool is not None, params, *_param_tail(params))
 
 
 # =============================================================================================
@@ -2991,7 +3030,7 @@ class _ResidualStackFn(Function):
         x, hs, ys = ctx.saved_tensors
         L, B, D = ys.shape
         H = hs.shape[2]
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _contig(g)
         dzs, dhs, dx = torch.empty_like(ys), torch.empty_like(hs), torch.empty_like(x)
         _lib_().recalgo_res_stack_bwd(_p(g), _p(hs), _p(ys), _ptr_array([v.data for v in w0s]), _ptr_array([v.data for v in w1s]),
                                       B, D, H, L, _p(dzs), _p(dhs), _p(dx), _stream(x))
@@ -3033,12 +3072,12 @@ def afm_supported(F: int, K: int, t: int) -> bool:
 
 
 class _AfmAttentionFn(Function):
-    """include/recalgo_afm.h recalgo_afm_attention_fwd / recalgo_afm_attention_bwd; params = (w, b, h), `tensors` the same three
-    with None where params holds a Variable.  Saved: the fields and the pre-softmax scores [B, P]."""
+    """include/recalgo_afm.h recalgo_afm_attention_fwd / recalgo_afm_attention_bwd; params = (w, b, h) ("Parameters of a fused
+    layer" above).  Saved: the fields and the pre-softmax scores [B, P]."""
 
     @staticmethod
     def forward(ctx, anchor, fields, F, K, differentiated, params, *tensors):
-        ts, vs = _bst_split(params)
+        ts, vs = _split_params(params)
         B, t = fields.shape[0], int(ts[0].shape[1])
         out = torch.empty(B, K, device=fields.device, dtype=torch.float32)
         # (the caller's grad mode: inside a Function's forward it is always off; PREDICT / EVAL keep no scores)
@@ -3054,15 +3093,14 @@ class _AfmAttentionFn(Function):
         ts, vs, F, K = ctx.ts, ctx.vs, ctx.F, ctx.K
         fields, scores = ctx.saved_tensors
         B, t = fields.shape[0], int(ts[0].shape[1])
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _contig(g)
         lib = _lib_()
         d_fields = torch.empty_like(fields)
-        outs = _bst_grad_buffers(ts, vs)                 # dw, db, dh
+        outs = _grad_buffers(ts, vs)                     # dw, db, dh
         ws = _workspace(int(lib.recalgo_afm_bwd_workspace_bytes(B, F, K, t)), fields.device)
         lib.recalgo_afm_attention_bwd(_p(g), _p(fields), *[_p(x) for x in ts], _p(scores), B, F, K, t, _p(d_fields),
                                       *[_p(o) for o in outs], _p(ws), _stream(fields))
-        rets = [None if v is not None else o for o, v in zip(outs, vs)]
-        return (None, d_fields if ctx.needs_input_grad[1] else None, None, None, None, None, *rets)
+        return _param_returns(ctx, {1: d_fields}, outs, vs)
 
 
 def afm_attention(fields: torch.Tensor, F: int, K: int, w, b, h, anchor=None) -> torch.Tensor:
@@ -3073,7 +3111,7 @@ def afm_attention(fields: torch.Tensor, F: int, K: int, w, b, h, anchor=None) ->
     the kernels do not serve (afm_supported): ValueError, there is no fallback here (nn.afm_attention owns the composed chain)."""
     F, K = int(F), int(K)
     params = [w, b, h]
-    ts, _ = _bst_split(params)
+    ts, _ = _split_params(params)
     t = int(ts[0].shape[1]) if ts[0].dim() == 2 else 0
     if not afm_supported(F, K, t):
         raise ValueError(f"afm_attention: the kernels serve 2 <= F <= 64, K % 4 == 0 with 4 <= K <= 32 and t % 16 == 0 with "
@@ -3085,8 +3123,7 @@ def afm_attention(fields: torch.Tensor, F: int, K: int, w, b, h, anchor=None) ->
         _chk(x, torch.float32, f"afm_attention: {name}")
         if x.numel() != n or (name == "w" and tuple(x.shape) != (K, t)):
             raise ValueError(f"afm_attention: {name} has shape {tuple(x.shape)}")
-    tensors = [None if isinstance(p, Variable) else p for p in params]
-    return _AfmAttentionFn.apply(anchor, fields, F, K, torch.is_grad_enabled(), params, *tensors)
+    return _AfmAttentionFn.apply(anchor, fields, F, K, torch.is_grad_enabled(), params, *_param_tail(params))
 
 
 # =============================================================================================
@@ -3100,16 +3137,15 @@ def autoint_supported(F: int, D: int, A: int, H: int) -> bool:
 
 
 class _AutoIntLayerFn(Function):
-    """include/recalgo_autoint.h recalgo_autoint_layer_fwd / recalgo_autoint_layer_bwd; params = (wq, wk, wv[, wres]), `tensors`
-    the same with None where params holds a Variable.  Saved: x and y (the backward recomputes everything between them)."""
+    """include/recalgo_autoint.h recalgo_autoint_layer_fwd / recalgo_autoint_layer_bwd; params = (wq, wk, wv, wres | None)
+    ("Parameters of a fused layer" above).  Saved: x and y (the backward recomputes everything between them)."""
 
     @staticmethod
     def forward(ctx, anchor, x, F, differentiated, params, *tensors):
-        ts, vs = _bst_split(params)
+        ts, vs = _split_params(params)
         B, (H, D, A) = x.shape[0], ts[0].shape
         y = torch.empty(B, F * H * A, device=x.device, dtype=torch.float32)
-        wres = ts[3] if len(ts) == 4 else None
-        _lib_().recalgo_autoint_layer_fwd(_p(x), _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(wres), B, F, D, A, H, _p(y), _stream(x))
+        _lib_().recalgo_autoint_layer_fwd(_p(x), *[_p(t) for t in ts], B, F, D, A, H, _p(y), _stream(x))
         if differentiated:               # (the caller's grad mode: inside a Function's forward it is always off)
             ctx.ts, ctx.vs, ctx.F = ts, vs, F
             ctx.save_for_backward(x, y)
@@ -3120,17 +3156,14 @@ class _AutoIntLayerFn(Function):
         ts, vs, F = ctx.ts, ctx.vs, ctx.F
         x, y = ctx.saved_tensors
         B, (H, D, A) = x.shape[0], ts[0].shape
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _contig(g)
         lib = _lib_()
         dx = torch.empty_like(x)
-        outs = _bst_grad_buffers(ts, vs)                 # dwq, dwk, dwv[, dwres]
-        has_res = len(ts) == 4
-        ws = _workspace(int(lib.recalgo_autoint_bwd_workspace_bytes(B, F, D, A, H, int(has_res))), x.device)
-        lib.recalgo_autoint_layer_bwd(_p(g), _p(x), _p(y), _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3] if has_res else None),
-                                      B, F, D, A, H, _p(dx), _p(outs[0]), _p(outs[1]), _p(outs[2]),
-                                      _p(outs[3] if has_res else None), _p(ws), _stream(x))
-        rets = [None if v is not None else o for o, v in zip(outs, vs)]
-        return (None, dx if ctx.needs_input_grad[1] else None, None, None, None, *rets)
+        outs = _grad_buffers(ts, vs)                     # dwq, dwk, dwv, dwres | None
+        ws = _workspace(int(lib.recalgo_autoint_bwd_workspace_bytes(B, F, D, A, H, int(ts[3] is not None))), x.device)
+        lib.recalgo_autoint_layer_bwd(_p(g), _p(x), _p(y), *[_p(t) for t in ts], B, F, D, A, H, _p(dx), *[_p(o) for o in outs],
+                                      _p(ws), _stream(x))
+        return _param_returns(ctx, {1: dx}, outs, vs)
 
 
 def autoint_layer(x: torch.Tensor, F: int, wq, wk, wv, wres=None, anchor=None) -> torch.Tensor:
@@ -3140,8 +3173,8 @@ def autoint_layer(x: torch.Tensor, F: int, wq, wk, wv, wres=None, anchor=None) -
     a tensor.  With grad enabled the forward keeps x and y, nothing else; the backward is one launch and the fixed-order sum of
     its partial rows.  Shapes the kernels do not serve (autoint_supported): ValueError — there is no fallback."""
     F = int(F)
-    params = [wq, wk, wv] + ([wres] if wres is not None else [])
-    ts, _ = _bst_split(params)
+    params = [wq, wk, wv, wres]
+    ts, _ = _split_params(params)
     if ts[0].dim() != 3:
         raise ValueError(f"autoint_layer: wq must be [H, D, A], got {tuple(ts[0].shape)}")
     H, D, A = (int(v) for v in ts[0].shape)
@@ -3153,15 +3186,10 @@ def autoint_layer(x: torch.Tensor, F: int, wq, wk, wv, wres=None, anchor=None) -
                          f"(there is no fallback)")
     if x.dim() != 2 or x.shape[0] == 0 or x.shape[1] != F * D:
         raise ValueError(f"autoint_layer: x must be a non-empty [B, F * D = {F * D}] matrix, got {tuple(x.shape)}")
-    for t, shape, name in zip(ts, ((H, D, A), (H, D, A), (H, D, A), (D, H * A)), ("wq", "wk", "wv", "wres")):
-        if tuple(t.shape) != shape:
-            raise ValueError(f"autoint_layer: {name} has shape {tuple(t.shape)}, expected {shape}")
-    for t, name in zip([x] + ts, ("x", "wq", "wk", "wv", "wres")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != x.device:
-            raise ValueError(f"autoint_layer: {name} must be a contiguous float32 tensor on x's device, got {t.dtype} on {t.device}"
-                             f"{'' if t.is_contiguous() else ', not contiguous'}")
-    tensors = [None if isinstance(p, Variable) else p for p in params]
-    return _AutoIntLayerFn.apply(anchor, x, F, torch.is_grad_enabled(), params, *tensors)
+    names = ("wq", "wk", "wv", "wres")
+    _check_param_shapes("autoint_layer", ts, ((H, D, A), (H, D, A), (H, D, A), (D, H * A)), names)
+    _check_fp32_on_device("autoint_layer", [x] + ts, ("x",) + names)
+    return _AutoIntLayerFn.apply(anchor, x, F, torch.is_grad_enabled(), params, *_param_tail(params))
 
 
 # =============================================================================================
@@ -3175,47 +3203,38 @@ def dcnv2_supported(D: int, r: int, E: int) -> bool:
 
 
 class _Dcnv2LayerFn(Function):
-    """include/recalgo_dcnv2.h recalgo_dcnv2_layer_fwd / recalgo_dcnv2_layer_bwd; params = (V, C, U, gate | None, bias), `tensors`
-    the same with None where params holds a Variable.  Saved: x0 and xl (the backward recomputes everything from them).  `same`:
-    xl IS x0 (a stack's first layer) — x0 is passed once and receives dx0 + dxl."""
+    """include/recalgo_dcnv2.h recalgo_dcnv2_layer_fwd / recalgo_dcnv2_layer_bwd; params = (V, C, U, gate | None, bias) ("Parameters
+    of a fused layer" above).  Saved: x0 and xl (the backward recomputes everything from them).  `same`: xl IS x0 (a stack's
+    first layer) — x0 is passed once and receives dx0 + dxl."""
 
     @staticmethod
     def forward(ctx, anchor, x0, xl, differentiated, params, *tensors):
         same = xl is None
         xl = x0 if same else xl
-        gated = params[3] is not None
-        ts, vs = _bst_split([p for p in params if p is not None])
+        ts, vs = _split_params(params)
         B, (E, D, r) = x0.shape[0], ts[0].shape
         y = torch.empty_like(x0)
-        gate, bias = (ts[3], ts[4]) if gated else (None, ts[3])
-        _lib_().recalgo_dcnv2_layer_fwd(_p(x0), _p(xl), _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(gate), _p(bias), B, D, r, E, _p(y),
-                                        _stream(x0))
+        _lib_().recalgo_dcnv2_layer_fwd(_p(x0), _p(xl), *[_p(t) for t in ts], B, D, r, E, _p(y), _stream(x0))
         if differentiated:               # (the caller's grad mode: inside a Function's forward it is always off)
-            ctx.ts, ctx.vs, ctx.gated, ctx.same = ts, vs, gated, same
+            ctx.ts, ctx.vs, ctx.same = ts, vs, same
             ctx.save_for_backward(x0, xl)
         return y
 
     @staticmethod
     def backward(ctx, g):
-        ts, vs, gated, same = ctx.ts, ctx.vs, ctx.gated, ctx.same
+        ts, vs, same = ctx.ts, ctx.vs, ctx.same
         x0, xl = ctx.saved_tensors
         B, (E, D, r) = x0.shape[0], ts[0].shape
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _contig(g)
         lib = _lib_()
         dx0, dxl = torch.empty_like(x0), torch.empty_like(xl)
-        outs = _bst_grad_buffers(ts, vs)                 # dV, dC, dU[, dgate], dbias
-        gate, bias = (ts[3], ts[4]) if gated else (None, ts[3])
-        dgate, dbias = (outs[3], outs[4]) if gated else (None, outs[3])
+        outs = _grad_buffers(ts, vs)                     # dV, dC, dU, dgate | None, dbias
         ws = _workspace(int(lib.recalgo_dcnv2_bwd_workspace_bytes(B, D, r, E)), x0.device)
-        lib.recalgo_dcnv2_layer_bwd(_p(g), _p(x0), _p(xl), _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(gate), _p(bias), B, D, r, E,
-                                    _p(dx0), _p(dxl), _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(dgate), _p(dbias), _p(ws),
-                                    _stream(x0))
-        rets = [None if v is not None else o for o, v in zip(outs, vs)]
-        if not gated:
-            rets.insert(3, None)
+        lib.recalgo_dcnv2_layer_bwd(_p(g), _p(x0), _p(xl), *[_p(t) for t in ts], B, D, r, E, _p(dx0), _p(dxl),
+                                    *[_p(o) for o in outs], _p(ws), _stream(x0))
         if same:
-            return (None, dx0.add_(dxl) if ctx.needs_input_grad[1] else None, None, None, None, *rets)
-        return (None, dx0 if ctx.needs_input_grad[1] else None, dxl if ctx.needs_input_grad[2] else None, None, None, *rets)
+            return _param_returns(ctx, {1: dx0.add_(dxl)} if ctx.needs_input_grad[1] else {}, outs, vs)
+        return _param_returns(ctx, {1: dx0, 2: dxl}, outs, vs)
 
 
 def dcnv2_layer(x0: torch.Tensor, xl: torch.Tensor, V, C, U, gate, bias, anchor=None) -> torch.Tensor:
@@ -3226,7 +3245,7 @@ def dcnv2_layer(x0: torch.Tensor, xl: torch.Tensor, V, C, U, gate, bias, anchor=
     the forward keeps x0 and xl, nothing else; the backward recomputes from them and sums its partial rows in fixed order.
     Shapes the kernels do not serve (dcnv2_supported): ValueError — the composed layer is nn.cross_mix_layer(fused=False)."""
     params = [V, C, U, gate, bias]
-    ts, _ = _bst_split([p for p in params if p is not None])
+    ts, _ = _split_params(params)
     if ts[0].dim() != 3:
         raise ValueError(f"dcnv2_layer: V must be [E, D, r], got {tuple(ts[0].shape)}")
     E, D, r = (int(v) for v in ts[0].shape)
@@ -3238,17 +3257,10 @@ def dcnv2_layer(x0: torch.Tensor, xl: torch.Tensor, V, C, U, gate, bias, anchor=
         raise ValueError(f"dcnv2_layer: only a single expert runs without a gate, got E={E}")
     if x0.dim() != 2 or x0.shape[0] == 0 or x0.shape[1] != D or tuple(xl.shape) != tuple(x0.shape):
         raise ValueError(f"dcnv2_layer: x0 and xl must be non-empty [B, D = {D}] matrices, got {tuple(x0.shape)} and {tuple(xl.shape)}")
-    names = ("V", "C", "U") + (("gate",) if gate is not None else ()) + ("bias",)
-    shapes = ((E, D, r), (E, r, r), (E, D, r)) + (((E, D),) if gate is not None else ()) + ((D,),)
-    for t, shape, name in zip(ts, shapes, names):
-        if tuple(t.shape) != shape:
-            raise ValueError(f"dcnv2_layer: {name} has shape {tuple(t.shape)}, expected {shape}")
-    for t, name in zip([x0, xl] + ts, ("x0", "xl") + names):
-        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != x0.device:
-            raise ValueError(f"dcnv2_layer: {name} must be a contiguous float32 tensor on x0's device, got {t.dtype} on {t.device}"
-                             f"{'' if t.is_contiguous() else ', not contiguous'}")
-    tensors = [None if (p is None or isinstance(p, Variable)) else p for p in params]
-    return _Dcnv2LayerFn.apply(anchor, x0, None if xl is x0 else xl, torch.is_grad_enabled(), params, *tensors)
+    names = ("V", "C", "U", "gate", "bias")
+    _check_param_shapes("dcnv2_layer", ts, ((E, D, r), (E, r, r), (E, D, r), (E, D), (D,)), names)
+    _check_fp32_on_device("dcnv2_layer", [x0, xl] + ts, ("x0", "xl") + names)
+    return _Dcnv2LayerFn.apply(anchor, x0, None if xl is x0 else xl, torch.is_grad_enabled(), params, *_param_tail(params))
 
 
 # =============================================================================================
@@ -3267,12 +3279,12 @@ def _flen_groups(group_of):
 
 
 class _FlenFn(Function):
-    """include/recalgo_flen.h recalgo_flen_fwd / recalgo_flen_bwd; params = (r_mf, r_fm, bias), `tensors` the same with None
-    where params holds a Variable.  Saved: x alone (the backward recomputes e and q, and the Dicefactor mask from its key)."""
+    """include/recalgo_flen.h recalgo_flen_fwd / recalgo_flen_bwd; params = (r_mf, r_fm, bias) ("Parameters of a fused layer"
+    above).  Saved: x alone (the backward recomputes e and q, and the Dicefactor mask from its key)."""
 
     @staticmethod
     def forward(ctx, anchor, x, F, group_of, dice, differentiated, params, *tensors):
-        ts, vs = _bst_split(params)
+        ts, vs = _split_params(params)
         B, M, K = x.shape[0], ts[1].shape[0], ts[2].shape[0]
         e = torch.empty(B, M * K, device=x.device, dtype=torch.float32)
         h = torch.empty(B, K, device=x.device, dtype=torch.float32)
@@ -3291,19 +3303,17 @@ class _FlenFn(Function):
         ts, vs, F = ctx.ts, ctx.vs, ctx.F
         x, = ctx.saved_tensors
         B, M, K = x.shape[0], ts[1].shape[0], ts[2].shape[0]
-        g_e = g_e if g_e.is_contiguous() else g_e.contiguous()
-        g_h = g_h if g_h.is_contiguous() else g_h.contiguous()
+        g_e, g_h = _contig(g_e), _contig(g_h)
         lib = _lib_()
         dx = torch.empty_like(x)
-        outs = _bst_grad_buffers(ts, vs)                 # dr_mf, dr_fm, dbias
+        outs = _grad_buffers(ts, vs)                     # dr_mf, dr_fm, dbias
         groups = _flen_groups(ctx.group_of)
         cd, keep = _cdrop(ctx.dice)
         ws = _workspace(int(lib.recalgo_flen_bwd_workspace_bytes(B, F, M, K)), x.device)
         lib.recalgo_flen_bwd(_p(g_e), _p(g_h), _p(x), ctypes.cast(groups, ctypes.c_void_p), _p(ts[0]), _p(ts[1]), cd, B, F, M, K,
                              _p(dx), _p(outs[0]), _p(outs[1]), _p(outs[2]), _p(ws), _stream(x))
         del keep
-        rets = [None if v is not None else o for o, v in zip(outs, vs)]
-        return (None, dx if ctx.needs_input_grad[1] else None, None, None, None, None, None, *rets)
+        return _param_returns(ctx, {1: dx}, outs, vs)
 
 
 def flen_interaction(fields: torch.Tensor, F: int, group_of, r_mf, r_fm, bias, dice: Optional["DropSpec"] = None, anchor=None):
@@ -3317,7 +3327,7 @@ def flen_interaction(fields: torch.Tensor, F: int, group_of, r_mf, r_fm, bias, d
     F = int(F)
     group_of = tuple(int(g) for g in group_of)
     params = [r_mf, r_fm, bias]
-    ts, _ = _bst_split(params)
+    ts, _ = _split_params(params)
     if ts[1].dim() != 1 or ts[2].dim() != 1:
         raise ValueError(f"flen_interaction: r_fm must be [M] and bias [K], got {tuple(ts[1].shape)} and {tuple(ts[2].shape)}")
     M, K = int(ts[1].shape[0]), int(ts[2].shape[0])
@@ -3331,21 +3341,16 @@ def flen_interaction(fields: torch.Tensor, F: int, group_of, r_mf, r_fm, bias, d
         raise ValueError(f"flen_interaction: group_of must map the F={F} fields onto every one of the M={M} groups, got {group_of}")
     if fields.dim() != 2 or fields.shape[0] == 0 or fields.shape[1] != F * K:
         raise ValueError(f"flen_interaction: fields must be a non-empty [B, F * K = {F * K}] matrix, got {tuple(fields.shape)}")
-    for t, shape, name in zip(ts, ((P,), (M,), (K,)), ("r_mf", "r_fm", "bias")):
-        if tuple(t.shape) != shape:
-            raise ValueError(f"flen_interaction: {name} has shape {tuple(t.shape)}, expected {shape}")
-    for t, name in zip([fields] + ts, ("fields", "r_mf", "r_fm", "bias")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != fields.device:
-            raise ValueError(f"flen_interaction: {name} must be a contiguous float32 tensor on fields' device, got {t.dtype} on "
-                             f"{t.device}{'' if t.is_contiguous() else ', not contiguous'}")
+    names = ("r_mf", "r_fm", "bias")
+    _check_param_shapes("flen_interaction", ts, ((P,), (M,), (K,)), names)
+    _check_fp32_on_device("flen_interaction", [fields] + ts, ("fields",) + names)
     if dice is not None:
         if not 0.0 < dice.rate < 1.0:
             raise ValueError(f"flen_interaction: the Dicefactor rate must lie in (0, 1), got {dice.rate}")
         if fields.shape[0] * (P + M) * K >= 1 << 32:
             raise ValueError("flen_interaction: Dicefactor indexes B (P + M) K < 2^32 path components")
         dice.check_mask((fields.shape[0], P + M, K))
-    tensors = [None if isinstance(p, Variable) else p for p in params]
-    return _FlenFn.apply(anchor, fields, F, group_of, dice, torch.is_grad_enabled(), params, *tensors)
+    return _FlenFn.apply(anchor, fields, F, group_of, dice, torch.is_grad_enabled(), params, *_param_tail(params))
 
 
 class _VariableLeafFn(Function):
@@ -3380,12 +3385,12 @@ def dien_supported(T: int, na: int, nh: int) -> bool:
 
 
 class _DienGruFn(Function):
-    """include/recalgo_dien.h recalgo_dien_gru_fwd / recalgo_dien_gru_bwd; params = (Wg, bg, Wc, bc), `tensors` the same four
-    with None where params holds a Variable."""
+    """include/recalgo_dien.h recalgo_dien_gru_fwd / recalgo_dien_gru_bwd; params = (Wg, bg, Wc, bc) ("Parameters of a fused
+    layer" above)."""
 
     @staticmethod
     def forward(ctx, anchor, x, lengths, params, *tensors):
-        ts, vs = _bst_split(params)
+        ts, vs = _split_params(params)
         B, T, na = x.shape
         nh = ts[3].shape[0]
         h = torch.empty(B, T, nh, device=x.device, dtype=torch.float32)
@@ -3400,24 +3405,23 @@ class _DienGruFn(Function):
         x, h = ctx.saved_tensors
         B, T, na = x.shape
         nh = h.shape[2]
-        g = g if g.is_contiguous() else g.contiguous()
+        g = _contig(g)
         lib = _lib_()
         dx = torch.empty_like(x)
-        outs = _bst_grad_buffers(ts, vs)                 # dWg, dbg, dWc, dbc
+        outs = _grad_buffers(ts, vs)                     # dWg, dbg, dWc, dbc
         ws = _workspace(int(lib.recalgo_dien_gru_bwd_workspace_bytes(B, na, nh)), x.device)
         lib.recalgo_dien_gru_bwd(_p(x), _p(lengths), _p(h), *[_p(t) for t in ts], _p(g), B, T, na, nh, _p(dx),
                                  *[_p(o) for o in outs], _p(ws), _stream(x))
-        rets = [None if v is not None else o for o, v in zip(outs, vs)]
-        return (None, dx if ctx.needs_input_grad[1] else None, None, None, *rets)
+        return _param_returns(ctx, {1: dx}, outs, vs)
 
 
 class _DienEvolveFn(Function):
-    """include/recalgo_dien.h recalgo_dien_evolve_fwd / recalgo_dien_evolve_bwd; params = (w_att, Wg, bg, Wc, bc).  -> (final,
-    att, states); only `final` is differentiable."""
+    """include/recalgo_dien.h recalgo_dien_evolve_fwd / recalgo_dien_evolve_bwd; params = (w_att, Wg, bg, Wc, bc) ("Parameters of
+    a fused layer" above).  -> (final, att, states); only `final` is differentiable."""
 
     @staticmethod
     def forward(ctx, anchor, h, target, lengths, mode, params, *tensors):
-        ts, vs = _bst_split(params)
+        ts, vs = _split_params(params)
         B, T, nh = h.shape
         na = target.shape[1]
         att = torch.empty(B, T, device=h.device, dtype=torch.float32)
@@ -3436,16 +3440,14 @@ class _DienEvolveFn(Function):
         h, target, att, states = ctx.saved_tensors
         B, T, nh = h.shape
         na = target.shape[1]
-        g_final = g_final if g_final.is_contiguous() else g_final.contiguous()
+        g_final = _contig(g_final)
         lib = _lib_()
         dh, dtarget = torch.empty_like(h), torch.empty_like(target)
-        outs = _bst_grad_buffers(ts, vs)                 # dw_att, dWg, dbg, dWc, dbc
+        outs = _grad_buffers(ts, vs)                     # dw_att, dWg, dbg, dWc, dbc
         ws = _workspace(int(lib.recalgo_dien_evolve_bwd_workspace_bytes(B, na, nh)), h.device)
         lib.recalgo_dien_evolve_bwd(_p(h), _p(target), _p(lengths), *[_p(t) for t in ts], _p(att), _p(states), _p(g_final), B, T,
                                     na, nh, ctx.mode, _p(dh), _p(dtarget), *[_p(o) for o in outs], _p(ws), _stream(h))
-        rets = [None if v is not None else o for o, v in zip(outs, vs)]
-        return (None, dh if ctx.needs_input_grad[1] else None, dtarget if ctx.needs_input_grad[2] else None, None, None, None,
-                *rets)
+        return _param_returns(ctx, {1: dh, 2: dtarget}, outs, vs)
 
 
 def _dien_check(what, B, T, na, nh, params, shapes, names):
@@ -3455,11 +3457,7 @@ def _dien_check(what, B, T, na, nh, params, shapes, names):
                          "(there is no fallback)")
     if B == 0:
         raise ValueError(f"{what}: empty batch")
-    ts, _ = _bst_split(params)
-    for t, shape, name in zip(ts, shapes, names):
-        _chk(t, torch.float32, f"{what}: {name}")
-        if tuple(t.shape) != shape:
-            raise ValueError(f"{what}: {name} has shape {tuple(t.shape)}, expected {shape}")
+    _check_param_shapes(what, _split_params(params)[0], shapes, names, chk=True)
 
 
 def _dien_lengths(lengths, B, what):
@@ -3483,8 +3481,7 @@ def dien_gru(x: torch.Tensor, lengths: Optional[torch.Tensor], Wg, bg, Wc, bc, a
     nh = int(bc_t.shape[0]) if bc_t.dim() == 1 else 0
     _dien_check("dien_gru", B, T, na, nh, params, [(na + nh, 2 * nh), (2 * nh,), (na + nh, nh), (nh,)], ("Wg", "bg", "Wc", "bc"))
     _chk(x, torch.float32, "dien_gru: x")
-    tensors = [None if isinstance(p, Variable) else p for p in params]
-    return _DienGruFn.apply(anchor, x, _dien_lengths(lengths, B, "dien_gru"), params, *tensors)
+    return _DienGruFn.apply(anchor, x, _dien_lengths(lengths, B, "dien_gru"), params, *_param_tail(params))
 
 
 def dien_evolve(h: torch.Tensor, target: torch.Tensor, lengths: torch.Tensor, w_att, Wg, bg, Wc, bc, mode: str = "AGRU",
@@ -3504,8 +3501,8 @@ def dien_evolve(h: torch.Tensor, target: torch.Tensor, lengths: torch.Tensor, w_
     _chk(target, torch.float32, "dien_evolve: target")
     if lengths is None:
         raise ValueError("dien_evolve: lengths are required")
-    tensors = [None if isinstance(p, Variable) else p for p in params]
-    return _DienEvolveFn.apply(anchor, h, target, _dien_lengths(lengths, B, "dien_evolve"), DIEN_MODES[mode], params, *tensors)
+    return _DienEvolveFn.apply(anchor, h, target, _dien_lengths(lengths, B, "dien_evolve"), DIEN_MODES[mode], params,
+                               *_param_tail(params))
 
 
 # =============================================================================================
@@ -3577,7 +3574,9 @@ def metrics_element_stride(t: torch.Tensor) -> Optional[int]:
         return 1
     if len(long_dims) == 1:
         return long_dims[0] if long_dims[0] >= 1 else None
-    return 1 if t.is_contiguous() else None
+    if t.is_contiguous():
+        return 1
+    return None
 
 
 def metrics_slot_table(slots):
